@@ -2,6 +2,10 @@
 """bench.py — ADMM iterations/sec of the MI355X-native SCS hot path + SpMV roofline.
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.
+  * A plain run does what the headline needs and nothing more: set up, warm up, time the K steps, write the outputs
+    (--dump-outputs DIR: x, y, s of the timed solve as DIR/<name>.npy), print the line.  Everything else below — the in-situ
+    kernel events inside the timed solve, the roofline, the steady window, the gather, the CPU baselines, the config-5 batch leg,
+    the other configs — runs with --full only; in a plain run those keys of the line are null.
   * N > 1 without a launcher (WORLD_SIZE unset): this process starts N ranks itself
     (`python -m torch.distributed.run --nproc-per-node N ... bench.py`, rendezvous on 127.0.0.1) BEFORE it
     touches the GPU, forwards rank 0's JSON line and exits with the children's code.  Under torchrun
@@ -50,6 +54,7 @@ for p in (ROOT, os.path.join(ROOT, "scs-python_amd")):
 HBM_PEAK = 8000.0      # GB/s, MI355X HBM3E spec (MI355X_MICROARCH.md)
 MFMA_F64_PEAK = 78.6   # TFLOP/s, MI355X fp64 matrix rate (spec, dense)
 STEADY_MARK, STEADY_SPAN = 105, 120
+DUMP_CAP_BYTES = 64 * 10 ** 6   # --dump-outputs: at most this much array data (the metric workload's x, y, s: 40 MB)
 
 
 def parse():
@@ -58,6 +63,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)     # the driver's values
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="target_lp_soc")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: in-situ kernel events, roofline, steady window, gather, CPU "
+                         "baselines, config-5 batch leg, other configs (the --no-* options below leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write x, y, s of the timed solve as DIR/<name>.npy (float64, rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=20)
     ap.add_argument("--cpu-cap-s", type=float, default=30.0, help="wall-clock cap of every CPU child (LDL' rungs, all-core CG)")
@@ -79,6 +89,20 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--force-device", type=int, default=None)
     return ap.parse_args()
+
+
+def dump_outputs(outdir, arrays, cap_bytes=DUMP_CAP_BYTES):
+    """outdir/<name>.npy in float64 for every named array; when they hold more than `cap_bytes` in all, each one is cut to a
+    sample of its entries in proportion to its size, at indices drawn from a fixed seed (the same ones in every run)"""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64).ravel() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > cap_bytes:
+            keep = a.size * cap_bytes // total
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def spmv_bytes(nnz, rows, cols):
@@ -250,7 +274,7 @@ def main():
             wsolver = scs.SCS(data, K, max_iters=warmup, **common)
             wsolver.solve()
         solver = scs.SCS(data, K, max_iters=steps, **common)
-        if not os.environ.get("BENCH_NO_INSITU"):
+        if args.full and not os.environ.get("BENCH_NO_INSITU"):
             solver._solver._set_profiling(True)
         # Quiet start: some 0.1-0.3 s after host pages that the runtime had pinned for a copy are released (the previous
         # workload's matrix, the generator's temporaries) the kernel driver evicts this process's queues for 30-80 ms — one
@@ -283,14 +307,40 @@ def main():
         info = sol["info"]
         assert info["iter"] == steps, (info["iter"], steps, info["status"])
         del wsolver
+        elapsed_max, total_iters = reduce_max_sum(elapsed, info["iter"])
+        _, total_cg = reduce_max_sum(elapsed, info["cg_iters"])
+        cg_per_s = total_cg / elapsed_max
+        line = {
+            "metric": "ADMM iters/sec (random %s cone program, indirect CG linsys, AA lookback 10)" % (
+                "LP+SOC" if "lp_soc" in workload else workload),
+            "value": round(total_iters / elapsed_max, 4),
+            "unit": "ADMM iters/s",
+            "n_gpus": world, "steps": steps, "warmup": warmup,
+            "ms_per_step": round(elapsed_max * 1e3 / steps, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {
+                "workload": "%s: m=%d n=%d nnz=%d cone=%s seed=%d(+rank); one independent instance per GPU" % (
+                    workload, m, n, nnz, cone_summary(K), seed),
+                "world_size_seen": world, "backend": args.dist_backend if world > 1 else None,
+                "cg_steps_per_admm_iter": round(info["cg_iters"] / max(info["iter"], 1), 2),
+                "cg_steps_per_s": round(cg_per_s, 1), "ms_per_cg_step": round(1e3 / cg_per_s * world, 4),
+                "admm_iters_timed": int(info["iter"]), "solve_ms_inside_scs_solve": round(info["solve_time"], 2),
+                "aa_extrapolations_in_timed_region": int(info["aa_stats"]["n_accept"]),
+                "lin_sys_ms": round(info["lin_sys_time"], 1), "cone_ms": round(info["cone_time"], 1),
+                "accel_ms": round(info["accel_time"], 1), "setup_ms": round(info["setup_time"], 1),
+                "gen_s": round(t_gen, 1), "gather_ms": None,
+            },
+            "steady_window": None,
+            "roofline": None,
+        }
+        if not args.full:
+            return line, data, K, sol
         psd_t = solver._solver._time_psd(reps=20)    # None unless the workload has PSD cones
         kt = solver._solver._kernel_times()          # in-situ samples (one CG step per host sync)
         kb = solver._solver._time_matvec(reps=30)    # back-to-back batch, event overhead amortised
-        elapsed_max, total_iters = reduce_max_sum(elapsed, info["iter"])
-        _, total_cg = reduce_max_sum(elapsed, info["cg_iters"])
 
         # ---------------- single RCCL gather of the solutions (outside the timed region) ----------------
-        gather_ms = None
         if gather and world > 1:
             if args.dist_backend == "nccl":  # the payload never visits the host: x | y | s straight from the solver's HBM buffers
                 payload = torch.empty(n + 2 * m, dtype=torch.float64, device=coll_dev)
@@ -304,6 +354,7 @@ def main():
             dist.gather(payload, bufs, dst=0)
             torch.cuda.synchronize()
             gather_ms = (time.perf_counter() - tg) * 1e3
+            line["config"]["gather_ms"] = gather_ms
             del bufs, payload
         del solver
 
@@ -409,38 +460,18 @@ def main():
                         "algorithmic_flops_per_launch": psd_t["ref_flops"], "avg_launch_ms": round(psd_t["ms"], 4),
                         "samples": kt["cone_n"], "ms_reprojecting_the_same_vector": psd_t.get("ms_same_vector"),
                         "spmv": {k_: spmv_roofline[k_] for k_ in ("k1", "k2")}}
-        cg_per_s = total_cg / elapsed_max
-        line = {
-            "metric": "ADMM iters/sec (random %s cone program, indirect CG linsys, AA lookback 10)" % (
-                "LP+SOC" if "lp_soc" in workload else workload),
-            "value": round(total_iters / elapsed_max, 4),
-            "unit": "ADMM iters/s",
-            "n_gpus": world, "steps": steps, "warmup": warmup,
-            "ms_per_step": round(elapsed_max * 1e3 / steps, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {
-                "workload": "%s: m=%d n=%d nnz=%d cone=%s seed=%d(+rank); one independent instance per GPU" % (
-                    workload, m, n, nnz, cone_summary(K), seed),
-                "world_size_seen": world, "backend": args.dist_backend if world > 1 else None,
-                "cg_steps_per_admm_iter": round(info["cg_iters"] / max(info["iter"], 1), 2),
-                "cg_steps_per_s": round(cg_per_s, 1), "ms_per_cg_step": round(1e3 / cg_per_s * world, 4),
-                "admm_iters_timed": int(info["iter"]), "solve_ms_inside_scs_solve": round(info["solve_time"], 2),
-                "aa_extrapolations_in_timed_region": int(info["aa_stats"]["n_accept"]),
-                "lin_sys_ms": round(info["lin_sys_time"], 1), "cone_ms": round(info["cone_time"], 1),
-                "accel_ms": round(info["accel_time"], 1), "setup_ms": round(info["setup_time"], 1),
-                "gen_s": round(t_gen, 1), "gather_ms": gather_ms,
-            },
-            "steady_window": steady_out,
-            "roofline": roofline,
-        }
-        return line, data, K
+        line["steady_window"] = steady_out
+        line["roofline"] = roofline
+        return line, data, K, sol
 
-    out, data, K = measure(args.workload, args.steps, args.warmup, steady=not args.no_steady, gather=True)
+    out, data, K, sol = measure(args.workload, args.steps, args.warmup, steady=not args.no_steady, gather=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x": sol["x"], "y": sol["y"], "s": sol["s"]})
+    del sol
 
     # ---------------- config 5: batch of independent small problems, sharded over the ranks ----------------
     batch_leg = None
-    if not args.no_batch:
+    if args.full and not args.no_batch:
         Kb, nb_, kb_, seedb = pg.workload("config5_small")
         NB = args.batch_problems
         mine = set(scs_batch.shard_indices(NB, rank, world))
@@ -514,7 +545,7 @@ def main():
 
     # ---------------- other BASELINE configs: one line each (N = 1) ----------------
     other = None
-    if world == 1 and not args.no_other_configs:
+    if world == 1 and args.full and not args.no_other_configs:
         other = []
         for wl, st, wu in (("config2_lp_soc", 100, 10), ("config3_mixed", 20, 3), ("config4_psd", 100, 5), ("target_qp", 20, 2),
                            ("powerlaw_lp", 20, 2), ("banded_lp", 20, 2)):
@@ -522,7 +553,7 @@ def main():
                 continue
             # config 4: the first 100 iterations run with the residual-tied PSD sweep level, later ones do not — the
             # line carries the window past iteration 100 and a whole solve next to the cold-start window
-            line, d4, K4 = measure(wl, st, wu, steady=(wl == "config4_psd"), gather=False)
+            line, d4, K4, _ = measure(wl, st, wu, steady=(wl == "config4_psd"), gather=False)
             if wl == "config4_psd":
                 ws4 = scs.SCS(d4, K4, verbose=False, acceleration_lookback=10, linear_solver=scs.LinearSolver.HIP_INDIRECT)
                 ws4._solver._set_profiling(True)  # in-situ events around the cone kernels of the queued iterations (as in the timed window)
@@ -606,7 +637,7 @@ def main():
 
     # ---------------- CPU baseline (oracle; bounded samples; everything observed in this run) ----------------
     cpu_baseline = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import scs_oracle  # the checker, timed beside the product; never in the product path
         ncores = os.cpu_count() or 1
         nquota = cpu_quota()

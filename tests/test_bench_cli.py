@@ -1,10 +1,12 @@
 """bench.py's command-line contract: `--gpus N` really runs N ranks (the process becomes the launcher when no
-launcher started it), and a world size that contradicts --gpus is an error rather than a silently wrong line."""
+launcher started it), and a world size that contradicts --gpus is an error rather than a silently wrong line; a plain run
+measures the headline alone, `--full` everything beside it, and `--dump-outputs` writes what the timed solve returned."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,6 +30,27 @@ def test_world_size_mismatch_is_refused():
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
 
 
+def test_dump_outputs_samples_past_the_cap(tmp_path):
+    """no GPU needed: under the cap every array is written whole in float64; over it each one keeps its share of the cap, at the
+    same indices in every call"""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    arrays = {"x": rng.standard_normal(1000), "y": rng.standard_normal(3000).astype(np.float32)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v.astype(np.float64))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, cap_bytes=8000)
+    sizes = 0
+    for k, v in arrays.items():
+        a, b = np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy"))
+        assert np.array_equal(a, b) and np.isin(a, v.astype(np.float64)).all()
+        sizes += a.nbytes
+    assert np.load(tmp_path / "a" / "x.npy").size == 250 and sizes <= 8000
+
+
 def _last_json(stdout):
     lines = [ln for ln in stdout.splitlines() if ln.startswith("{")]
     assert lines, stdout[-2000:]
@@ -39,7 +62,7 @@ def test_gpus_2_spawns_two_ranks_on_one_gpu_box():
     """`python bench.py --gpus 2` with no launcher: two ranks are started (torch.distributed.run), here both on device
     0 with the gloo backend (a 1-GPU box); rank 0 prints the one JSON line with n_gpus = 2 = the world size it saw,
     the batch leg covers every problem exactly once across the ranks."""
-    cmd = [sys.executable, BENCH, "--gpus", "2", "--steps", "20", "--warmup", "2", "--workload", "config2_lp_soc",
+    cmd = [sys.executable, BENCH, "--full", "--gpus", "2", "--steps", "20", "--warmup", "2", "--workload", "config2_lp_soc",
            "--dist-backend", "gloo", "--force-device", "0", "--batch-problems", "12", "--batch-threads", "4", "--no-other-configs"]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -59,7 +82,7 @@ def test_gpus_8_dry_run_on_one_gpu_box():
     """the plumbing of the driver's 8-GPU run, dry — 8 ranks (torch.distributed.run, gloo) on the ONE GPU of the
     box: the line says n_gpus = world size = 8, every problem of the batch is solved exactly once across the ranks (24 = 3 per
     rank), the gather happened, and a rank sets up CPU quota // 8 (>= 1) workspaces at a time (SURVEY 8e; BASELINE config 5)."""
-    cmd = [sys.executable, BENCH, "--gpus", "8", "--steps", "10", "--warmup", "1", "--workload", "small_lp_soc", "--no-steady",
+    cmd = [sys.executable, BENCH, "--full", "--gpus", "8", "--steps", "10", "--warmup", "1", "--workload", "small_lp_soc", "--no-steady",
            "--dist-backend", "gloo", "--force-device", "0", "--batch-problems", "24", "--no-other-configs"]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -81,7 +104,7 @@ def test_gpus_8_dry_run_on_one_gpu_box():
 
 @pytest.mark.gpu
 def test_single_gpu_line_has_every_leg():
-    cmd = [sys.executable, BENCH, "--steps", "20", "--warmup", "2", "--workload", "config2_lp_soc", "--cpu-iters", "3",
+    cmd = [sys.executable, BENCH, "--full", "--steps", "20", "--warmup", "2", "--workload", "config2_lp_soc", "--cpu-iters", "3",
            "--batch-problems", "8", "--batch-threads", "4", "--cpu-cap-s", "12", "--no-other-configs"]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -117,7 +140,7 @@ def test_single_gpu_line_has_every_leg():
 def test_other_configs_lines_and_ungrouped_batch_leg():
     """the lines of BASELINE configs 2-4 that ride along with the default run (config 3 with its box cone, config 4 with
     the MFMA roofline), and the one-problem-per-stream batch mode kept for A/B"""
-    cmd = [sys.executable, BENCH, "--steps", "10", "--warmup", "1", "--workload", "small_lp_soc", "--no-cpu-baseline", "--no-steady",
+    cmd = [sys.executable, BENCH, "--full", "--steps", "10", "--warmup", "1", "--workload", "small_lp_soc", "--no-cpu-baseline", "--no-steady",
            "--batch-problems", "6", "--batch-threads", "3", "--batch-ungrouped"]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -132,3 +155,28 @@ def test_other_configs_lines_and_ungrouped_batch_leg():
     assert oc[-1]["roofline"]["frac"] > oc[0]["roofline"]["frac"]  # gathers with locality: the ceiling of the decomposition
     assert oc[4]["roofline"]["bound"] == "hbm" and "row lengths" in oc[4]["config"]["why_this_line"]  # power-law rows: the pass layout is kept
     assert out["config5_batch"]["solved"] == 6 and "one problem per stream" in out["config5_batch"]["workload"]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_alone_and_dumps_what_full_computes(tmp_path):
+    """a plain run: the headline line with --steps timed steps and nothing beside it; its outputs are the arrays of the timed solve,
+    bit for bit what a --full run (in-situ kernel events inside the timed solve) computes on the same inputs"""
+    base = [sys.executable, BENCH, "--gpus", "1", "--steps", "7", "--warmup", "2", "--workload", "small_lp_soc"]
+    r = subprocess.run(base + ["--dump-outputs", str(tmp_path / "plain")], env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _last_json(r.stdout)
+    assert out["steps"] == 7 and out["config"]["admm_iters_timed"] == 7 and out["warmup"] == 2
+    assert out["unit"] == "ADMM iters/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["ms_per_step"] > 0 and abs(out["value"] - 1e3 / out["ms_per_step"]) < 1e-2 * out["value"]
+    for key in ("steady_window", "roofline", "cpu_baseline", "config5_batch", "other_configs"):
+        assert out[key] is None, key
+    r = subprocess.run(base + ["--full", "--no-steady", "--no-cpu-baseline", "--no-batch", "--no-other-configs",
+                               "--dump-outputs", str(tmp_path / "full")], env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    full = _last_json(r.stdout)
+    assert full["roofline"]["samples"] > 0 and full["steps"] == 7
+    m = 2000 + 10 * 200   # small_lp_soc: n = 2000, K = {l: 2000, q: 200 x 10}
+    for name, size in (("x", 2000), ("y", m), ("s", m)):
+        a, b = np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))
+        assert a.dtype == np.float64 and a.shape == (size,) and np.isfinite(a).all()
+        assert np.array_equal(a, b), name

@@ -1,77 +1,41 @@
-"""the reference's OWN CPython glue, read where it lies (`/root/reference/scs/scspy.c` with
-`scsmodule.h` / `scsobject.h`), compiles against this repo's `include/` (glbopts.h, scs.h, scs_types.h) and links
-against `libscs_hip.so` — unchanged.  The build goes to a temporary directory (nothing of the reference enters the
-repo or travels to the GPU box); skipped where `/root/reference` does not exist.
+"""the reference's OWN CPython glue (`scs/scspy.c` with `scsmodule.h` / `scsobject.h`) compiles against this
+repo's `include/` (glbopts.h, scs.h, scs_types.h) and links against `libscs_hip.so` — unchanged.  build() compiles it into
+oracle/_ref/ (oracle/ref_glue.py: nothing of the reference enters the repo); skipped where build() had no reference tree to compile.
 
-The only test-local piece is a backport header for three CPython 3.13 functions the glue takes from the
-`pythoncapi-compat` submodule (empty in the snapshot; `R:scs/scsobject.h:1,112,154,168`) — this image has CPython 3.10.
+The only local piece is a backport header for three CPython 3.13 functions the glue takes from the `pythoncapi-compat` submodule
+(empty in the snapshot; `R:scs/scsobject.h:1,112,154,168`): oracle/ref_compat/.
 Without a GPU `scs_init` returns NULL, so what can run here is everything the glue does BEFORE the core is entered
 plus the failure path: module surface, argument parsing and its messages, and "ScsWork allocation error!".
 """
 import importlib.util
 import os
-import subprocess
-import sys
-import sysconfig
 
 import numpy as np
 import pytest
 from scipy import sparse
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/scs"
-LIBDIR = os.path.join(ROOT, "scs-python_amd", "scs")
+from oracle import ref_glue
 
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "scspy.c")),
-                                reason="the reference tree is only present in the build container")
-
-COMPAT = r"""
-#include <Python.h>
-#if PY_VERSION_HEX < 0x030D0000
-static inline int PyDict_GetItemStringRef(PyObject *d, const char *k, PyObject **out) {
-  PyObject *key = PyUnicode_FromString(k);
-  if (!key) { *out = NULL; return -1; }
-  PyObject *v = PyDict_GetItemWithError(d, key);
-  Py_DECREF(key);
-  if (v) { Py_INCREF(v); *out = v; return 1; }
-  *out = NULL;
-  return PyErr_Occurred() ? -1 : 0;
-}
-static inline PyObject *PyList_GetItemRef(PyObject *l, Py_ssize_t i) {
-  PyObject *v = PyList_GetItem(l, i);
-  Py_XINCREF(v);
-  return v;
-}
-#endif
-"""
+pytestmark = pytest.mark.skipif(not os.path.exists(ref_glue.LOG),
+                                reason="oracle/_ref has no build of the reference glue: build() found no reference tree")
 
 
-def _cc_args(tmp):
-    os.makedirs(os.path.join(tmp, "pythoncapi-compat"), exist_ok=True)
-    with open(os.path.join(tmp, "pythoncapi-compat", "pythoncapi_compat.h"), "w") as f:
-        f.write(COMPAT)
-    return ["-I", os.path.join(ROOT, "include"), "-idirafter", str(tmp),
-            "-I", sysconfig.get_paths()["include"], "-I", np.get_include(),
-            "-DCTRLC=1", "-DCOPYAMATRIX=1"]      # the defines every backend target passes, R:meson.build:288-313
+def _build_log():
+    with open(ref_glue.LOG) as f:
+        return f.read()[-3000:]
 
 
-def test_reference_glue_compiles_against_include(tmp_path):
-    """`gcc -fsyntax-only` of the glue: every type, field, macro and function it names exists in include/."""
-    r = subprocess.run(["gcc", "-fsyntax-only", "-Werror=implicit-function-declaration", os.path.join(REF, "scspy.c")]
-                       + _cc_args(tmp_path), capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+def test_reference_glue_compiles_against_include():
+    """build() compiled the glue with -Werror=implicit-function-declaration (it recompiles it every time): every type, field,
+    macro and function it names exists in include/."""
+    assert os.path.exists(ref_glue.MODULE), _build_log()
 
 
 @pytest.fixture(scope="module")
-def glue(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp("refglue")
-    so = os.path.join(tmp, "_scs_direct" + sysconfig.get_config_var("EXT_SUFFIX"))   # default module name, R:scs/scsmodule.h:98-99
-    cmd = (["gcc", "-shared", "-fPIC", "-O1", "-o", so, os.path.join(REF, "scspy.c")] + _cc_args(tmp)
-           + ["-L", LIBDIR, "-lscs_hip", "-Wl,-rpath," + LIBDIR])
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+def glue():
+    assert os.path.exists(ref_glue.MODULE), _build_log()
     from scs import _scs_hip  # noqa: F401  (preloads the HIP runtime the library links against)
-    spec = importlib.util.spec_from_file_location("_scs_direct", so)
+    spec = importlib.util.spec_from_file_location("_scs_direct", ref_glue.MODULE)
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 for w in 3 2 1 3 2 1; do
   echo "== SCS_HIP_CHUNK_WINDOW=$w"
-  SCS_HIP_CHUNK_WINDOW=$w python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-batch --no-other-configs 2>/dev/null | python -c '
+  SCS_HIP_CHUNK_WINDOW=$w python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-batch --no-other-configs 2>/dev/null | python -c '
 import json, sys
 for line in sys.stdin:
     line = line.strip()

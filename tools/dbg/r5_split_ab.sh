@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 run() {
   echo "== $1"
   shift
-  env "$@" python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-batch --no-other-configs --no-steady 2>/dev/null | python -c '
+  env "$@" python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-batch --no-other-configs --no-steady 2>/dev/null | python -c '
 import json, sys
 for line in sys.stdin:
     line = line.strip()

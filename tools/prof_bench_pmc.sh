@@ -13,6 +13,6 @@ GROUPS_LIST=${PMC_GROUPS:-"FETCH_SIZE|WRITE_SIZE|TCC_HIT_sum TCC_MISS_sum|GRBM_G
 IFS='|' read -ra GR <<< "$GROUPS_LIST"
 for c in "${GR[@]}"; do
   d=$O/$(echo $c | tr ' ' '_')
-  timeout ${PROF_TIMEOUT:-240} rocprofv3 --pmc $c -d $d -o run -- python3 bench.py --no-cpu-baseline --no-batch --no-steady --no-other-configs --steps 20 --warmup 2 "$@" > $d.log 2>&1
+  timeout ${PROF_TIMEOUT:-240} rocprofv3 --pmc $c -d $d -o run -- python3 bench.py --full --no-cpu-baseline --no-batch --no-steady --no-other-configs --steps 20 --warmup 2 "$@" > $d.log 2>&1
   python3 tools/rocpd_summary.py --executed $(find $d -name "*.db" | head -1) | grep -E "^==|k_spmv_cs_il<Epi(DivR|Gp),"
 done

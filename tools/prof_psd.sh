@@ -8,7 +8,7 @@ cd $GRAFT_REPO_ROOT
 T=$1
 O=gpurun_out/psd_$T
 mkdir -p $O
-ARGS="--workload config4_psd --steps 100 --warmup 5 --no-cpu-baseline --no-batch --no-steady --no-other-configs"
+ARGS="--full --workload config4_psd --steps 100 --warmup 5 --no-cpu-baseline --no-batch --no-steady --no-other-configs"
 timeout ${PROF_TIMEOUT:-300} rocprofv3 --kernel-trace --stats -d $O/trace -o run -- python3 bench.py $ARGS > $O/trace.log 2>&1
 tail -1 $O/trace.log | cut -c1-1500
 python3 tools/rocpd_summary.py $(find $O/trace -name "*.db" | head -1) > $O/summary.txt 2>&1
