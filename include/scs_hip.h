@@ -202,6 +202,22 @@ int scs_hip_psd_refine_stats(ScsWork *w, double *out, int cap);
 /* last error message of the calling thread ("" if none) */
 const char *scs_hip_last_error(void);
 
+/* ------------------------------------------------------- spectral cones
+ * The same entry points for a cone that carries the spectral fields of ScsCone (scs_types.h, USE_SPECTRAL_CONES): they
+ * read the whole struct, the plain names above read it only up to psize.  A consumer compiled with -DUSE_SPECTRAL_CONES
+ * reaches them through the plain names (the remapping below); one compiled without the flag keeps the short struct and
+ * the plain entries.  INTEGRATION.md §B. */
+#if defined(USE_SPECTRAL_CONES)
+ScsWork *scs_init_spectral(const ScsData *d, const ScsCone *k, const ScsSettings *stgs);
+ScsWork *scs_hip_init_linsys_spectral(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys);
+int scs_hip_proj_cone_spectral(scs_float *x, const ScsCone *k, scs_int m, int dual);
+#if !defined(SCS_HIP_BUILDING_LIBRARY)
+#define scs_init scs_init_spectral
+#define scs_hip_init_linsys scs_hip_init_linsys_spectral
+#define scs_hip_proj_cone scs_hip_proj_cone_spectral
+#endif
+#endif
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,21 @@ typedef struct {
   scs_int ed;    /* dual exponential triples                 :746     */
   scs_float *p;  /* power cone exponents in [-1,1], <0 dual  :738     */
   scs_int psize;
+#ifdef USE_SPECTRAL_CONES
+  /* spectral cones, rows after p in the order d, nuc, ell1, sl (R:scs/scsobject.h:751-794).  Present only when the
+   * consumer is compiled with -DUSE_SPECTRAL_CONES; scs_hip.h then routes it to the entry points that read them
+   * (INTEGRATION.md §B).  Without the flag the struct ends at psize, as it always has. */
+  scs_int *d;     /* log-det cones (t, v, svec X), X of order d[i]: n(n+1)/2 + 2 rows  */
+  scs_int dsize;
+  scs_int *nuc_m; /* nuclear-norm cones (t, vec X), X nuc_m[i] x nuc_n[i] column-major: m n + 1 rows */
+  scs_int *nuc_n;
+  scs_int nucsize;
+  scs_int *ell1;  /* ell1-norm cones (t, x), x of length ell1[i]: n + 1 rows          */
+  scs_int ell1_size;
+  scs_int *sl_n;  /* sum-of-k-largest-eigenvalues cones (t, svec X), order sl_n[i], k = sl_k[i]: n(n+1)/2 + 1 rows */
+  scs_int *sl_k;
+  scs_int sl_size;
+#endif
 } ScsCone;
 
 /* Settings.  Keyword table R:scs/scsobject.h:467-495, parsed into these

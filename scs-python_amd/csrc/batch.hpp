@@ -245,6 +245,7 @@ struct GroupSolve {
     if (w->has_P && (w->Pf.cs.ok || w->Pf.has_slab)) return false;
     if (w->persist_wgs > 0 || !w->log_csv_filename.empty() || w->mark_iter >= 0 || w->stgs.verbose) return false;  // (a verbose member prints its own table: solved by scs_solve)
     if (w->n_psd_big > 0 || w->n_cs > 0 || w->n_soc_big > 0 || w->cone.bsize > kBoxMultiMin) return false;
+    if (w->cone.has_spectral()) return false;  // spectral cones (spectral.hpp) have no grouped kernels: solved by scs_solve
     if (w->aa.mem > 0 && !w->aa.tsqr) return false;
     return true;
   }

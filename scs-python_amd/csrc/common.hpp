@@ -13,6 +13,13 @@
 #include <utility>
 #include <vector>
 
+// the library reads the whole ScsCone, spectral fields included, and defines both the plain and the *_spectral entry points
+#ifndef USE_SPECTRAL_CONES
+#define USE_SPECTRAL_CONES
+#endif
+#ifndef SCS_HIP_BUILDING_LIBRARY
+#define SCS_HIP_BUILDING_LIBRARY
+#endif
 #include "../../include/scs_hip.h"
 #include "options.hpp"
 

@@ -11,8 +11,15 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <string>
 #include <vector>
 
+#ifndef USE_SPECTRAL_CONES
+#define USE_SPECTRAL_CONES
+#endif
+#ifndef SCS_HIP_BUILDING_LIBRARY
+#define SCS_HIP_BUILDING_LIBRARY
+#endif
 #include "../../include/scs_hip.h"
 
 namespace scship {
@@ -28,14 +35,61 @@ struct HostCone {
   int z = 0, l = 0, bsize = 0, ep = 0, ed = 0;
   std::vector<double> bu, bl, p;
   std::vector<int> q, s, cs;
-  std::vector<int> boundaries;  // [z+l+bsize, q..., s(s+1)/2..., cs^2..., 3 x (ep+ed+psize)]
+  // spectral cones (spectral.hpp), after p in the order d, nuc, ell1, sl
+  std::vector<int> d, nuc_m, nuc_n, ell1, sl_n, sl_k;
+  std::vector<int> boundaries;  // [z+l+bsize, q..., s(s+1)/2..., cs^2..., 3 x (ep+ed+psize), d..., nuc..., ell1..., sl...]
   int m = 0;
   int off_box = 0, off_q = 0, off_s = 0, off_cs = 0, off_ep = 0, off_ed = 0, off_p = 0;
+  int off_d = 0, off_nuc = 0, off_ell1 = 0, off_sl = 0;
+  bool has_spectral() const { return !d.empty() || !nuc_m.empty() || !ell1.empty() || !sl_n.empty(); }
 };
+
+// limits of the spectral kernels (spectral.hpp: everything of one matrix in the LDS of one workgroup); INTEGRATION.md "Limits"
+constexpr int kSpectralMaxOrder = 64;       // d, sl: order; nuc: min(m, n)
+constexpr int kSpectralNucMaxElems = 8192;  // nuc: m n
+
+// the spectral fields of k (ABI: include/scs_types.h; entry points for consumers built without them pass a cone whose spectral
+// fields are zero).  Returns "" or the reason the cone is refused.
+inline std::string spectral_cone_error(const ScsCone *k) {
+  if (k->dsize < 0 || k->nucsize < 0 || k->ell1_size < 0 || k->sl_size < 0) return "negative spectral cone count";
+  if ((k->dsize && !k->d) || (k->nucsize && (!k->nuc_m || !k->nuc_n)) || (k->ell1_size && !k->ell1) ||
+      (k->sl_size && (!k->sl_n || !k->sl_k)))
+    return "spectral cone count without its array";
+  for (int i = 0; i < k->dsize; ++i) {
+    if (k->d[i] < 1) return "log-det cone d[" + std::to_string(i) + "] = " + std::to_string(k->d[i]) + ": order must be >= 1";
+    if (k->d[i] > kSpectralMaxOrder)
+      return "log-det cone d[" + std::to_string(i) + "] = " + std::to_string(k->d[i]) + " exceeds the supported order " +
+             std::to_string(kSpectralMaxOrder);
+  }
+  for (int i = 0; i < k->nucsize; ++i) {
+    const long a = k->nuc_m[i], b = k->nuc_n[i];
+    const std::string nm = "nuclear-norm cone " + std::to_string(i) + " (" + std::to_string(a) + " x " + std::to_string(b) + ")";
+    if (a < 1 || b < 1) return nm + ": sizes must be >= 1";
+    if (std::min(a, b) > kSpectralMaxOrder) return nm + ": min(m, n) exceeds " + std::to_string(kSpectralMaxOrder);
+    if (a * b > kSpectralNucMaxElems) return nm + ": m n exceeds " + std::to_string(kSpectralNucMaxElems);
+  }
+  for (int i = 0; i < k->ell1_size; ++i)
+    if (k->ell1[i] < 1) return "ell1 cone " + std::to_string(i) + ": length must be >= 1";
+  for (int i = 0; i < k->sl_size; ++i) {
+    const int n = k->sl_n[i], kk = k->sl_k[i];
+    const std::string nm = "sum-of-largest cone " + std::to_string(i) + " (n = " + std::to_string(n) + ", k = " + std::to_string(kk) + ")";
+    if (n < 1) return nm + ": order must be >= 1";
+    if (n > kSpectralMaxOrder) return nm + ": order exceeds the supported order " + std::to_string(kSpectralMaxOrder);
+    if (kk < 1 || kk > n) return nm + ": k must satisfy 1 <= k <= n";
+  }
+  return "";
+}
 
 inline long sd_size(long s) { return s * (s + 1) / 2; }
 
-inline bool build_cone(const ScsCone *k, HostCone &c) {
+inline bool build_cone(const ScsCone *k, HostCone &c, std::string *why = nullptr) {
+  {
+    const std::string e = spectral_cone_error(k);
+    if (!e.empty()) {
+      if (why) *why = e;
+      return false;
+    }
+  }
   if (k->z < 0 || k->l < 0 || k->bsize < 0 || k->ep < 0 || k->ed < 0) return false;
   if (k->qsize < 0 || k->ssize < 0 || k->psize < 0 || k->cssize < 0) return false;
   c.z = k->z; c.l = k->l; c.bsize = k->bsize; c.ep = k->ep; c.ed = k->ed;
@@ -61,6 +115,16 @@ inline bool build_cone(const ScsCone *k, HostCone &c) {
   c.off_ep = (int)cnt; cnt += 3L * c.ep;
   c.off_ed = (int)cnt; cnt += 3L * c.ed;
   c.off_p = (int)cnt; cnt += 3L * (long)c.p.size();
+  c.d.assign(k->d, k->d + k->dsize);
+  c.nuc_m.assign(k->nuc_m, k->nuc_m + k->nucsize);
+  c.nuc_n.assign(k->nuc_n, k->nuc_n + k->nucsize);
+  c.ell1.assign(k->ell1, k->ell1 + k->ell1_size);
+  c.sl_n.assign(k->sl_n, k->sl_n + k->sl_size);
+  c.sl_k.assign(k->sl_k, k->sl_k + k->sl_size);
+  c.off_d = (int)std::min(cnt, 2000000001L); for (int v : c.d) cnt += sd_size(v) + 2;
+  c.off_nuc = (int)std::min(cnt, 2000000001L); for (size_t i = 0; i < c.nuc_m.size(); ++i) cnt += (long)c.nuc_m[i] * c.nuc_n[i] + 1;
+  c.off_ell1 = (int)std::min(cnt, 2000000001L); for (int v : c.ell1) cnt += (long)v + 1;
+  c.off_sl = (int)std::min(cnt, 2000000001L); for (int v : c.sl_n) cnt += sd_size(v) + 1;
   if (cnt > 2000000000L) return false;
   c.m = (int)cnt;
   c.boundaries.clear();
@@ -69,6 +133,11 @@ inline bool build_cone(const ScsCone *k, HostCone &c) {
   for (int s : c.s) c.boundaries.push_back((int)sd_size(s));
   for (int s : c.cs) c.boundaries.push_back(s * s);
   for (int i = 0; i < c.ep + c.ed + (int)c.p.size(); ++i) c.boundaries.push_back(3);
+  // none of the spectral cones is invariant under per-row scaling: one boundary (one averaged row scale) per cone
+  for (int v : c.d) c.boundaries.push_back((int)sd_size(v) + 2);
+  for (size_t i = 0; i < c.nuc_m.size(); ++i) c.boundaries.push_back(c.nuc_m[i] * c.nuc_n[i] + 1);
+  for (int v : c.ell1) c.boundaries.push_back(v + 1);
+  for (int v : c.sl_n) c.boundaries.push_back((int)sd_size(v) + 1);
   return true;
 }
 

@@ -8,6 +8,7 @@
 // can be replayed.  Layout: magic "SCSHIP01", then records  <u32 tag><u64 count><payload>  with tags
 // 1 dims(i32 m,n) 2 settings(f64 x 16, field order of ScsSettings without the file names) 3 cone scalars (i32 z,l,bsize,ep,ed)
 // 4 bu 5 bl 6 q 7 s 8 p 9 b 10 c 11 A.x 12 A.i 13 A.p 14 P.x 15 P.i 16 P.p 17 cs  (f64 or i32 arrays).
+// Spectral cones, only when present: 18 d 19 nuc_m 20 nuc_n 21 ell1 22 sl_n 23 sl_k (i32 arrays).
 static void write_record(FILE *f, unsigned tag, const void *ptr, size_t count, size_t elem) {
   const unsigned long long c = count;
   std::fwrite(&tag, sizeof(tag), 1, f);
@@ -34,6 +35,16 @@ static void write_problem_data(const char *fname, const ScsData *d, const ScsCon
   write_record(f, 7, k->s, (size_t)k->ssize, sizeof(int));
   write_record(f, 8, k->p, (size_t)k->psize, sizeof(double));
   if (k->cssize) write_record(f, 17, k->cs, (size_t)k->cssize, sizeof(int));
+  if (k->dsize) write_record(f, 18, k->d, (size_t)k->dsize, sizeof(int));
+  if (k->nucsize) {
+    write_record(f, 19, k->nuc_m, (size_t)k->nucsize, sizeof(int));
+    write_record(f, 20, k->nuc_n, (size_t)k->nucsize, sizeof(int));
+  }
+  if (k->ell1_size) write_record(f, 21, k->ell1, (size_t)k->ell1_size, sizeof(int));
+  if (k->sl_size) {
+    write_record(f, 22, k->sl_n, (size_t)k->sl_size, sizeof(int));
+    write_record(f, 23, k->sl_k, (size_t)k->sl_size, sizeof(int));
+  }
   write_record(f, 9, d->b, (size_t)d->m, sizeof(double));
   write_record(f, 10, d->c, (size_t)d->n, sizeof(double));
   write_record(f, 11, d->A->x, (size_t)d->A->p[d->n], sizeof(double));

@@ -210,7 +210,9 @@ double scs_hip_spmv_bench(const ScsMatrix *A, int transpose, int reps) {
 // of the GPU — opened every barrier of the launch and left garbage; the call is then repeated from its inputs with one workgroup per
 // matrix, the path a solve takes after a SpinTimeout.
 static void oneshot_cone_work(ScsHipWork &w, const ScsCone *k, scs_int m, int warm, hipStream_t s, bool no_spin) {
-  if (!build_cone(k, w.cone) || w.cone.m != m) throw std::runtime_error("invalid cone");
+  std::string why;
+  if (!k || !build_cone(k, w.cone, &why)) throw std::runtime_error(why.empty() ? "invalid cone" : "invalid cone: " + why);
+  if (w.cone.m != m) throw std::runtime_error("invalid cone");
   int dev = 0;
   HIP_CHECK(hipGetDevice(&dev));
   w.device = dev;  // (spin_chain(), the occupancy query of psd_mc_members)
@@ -232,7 +234,7 @@ static bool oneshot_spin_error(ScsHipWork &w, hipStream_t s) {  // the stream is
   return err != 0;
 }
 
-int scs_hip_proj_cone(scs_float *x, const ScsCone *k, scs_int m, int dual) {
+static int proj_cone_impl(scs_float *x, const ScsCone *k, scs_int m, int dual) {
   try {
     set_last_error("");
     refresh_options();
@@ -264,7 +266,15 @@ int scs_hip_proj_cone(scs_float *x, const ScsCone *k, scs_int m, int dual) {
   }
 }
 
-int scs_hip_proj_cone_seq(scs_float *xs, const ScsCone *k, scs_int m, int dual, int count, scs_float *stats, int stats_cap) {
+int scs_hip_proj_cone(scs_float *x, const ScsCone *k, scs_int m, int dual) {
+  const ScsCone kk = short_cone(k);
+  return proj_cone_impl(x, k ? &kk : nullptr, m, dual);
+}
+int scs_hip_proj_cone_spectral(scs_float *x, const ScsCone *k, scs_int m, int dual) { return proj_cone_impl(x, k, m, dual); }
+
+int scs_hip_proj_cone_seq(scs_float *xs, const ScsCone *k_in, scs_int m, int dual, int count, scs_float *stats, int stats_cap) {
+  const ScsCone k_short = short_cone(k_in);
+  const ScsCone *k = k_in ? &k_short : nullptr;
   try {
     set_last_error("");
     refresh_options();
@@ -395,7 +405,8 @@ int scs_hip_normalize(ScsMatrix *A, ScsMatrix *P, scs_float *b, scs_float *c, co
     set_last_error("");
     refresh_options();
     HostCone cone;
-    if (!build_cone(k, cone) || cone.m != A->m) throw std::runtime_error("invalid cone");
+    const ScsCone kk = short_cone(k);
+    if (!k || !build_cone(&kk, cone) || cone.m != A->m) throw std::runtime_error("invalid cone");
     if (!validate_matrix(A, A->m, A->n)) throw std::runtime_error("invalid A");
     TmpStream ts;
     hipStream_t s = ts.s;

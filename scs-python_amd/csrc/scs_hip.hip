@@ -15,6 +15,7 @@
 //   rsk = R (v + u - 2 u_t)   (only when residuals are needed)
 //   v  += alpha (u - u_t)
 #include <atomic>
+#include <cstddef>
 #include <chrono>
 #include <csignal>
 #include <functional>
@@ -29,6 +30,7 @@
 #include "host_setup.hpp"
 #include "normalize_dev.hpp"
 #include "psd.hpp"
+#include "spectral.hpp"
 #ifdef SCS_HIP_LABS  // experiments that lost their measurement (options.hpp): compiled into libscs_hip_labs.so only
 #include "cg_persist.hpp"
 #include "minres.hpp"
@@ -51,9 +53,43 @@
 #include "batch.hpp"
 
 // ================================================================ C ABI
+// A consumer compiled without USE_SPECTRAL_CONES hands over a ScsCone that ends at psize: the plain entry points copy that
+// prefix and nothing beyond it (the spectral fields of the copy are zero).
+static ScsCone short_cone(const ScsCone *k) {
+  ScsCone c;
+  std::memset(&c, 0, sizeof(c));
+  if (k) std::memcpy(&c, k, offsetof(ScsCone, d));
+  return c;
+}
+
 extern "C" {
 
 ScsWork *scs_init(const ScsData *d, const ScsCone *k, const ScsSettings *stgs) {
+  try {
+    set_last_error("");
+    refresh_options();
+    const ScsCone kk = short_cone(k);
+    return init_impl(d, k ? &kk : nullptr, stgs);
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return nullptr;
+  }
+}
+
+ScsWork *scs_hip_init_linsys(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys) {
+  try {
+    set_last_error("");
+    refresh_options();
+    const ScsCone kk = short_cone(k);
+    return init_impl(d, k ? &kk : nullptr, stgs, linsys);
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return nullptr;
+  }
+}
+
+// the entries for consumers built with USE_SPECTRAL_CONES (include/scs_hip.h): the whole struct
+ScsWork *scs_init_spectral(const ScsData *d, const ScsCone *k, const ScsSettings *stgs) {
   try {
     set_last_error("");
     refresh_options();
@@ -64,7 +100,7 @@ ScsWork *scs_init(const ScsData *d, const ScsCone *k, const ScsSettings *stgs) {
   }
 }
 
-ScsWork *scs_hip_init_linsys(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys) {
+ScsWork *scs_hip_init_linsys_spectral(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys) {
   try {
     set_last_error("");
     refresh_options();

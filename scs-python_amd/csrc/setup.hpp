@@ -85,6 +85,47 @@ static void upload_cone_meta(ScsHipWork *w) {
     w->cs_stage.alloc_zero((size_t)std::max(stot, 1L), s);
   }
   if (w->n_psd || w->n_cs) w->psd_scratch.alloc_zero((size_t)std::max(wtot, 1L), s);
+  if (c.has_spectral()) {  // spectral cones: offsets and sizes per kind in one block (spectral.hpp SpecBatch)
+    std::vector<int> meta;
+    auto put = [&](const std::vector<int> &v) { const size_t at = meta.size(); meta.insert(meta.end(), v.begin(), v.end()); return at; };
+    std::vector<int> off;
+    int max_sl = 0, max_d = 0, max_rc = 0, max_c = 0;
+    std::vector<int> loff, ln, sn;
+    o = c.off_ell1;
+    for (int v : c.ell1) {
+      (v > kSpecEll1WaveMax ? loff : off).push_back(o);
+      (v > kSpecEll1WaveMax ? ln : sn).push_back(v);
+      o += v + 1;
+    }
+    const size_t e_off = put(off), e_n = put(sn), el_off = put(loff), el_n = put(ln);
+    off.clear();
+    o = c.off_sl;
+    for (int v : c.sl_n) { off.push_back(o); o += (int)sd_size(v) + 1; max_sl = std::max(max_sl, v); }
+    const size_t s_off = put(off), s_n = put(c.sl_n), s_k = put(c.sl_k);
+    off.clear();
+    o = c.off_d;
+    for (int v : c.d) { off.push_back(o); o += (int)sd_size(v) + 2; max_d = std::max(max_d, v); }
+    const size_t d_off = put(off), d_n = put(c.d);
+    off.clear();
+    o = c.off_nuc;
+    for (size_t i = 0; i < c.nuc_m.size(); ++i) {
+      off.push_back(o);
+      o += c.nuc_m[i] * c.nuc_n[i] + 1;
+      max_rc = std::max(max_rc, c.nuc_m[i] * c.nuc_n[i]);
+      max_c = std::max(max_c, std::min(c.nuc_m[i], c.nuc_n[i]));
+    }
+    const size_t u_off = put(off), u_m = put(c.nuc_m), u_n = put(c.nuc_n);
+    w->spec_meta.upload(meta.data(), meta.size(), s);
+    const int *mp = w->spec_meta.p;
+    w->spec_ell1 = SpecBatch{mp + e_off, mp + e_n, nullptr, (int)sn.size()};
+    w->spec_ell1_long = SpecBatch{mp + el_off, mp + el_n, nullptr, (int)ln.size()};
+    w->spec_sl = SpecBatch{mp + s_off, mp + s_n, mp + s_k, (int)c.sl_n.size()};
+    w->spec_d = SpecBatch{mp + d_off, mp + d_n, nullptr, (int)c.d.size()};
+    w->spec_nuc = SpecBatch{mp + u_off, mp + u_m, mp + u_n, (int)c.nuc_m.size()};
+    w->spec_sl_lds = spec_eig_lds_bytes(max_sl);
+    w->spec_d_lds = spec_eig_lds_bytes(max_d);
+    w->spec_nuc_lds = spec_nuc_lds_bytes(max_rc, max_c);
+  }
   {
     int big_total = 0, max_order = 0;
     for (int sdim : c.s)
@@ -122,7 +163,10 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
 
   std::unique_ptr<ScsHipWork> w(new ScsHipWork());
   w->device = current_device();
-  if (!build_cone(k, w->cone)) throw std::runtime_error("invalid cone");
+  {
+    std::string why;
+    if (!build_cone(k, w->cone, &why)) throw std::runtime_error(why.empty() ? "invalid cone" : "invalid cone: " + why);
+  }
   if (w->cone.m != d->m) throw std::runtime_error("cone dimensions do not match m");
   const int n = d->n, m = d->m;
   if (linsys == 2 && n > kDenseMaxN)

@@ -177,6 +177,24 @@ struct ScsHipWork {
   DevBuf<long> cs_soff, cs_woff;
   DevBuf<double> cs_stage;
   int n_cs = 0, n_cs_big = 0;
+  // spectral cones (spectral.hpp): one SpecBatch per kind, uploaded by upload_cone_meta; everything else lives in LDS
+  DevBuf<int> spec_meta;  // [ell1 off | n] [long ell1 off | n] [sl off | n | k] [d off | n] [nuc off | m | n]
+  SpecBatch spec_ell1{}, spec_ell1_long{}, spec_sl{}, spec_d{}, spec_nuc{};
+  size_t spec_sl_lds = 0, spec_d_lds = 0, spec_nuc_lds = 0;
+  // one launch per kind (ell1: one for the short and one for the long cones), whatever the number of cones
+  void launch_spectral(double *y, int dual) {
+    if (spec_d.count > 0)
+      hipLaunchKernelGGL(k_proj_eig_cone, dim3(spec_d.count), dim3(kSpecThreads), spec_d_lds, stream, y, spec_d, 1, dual, stall);
+    if (spec_nuc.count > 0)
+      hipLaunchKernelGGL(k_proj_nuc, dim3(spec_nuc.count), dim3(kSpecThreads), spec_nuc_lds, stream, y, spec_nuc, dual, stall);
+    if (spec_ell1.count > 0)
+      hipLaunchKernelGGL(k_proj_ell1, dim3(ceil_div(spec_ell1.count, kSpecThreads / kWave)), dim3(kSpecThreads), 0, stream, y, spec_ell1,
+                         dual, stall);
+    if (spec_ell1_long.count > 0)
+      hipLaunchKernelGGL(k_proj_ell1_block, dim3(spec_ell1_long.count), dim3(kSpecEll1BlockThreads), 0, stream, y, spec_ell1_long, dual, stall);
+    if (spec_sl.count > 0)
+      hipLaunchKernelGGL(k_proj_eig_cone, dim3(spec_sl.count), dim3(kSpecThreads), spec_sl_lds, stream, y, spec_sl, 0, dual, stall);
+  }
 
   // batched PSD projection of `count` packed matrices (the first `big` of order > kPsdSmallMax): K9 + its one-wave variant
   void launch_psd(double *base, const int *off, const int *order, const long *woff, int count, int big) {

@@ -347,6 +347,7 @@
     if (cone.ed > 0)  // K = K_exp^*: dual -> project onto K_exp
       hipLaunchKernelGGL(k_proj_exp, dim3(ceil_div(cone.ed, kConeThreads)), dim3(kConeThreads), 0, stream, y + cone.off_ed,
                          cone.ed, dual ? 1 : 0, stall);
+    launch_spectral(y, dual);  // (no cone of this kind: no launch)
     if (!cone.p.empty()) {
       const int np = (int)cone.p.size();
       if (dual)

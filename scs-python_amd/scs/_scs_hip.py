@@ -49,7 +49,10 @@ class _ScsCone(C.Structure):
     _fields_ = [("z", c_int), ("l", c_int), ("bu", _PD), ("bl", _PD), ("bsize", c_int),
                 ("q", _PI), ("qsize", c_int), ("s", _PI), ("ssize", c_int),
                 ("cs", _PI), ("cssize", c_int), ("ep", c_int), ("ed", c_int),
-                ("p", _PD), ("psize", c_int)]
+                ("p", _PD), ("psize", c_int),
+                # spectral cones (include/scs_types.h under USE_SPECTRAL_CONES; the *_spectral entry points read them)
+                ("d", _PI), ("dsize", c_int), ("nuc_m", _PI), ("nuc_n", _PI), ("nucsize", c_int),
+                ("ell1", _PI), ("ell1_size", c_int), ("sl_n", _PI), ("sl_k", _PI), ("sl_size", c_int)]
 
 
 class _ScsSettings(C.Structure):
@@ -137,6 +140,12 @@ def _load():
     lib.scs_init.argtypes = [C.POINTER(_ScsData), C.POINTER(_ScsCone), C.POINTER(_ScsSettings)]
     lib.scs_hip_init_linsys.restype = C.c_void_p
     lib.scs_hip_init_linsys.argtypes = [C.POINTER(_ScsData), C.POINTER(_ScsCone), C.POINTER(_ScsSettings), c_int]
+    lib.scs_init_spectral.restype = C.c_void_p
+    lib.scs_init_spectral.argtypes = [C.POINTER(_ScsData), C.POINTER(_ScsCone), C.POINTER(_ScsSettings)]
+    lib.scs_hip_init_linsys_spectral.restype = C.c_void_p
+    lib.scs_hip_init_linsys_spectral.argtypes = [C.POINTER(_ScsData), C.POINTER(_ScsCone), C.POINTER(_ScsSettings), c_int]
+    lib.scs_hip_proj_cone_spectral.restype = c_int
+    lib.scs_hip_proj_cone_spectral.argtypes = [_PD, C.POINTER(_ScsCone), c_int, c_int]
     lib.scs_hip_linsys_kind.restype = c_int
     lib.scs_hip_linsys_kind.argtypes = [C.c_void_p]
     lib.scs_hip_kkt_solve_dense.restype = c_int
@@ -387,6 +396,29 @@ def _cone_int_list(cone, key):
     return np.asarray(vals, dtype=np.int32)
 
 
+def _spectral_lists(cone):
+    """the spectral cone keys, parsed as R:scs/scsobject.h:751-794 does (before the core is entered)"""
+    out = {}
+    for key in ("d", "nuc_m", "nuc_n", "ell1", "sl_n", "sl_k"):
+        try:
+            out[key] = _cone_int_list(cone, key)
+        except ValueError:
+            raise ValueError("Failed to parse cone field %s" % key)
+        if key == "nuc_n" and out["nuc_n"].size != out["nuc_m"].size:
+            raise ValueError("nuc_m and nuc_n must have the same length")
+        if key == "sl_k" and out["sl_k"].size != out["sl_n"].size:
+            raise ValueError("sl_n and sl_k must have the same length")
+    return out
+
+
+def _set_spectral(k, sp):
+    """fill the spectral fields of a _ScsCone from _spectral_lists (the arrays must outlive the call)"""
+    k.d, k.dsize = _pi(sp["d"]), sp["d"].size
+    k.nuc_m, k.nuc_n, k.nucsize = _pi(sp["nuc_m"]), _pi(sp["nuc_n"]), sp["nuc_m"].size
+    k.ell1, k.ell1_size = _pi(sp["ell1"]), sp["ell1"].size
+    k.sl_n, k.sl_k, k.sl_size = _pi(sp["sl_n"]), _pi(sp["sl_k"]), sp["sl_n"].size
+
+
 def _cone_float_list(cone, key):
     if key not in cone or cone[key] is None:
         return np.zeros(0, dtype=np.float64)
@@ -516,6 +548,7 @@ class SCS(object):
         p = _cone_float_list(cone, "p")
         ep = _cone_pos_int(cone, "ep")
         ed = _cone_pos_int(cone, "ed")
+        spec = _spectral_lists(cone)
         # ---- settings validation (R:scs/scsobject.h:810-868)
         if st.max_iters <= 0:
             raise ValueError("max_iters must be positive")
@@ -549,13 +582,14 @@ class SCS(object):
         d = _ScsData(m, n, C.pointer(A), C.pointer(P) if have_P else None, _pd(bc), _pd(cc))
         k = _ScsCone(z, lcone, _pd(bu), _pd(bl), (bu.size + 1) if bu.size > 0 else 0,
                      _pi(q), q.size, _pi(s), s.size, _pi(cs), cs.size, ep, ed, _pd(p), p.size)
+        _set_spectral(k, spec)
         self._x = np.zeros(n)
         self._y = np.zeros(m)
         self._s = np.zeros(m)
         if self._LINSYS:
-            work = _lib.scs_hip_init_linsys(C.byref(d), C.byref(k), C.byref(st), self._LINSYS)
+            work = _lib.scs_hip_init_linsys_spectral(C.byref(d), C.byref(k), C.byref(st), self._LINSYS)
         else:
-            work = _lib.scs_init(C.byref(d), C.byref(k), C.byref(st))  # GIL released by ctypes
+            work = _lib.scs_init_spectral(C.byref(d), C.byref(k), C.byref(st))  # GIL released by ctypes
         if not work:
             # the reference's message (R:scs/scsobject.h:903-912) + the backend's own reason: invalid data, no GPU,
             # out of HBM, or a limit this backend has and the reference has not (INTEGRATION.md "Limits")
@@ -742,7 +776,9 @@ def _cone_struct(cone):
     k = _ScsCone(z, _cone_pos_int(cone, "l"), _pd(bu), _pd(bl), (bu.size + 1) if bu.size else 0,
                  _pi(q), q.size, _pi(s), s.size, _pi(cs), cs.size,
                  _cone_pos_int(cone, "ep"), _cone_pos_int(cone, "ed"), _pd(p), p.size)
-    return k, (bu, bl, q, s, cs, p)
+    spec = _spectral_lists(cone)
+    _set_spectral(k, spec)
+    return k, (bu, bl, q, s, cs, p, spec)
 
 
 def _check(rc):
@@ -797,7 +833,7 @@ def spmv_bench(A, transpose=False, reps=20):
 def proj_cone(z, cone, dual=False):
     x = np.array(z, dtype=np.float64, copy=True)
     k, keep = _cone_struct(cone)
-    _check(_lib.scs_hip_proj_cone(_pd(x), C.byref(k), x.size, 1 if dual else 0))
+    _check(_lib.scs_hip_proj_cone_spectral(_pd(x), C.byref(k), x.size, 1 if dual else 0))
     return x
 
 
@@ -811,12 +847,20 @@ def spin_fallbacks():
     return int(_lib.scs_hip_spin_fallbacks())
 
 
+def _no_spectral(cone, what):
+    """entry points whose C functions read ScsCone only up to psize (include/scs_hip.h): refuse spectral keys with a reason"""
+    k, keep = _cone_struct(cone)
+    if k.dsize or k.nucsize or k.ell1_size or k.sl_size:
+        raise ValueError("%s: spectral cones (d, nuc, ell1, sl) are not supported by this entry point" % what)
+    return k, keep
+
+
 def proj_cone_seq(zs, cone, dual=False, stats_cap=0):
     """rows of zs projected one after the other through one set of warm-started cone workspaces (include/scs_hip.h);
     returns (projections, refinement records of the large PSD matrices)"""
     xs = np.array(zs, dtype=np.float64, copy=True, order="C")
     assert xs.ndim == 2
-    k, keep = _cone_struct(cone)
+    k, keep = _no_spectral(cone, "proj_cone_seq")
     st = np.zeros(8 * max(stats_cap, 1))
     cnt = _lib.scs_hip_proj_cone_seq(_pd(xs), C.byref(k), xs.shape[1], 1 if dual else 0, xs.shape[0], _pd(st), int(stats_cap))
     if cnt < 0:
@@ -857,7 +901,7 @@ def normalize(A, P, b, c, cone):
         Pm, keepP = _matrix(P.copy())
     bb = np.array(b, dtype=np.float64, copy=True)
     cc = np.array(c, dtype=np.float64, copy=True)
-    k, keep = _cone_struct(cone)
+    k, keep = _no_spectral(cone, "normalize")
     D, E, sig = np.zeros(A.shape[0]), np.zeros(A.shape[1]), np.zeros(1)
     _check(_lib.scs_hip_normalize(C.byref(M), C.byref(Pm) if Pm is not None else None, _pd(bb), _pd(cc),
                                   C.byref(k), _pd(D), _pd(E), _pd(sig)))

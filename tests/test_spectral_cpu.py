@@ -1,0 +1,202 @@
+"""Spectral cones without a GPU: the numpy reference projections (tests/spectral_ref.py) certified by their optimality
+conditions and cross-checked against the oracle's standard cones, the front end's parsing, and the ScsCone layout of
+include/scs_types.h compiled with -DUSE_SPECTRAL_CONES."""
+import os
+import subprocess
+import zlib
+
+import numpy as np
+import pytest
+from scipy import sparse
+
+import spectral_ref as sr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _cases(kind, sz, rng):
+    """random and edge inputs of one cone: generic, inside, polar, boundary, repeated / zero eigenvalues, rank-deficient"""
+    L = sr.length(kind, sz)
+    out = [rng.standard_normal(L), 10 * rng.standard_normal(L), np.zeros(L)]
+    p = sr.proj(kind, sz, rng.standard_normal(L))
+    out += [p, 2.0 * p, -sr.proj(kind, sz, rng.standard_normal(L), dual=True)]  # boundary of K, inside K, polar cone
+    if kind in ("sl", "d"):
+        n = sz[0]
+        off = 2 if kind == "d" else 1
+        for spec in (np.ones(n), np.r_[np.zeros(n // 2), np.ones(n - n // 2)], np.r_[-np.ones(n // 2), 3 * np.ones(n - n // 2)]):
+            Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+            w = np.zeros(L)
+            w[:off] = rng.standard_normal(off)
+            w[off:] = sr.svec((Q * spec) @ Q.T)
+            out.append(w)
+    if kind == "nuc":
+        m, n = sz
+        r = max(1, min(m, n) // 2)
+        X = rng.standard_normal((m, r)) @ rng.standard_normal((r, n))
+        out.append(np.r_[rng.standard_normal(), X.reshape(-1, order="F")])
+    return out
+
+
+KINDS = [("ell1", (1,)), ("ell1", (7,)), ("ell1", (150,)), ("nuc", (3, 2)), ("nuc", (2, 5)), ("nuc", (4, 4)), ("nuc", (6, 1)),
+         ("sl", (1, 1)), ("sl", (4, 1)), ("sl", (5, 2)), ("sl", (6, 6)), ("d", (1,)), ("d", (2,)), ("d", (5,))]
+
+
+@pytest.mark.parametrize("kind,sz", KINDS)
+def test_reference_projection_is_certified(kind, sz):
+    """p = Pi_K(w): p in K, p - w in K*, <p, p - w> = 0; and the Moreau partner Pi_{K*}(w) = w + Pi_K(-w) lies in K*."""
+    rng = np.random.default_rng(zlib.crc32(repr((kind, sz)).encode()))
+    for w in _cases(kind, sz, rng):
+        scale = max(1.0, np.abs(w).max())
+        tol = 1e-8 * scale
+        p = sr.proj(kind, sz, w)
+        assert sr.member(kind, sz, p, tol), (kind, sz, w, p)
+        assert sr.member(kind, sz, p - w, tol, dual=True), (kind, sz, w, p)
+        assert abs(p @ (p - w)) <= 1e-8 * scale * scale, (kind, sz, p @ (p - w))
+        d = sr.proj(kind, sz, -w, dual=True)
+        assert sr.member(kind, sz, d, tol, dual=True)
+        np.testing.assert_allclose(p - d, w, atol=1e-9 * scale)  # Pi_K(w) - Pi_{K*}(-w) = w
+
+
+def test_reference_fixed_points():
+    """a point of K projects to itself, a point of the polar cone to 0"""
+    rng = np.random.default_rng(5)
+    for kind, sz in KINDS:
+        p = sr.proj(kind, sz, rng.standard_normal(sr.length(kind, sz)))
+        np.testing.assert_allclose(sr.proj(kind, sz, p), p, atol=1e-9 * max(1, np.abs(p).max()))
+        q = -sr.proj(kind, sz, rng.standard_normal(sr.length(kind, sz)), dual=True)
+        np.testing.assert_allclose(sr.proj(kind, sz, q), 0, atol=1e-9 * max(1, np.abs(q).max()))
+
+
+# ---- cross-checks against the oracle's projections onto standard cones
+@pytest.fixture(scope="module")
+def oracle():
+    from oracle import scs_oracle
+    scs_oracle.build()
+    return scs_oracle
+
+
+@pytest.mark.parametrize("dual", [False, True])
+def test_reference_matches_oracle_standard_cones(oracle, dual):
+    """d=[1] is the exponential cone (t <= v log(x / v) <=> v e^(t/v) <= x), nuc (m, 1) the SOC of order m + 1, ell1=[1] the
+    SOC of order 2.  (The exp-cone projection stops at a 1e-8 heuristic distance: hence its looser tolerance.)"""
+    rng = np.random.default_rng(11)
+    for _ in range(40):
+        w = rng.standard_normal(3) * rng.choice([0.1, 1, 10])
+        np.testing.assert_allclose(sr.proj("d", (1,), w, dual), oracle.proj_cone(w, {"ep": 1}, dual=dual), rtol=1e-6, atol=1e-6)
+        w = rng.standard_normal(5)
+        np.testing.assert_allclose(sr.proj("nuc", (4, 1), w, dual), oracle.proj_cone(w, {"q": [5]}, dual=dual), rtol=1e-9, atol=1e-12)
+        np.testing.assert_allclose(sr.proj("nuc", (1, 4), w, dual), oracle.proj_cone(w, {"q": [5]}, dual=dual), rtol=1e-9, atol=1e-12)
+        w = rng.standard_normal(2)
+        np.testing.assert_allclose(sr.proj("ell1", (1,), w, dual), oracle.proj_cone(w, {"q": [2]}, dual=dual), rtol=1e-9, atol=1e-12)
+
+
+@pytest.mark.parametrize("kind,sz", [("nuc", (3, 2)), ("nuc", (2, 4)), ("sl", (4, 2)), ("sl", (3, 1)), ("sl", (5, 5)), ("d", (2,)),
+                                     ("d", (3,))])
+def test_reference_matches_oracle_on_standard_reformulations(oracle, kind, sz):
+    """orders > 1: the oracle solves each cone's standard reformulation (nuc, sl: SDP; d: PSD + exp cones) and lands on the
+    reference projection — this pins the svec / vec layouts and the (t, v, X) order of d to the existing PSD and exp cones"""
+    rng = np.random.default_rng(zlib.crc32(repr(("reform", kind, sz)).encode()))
+    w = rng.standard_normal(sr.length(kind, sz))
+    if kind == "d":
+        w[1] = abs(w[1]) + 0.5
+    data, std = sr.reformulation(kind, sz, w)
+    ref = oracle.solve(data, std, eps_abs=1e-9, eps_rel=1e-9, max_iters=200000, verbose=False)
+    assert ref["info"]["status_val"] == 1
+    p = sr.proj(kind, sz, w)
+    assert abs(ref["info"]["pobj"] - (0.5 * np.sum((p - w) ** 2) - 0.5 * w @ w)) <= 1e-7
+    np.testing.assert_allclose(ref["x"][:w.size], p, atol=1e-7)
+
+
+# ---- front end
+def _raw(m, cone):
+    from scs import _scs_hip
+    A = sparse.eye(m, format="csc")
+    return lambda: _scs_hip.SCS((m, m), A.data, A.indices.astype(np.int32), A.indptr.astype(np.int32), None, None, None,
+                                np.ones(m), np.ones(m), cone, verbose=False)
+
+
+@pytest.mark.parametrize("cone,msg", [
+    ({"nuc_m": [3, 4], "nuc_n": [2]}, "nuc_m and nuc_n must have the same length"),
+    ({"sl_n": [3, 4], "sl_k": [1]}, "sl_n and sl_k must have the same length"),
+    ({"d": [-1]}, "Failed to parse cone field d"),
+    ({"d": [1.5]}, "Failed to parse cone field d"),
+    ({"nuc_m": "x", "nuc_n": [1]}, "Failed to parse cone field nuc_m"),
+    ({"nuc_m": [1], "nuc_n": [-2]}, "Failed to parse cone field nuc_n"),
+    ({"ell1": [[1]]}, "Failed to parse cone field ell1"),
+    ({"sl_n": [3], "sl_k": ["a"]}, "Failed to parse cone field sl_k"),
+])
+def test_front_end_messages(cone, msg):
+    """R:scs/scsobject.h:751-794: raised before the core is entered"""
+    with pytest.raises(ValueError, match=msg):
+        _raw(20, cone)()
+
+
+def test_front_end_fills_the_spectral_fields():
+    from scs import _scs_hip
+    k, keep = _scs_hip._cone_struct({"l": 2, "d": [3], "nuc_m": [4, 2], "nuc_n": [2, 5], "ell1": [6], "sl_n": [5], "sl_k": [2]})
+    assert (k.dsize, k.nucsize, k.ell1_size, k.sl_size) == (1, 2, 1, 1)
+    assert [k.nuc_m[i] for i in range(2)] == [4, 2] and [k.nuc_n[i] for i in range(2)] == [2, 5]
+    assert k.d[0] == 3 and k.ell1[0] == 6 and (k.sl_n[0], k.sl_k[0]) == (5, 2)
+    k, keep = _scs_hip._cone_struct({"l": 2})
+    assert (k.dsize, k.nucsize, k.ell1_size, k.sl_size) == (0, 0, 0, 0)
+
+
+def test_kernel_level_entries_without_spectral_variant_refuse_spectral_keys():
+    """scs_hip_proj_cone_seq / scs_hip_normalize read ScsCone up to psize: their wrappers say so instead of a bare row-count error"""
+    from scs import _scs_hip
+    with pytest.raises(ValueError, match="proj_cone_seq: spectral cones"):
+        _scs_hip.proj_cone_seq(np.zeros((1, 5)), {"ell1": [4]})
+    A = sparse.eye(5, format="csc")
+    with pytest.raises(ValueError, match="normalize: spectral cones"):
+        _scs_hip.normalize(A, None, np.ones(5), np.ones(5), {"ell1": [4]})
+
+
+_LAYOUT_C = r"""
+#include <stddef.h>
+#include <stdio.h>
+#include "scs_types.h"
+#define F(x) printf(#x " %zu\n", offsetof(ScsCone, x));
+int main(void) {
+  F(z) F(l) F(bu) F(bl) F(bsize) F(q) F(qsize) F(s) F(ssize) F(cs) F(cssize) F(ep) F(ed) F(p) F(psize)
+#ifdef USE_SPECTRAL_CONES
+  F(d) F(dsize) F(nuc_m) F(nuc_n) F(nucsize) F(ell1) F(ell1_size) F(sl_n) F(sl_k) F(sl_size)
+#endif
+  printf("sizeof %zu\n", sizeof(ScsCone));
+  return 0;
+}
+"""
+
+
+def _layout(tmp_path, flag):
+    src = tmp_path / "layout.c"
+    src.write_text(_LAYOUT_C)
+    exe = str(tmp_path / ("layout_spec" if flag else "layout_plain"))
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include")] + (["-DUSE_SPECTRAL_CONES"] if flag else []) + [str(src), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")
+    return dict((a, int(b)) for a, b in (ln.split() for ln in out if ln))
+
+
+def test_scs_cone_layout_matches_the_header(tmp_path):
+    """the ctypes mirror of ScsCone is the header's struct compiled with -DUSE_SPECTRAL_CONES; without the flag the struct
+    is the prefix up to psize, unchanged"""
+    from scs import _scs_hip
+    spec, plain = _layout(tmp_path, True), _layout(tmp_path, False)
+    for name, _ in _scs_hip._ScsCone._fields_:
+        assert getattr(_scs_hip._ScsCone, name).offset == spec[name], name
+    assert C_sizeof(_scs_hip._ScsCone) == spec["sizeof"]
+    assert plain["sizeof"] == spec["d"]  # the short struct ends where the spectral fields begin
+    for name in plain:
+        if name != "sizeof":
+            assert plain[name] == spec[name], name
+
+
+def C_sizeof(t):
+    import ctypes
+    return ctypes.sizeof(t)
+
+
+def test_spectral_entry_points_are_exported():
+    import ctypes
+    lib = ctypes.CDLL(os.path.join(ROOT, "scs-python_amd", "scs", "libscs_hip.so"))
+    for name in ("scs_init_spectral", "scs_hip_init_linsys_spectral", "scs_hip_proj_cone_spectral", "scs_init", "scs_hip_proj_cone"):
+        assert hasattr(lib, name), name
