@@ -149,6 +149,10 @@ int scs_hip_solution_to_device(ScsWork *w, scs_float *x_dev, scs_float *y_dev, s
  * CG-step counts are bit-identical to separate solves (timing fields are those of the group).  Returns 0, -1 on error
  * (scs_hip_last_error).  The workspaces must live on one device and must not be used by other threads meanwhile. */
 scs_int scs_hip_solve_batch(ScsWork **w, ScsSolution **sol, ScsInfo **info, scs_int count, scs_int warm_start);
+/* The grouping scs_hip_solve_batch(w, .., count, ..) would use, without solving: group_of[i] = the index of the group member i
+ * would join, -1 for a member it would solve alone by scs_solve.  Returns the number of groups, -1 on error (null arguments,
+ * a workspace twice; scs_hip_last_error).  scs_hip_solve_batch forms its groups with the same code. */
+int scs_hip_batch_plan(ScsWork **w, scs_int count, scs_int *group_of);
 
 /* bench.py: a timestamp inside the next scs_solve calls.  When ADMM iteration `iter` is about to start, the stream is
  * drained and out[4] = {ms since the start of the solve, CG steps so far, Anderson calls so far, accepted so far} is

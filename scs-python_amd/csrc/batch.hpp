@@ -100,6 +100,24 @@ __device__ __forceinline__ void d_psd_small4_blk(double *x, PsdBatch B, double *
                                                  const double *tol2) {
   d_proj_psd_small4(x, B, scratch, allow_warm, stall, tol2, (int)blockIdx.x);
 }
+__device__ __forceinline__ void d_soc_block_blk(double *x, const int *__restrict__ off, const int *__restrict__ dim, const int *__restrict__ big,
+                                                int nbig, const int *stall) {
+  d_proj_soc_block(x, off, dim, big, nbig, stall, (int)blockIdx.x);
+}
+__device__ __forceinline__ void d_cs_expand_blk(const double *__restrict__ x, CsBatch B, double *stage, const int *stall) {
+  d_cs_expand(x, B, stage, stall, (int)blockIdx.x);
+}
+__device__ __forceinline__ void d_cs_extract_blk(double *x, CsBatch B, const double *__restrict__ stage, const int *stall) {
+  d_cs_extract(x, B, stage, stall, (int)blockIdx.x);
+}
+__device__ __forceinline__ void d_ell1_blk(double *y, SpecBatch B, int dual, const int *stall) { d_proj_ell1(y, B, dual, stall, (int)blockIdx.x); }
+__device__ __forceinline__ void d_ell1_block_blk(double *y, SpecBatch B, int dual, const int *stall) {
+  d_proj_ell1_block(y, B, dual, stall, (int)blockIdx.x);
+}
+__device__ __forceinline__ void d_eig_cone_blk(double *y, SpecBatch B, int kind, int dual, const int *stall) {
+  d_proj_eig_cone(y, B, kind, dual, stall, (int)blockIdx.x);
+}
+__device__ __forceinline__ void d_nuc_blk(double *y, SpecBatch B, int dual, const int *stall) { d_proj_nuc(y, B, dual, stall, (int)blockIdx.x); }
 
 // ---- small bodies only the grouped path needs (the one-problem path uses hipMemset / hipMemcpy for these) ----
 __device__ __forceinline__ void d_copy_f64(const double *__restrict__ src, double *dst, long n) {
@@ -153,6 +171,14 @@ struct GroupSolve {
   SCS_GTABLE(kPsdSmallThreads, d_proj_soc_psd_small) t_soc_psd;  // both in one launch (members with short SOCs and small PSD matrices)
   SCS_GTABLE(kConeThreads, d_proj_exp) t_exp_p, t_exp_d;
   SCS_GTABLE(kConeThreads, d_proj_pow_dual) t_pow;
+  SCS_GTABLE(kConeThreads, d_soc_block_blk) t_soc_big;                  // SOCs longer than kSocBig
+  SCS_GTABLE(256, d_cs_expand_blk) t_cs_expand;                         // complex PSD: expand -> small-PSD kernel on the embeddings -> extract
+  SCS_GTABLE(kPsdSmallThreads, d_psd_small4_blk) t_cs_psd;
+  SCS_GTABLE(256, d_cs_extract_blk) t_cs_extract;
+  SCS_GTABLE(kSpecThreads, d_eig_cone_blk) t_spec_d, t_spec_sl;         // spectral cones (spectral.hpp), one table per kind
+  SCS_GTABLE(kSpecThreads, d_nuc_blk) t_spec_nuc;
+  SCS_GTABLE(kSpecThreads, d_ell1_blk) t_spec_ell1;
+  SCS_GTABLE(kSpecEll1BlockThreads, d_ell1_block_blk) t_spec_ell1_long;
   SCS_GTABLE(kVecThreads, d_v_update) t_v_update;
   SCS_GTABLE(kVecThreads, d_rsk) t_rsk;
   SCS_GTABLE(kSpmvThreads, d_spmv_stream<EpiResPri>) t_res_pri;
@@ -240,12 +266,14 @@ struct GroupSolve {
 
   // Can these workspaces advance as one group?  Same dimensions and cone structure (every launch geometry follows
   // from them), the plain CSR-stream layouts, cone kernels that are one launch each, the same Anderson schedule.
+  // Not grouped: PSD matrices above kPsdSmallMax and complex PSD cones whose embedding is above it (K9's split pipeline: a chain of launches
+  // with per-matrix scratch, and its refinement stage differs in bits from the one-launch kernel), large box cones (Newton rounds
+  // over many workgroups) — solved by scs_solve.
   static bool member_ok(const ScsHipWork *w) {
     if (w->At.cs.ok || w->Ar.cs.ok || w->At.has_slab || w->Ar.has_slab) return false;
     if (w->has_P && (w->Pf.cs.ok || w->Pf.has_slab)) return false;
     if (w->persist_wgs > 0 || !w->log_csv_filename.empty() || w->mark_iter >= 0 || w->stgs.verbose) return false;  // (a verbose member prints its own table: solved by scs_solve)
-    if (w->n_psd_big > 0 || w->n_cs > 0 || w->n_soc_big > 0 || w->cone.bsize > kBoxMultiMin) return false;
-    if (w->cone.has_spectral()) return false;  // spectral cones (spectral.hpp) have no grouped kernels: solved by scs_solve
+    if (w->n_psd_big > 0 || w->n_cs_big > 0 || w->cone.bsize > kBoxMultiMin) return false;
     if (w->aa.mem > 0 && !w->aa.tsqr) return false;
     return true;
   }
@@ -254,7 +282,8 @@ struct GroupSolve {
     return a->device == b->device && a->n == b->n && a->m == b->m && a->has_P == b->has_P && a->normalized == b->normalized &&
            a->linsys == b->linsys &&
            x.z == y.z && x.l == y.l && x.bsize == y.bsize && x.ep == y.ep && x.ed == y.ed && x.q == y.q && x.s == y.s &&
-           x.p.size() == y.p.size() && a->aa.mem == b->aa.mem && a->aa.type1 == b->aa.type1 &&
+           x.p.size() == y.p.size() && x.cs == y.cs && x.d == y.d && x.nuc_m == y.nuc_m && x.nuc_n == y.nuc_n && x.ell1 == y.ell1 &&
+           x.sl_n == y.sl_n && x.sl_k == y.sl_k && a->aa.mem == b->aa.mem && a->aa.type1 == b->aa.type1 &&
            a->stgs.acceleration_interval == b->stgs.acceleration_interval;
   }
 
@@ -349,7 +378,8 @@ struct GroupSolve {
     if (has_P) size_all(t_spmv_pws, t_spmv_p, t_res_px);
     if (dense) size_all(t_dense_rhs, t_dense_gemv, t_dense_gemv_kkt, t_dense_y, t_symv_tiles, t_symv_sum, t_symv_sum_kkt);
     if (c0.bsize > 0) t_box.resize((size_t)G);
-    soc_psd_fused = w0->soc_psd_one_launch && w0->n_soc > 0 && w0->n_psd > 0 && !w0->psd_small_one_wave;  // (member_ok: nothing big)
+    soc_psd_fused = w0->soc_psd_one_launch && w0->n_soc > 0 && w0->n_soc_big == 0 && w0->n_psd > 0 &&
+                    !w0->psd_small_one_wave;  // (as project_nonlinear_cones decides; member_ok: no big PSD matrix)
     if (soc_psd_fused) t_soc_psd.resize((size_t)G);
     else {
       if (w0->n_soc > 0) t_soc.resize((size_t)G);
@@ -358,6 +388,13 @@ struct GroupSolve {
     if (c0.ep > 0) t_exp_p.resize((size_t)G);
     if (c0.ed > 0) t_exp_d.resize((size_t)G);
     if (!c0.p.empty()) t_pow.resize((size_t)G);
+    if (w0->n_soc_big > 0) t_soc_big.resize((size_t)G);
+    if (w0->n_cs > 0) size_all(t_cs_expand, t_cs_psd, t_cs_extract);
+    if (w0->spec_d.count > 0) t_spec_d.resize((size_t)G);
+    if (w0->spec_sl.count > 0) t_spec_sl.resize((size_t)G);
+    if (w0->spec_nuc.count > 0) t_spec_nuc.resize((size_t)G);
+    if (w0->spec_ell1.count > 0) t_spec_ell1.resize((size_t)G);
+    if (w0->spec_ell1_long.count > 0) t_spec_ell1_long.resize((size_t)G);
     std::vector<DeviceAa::TsqrLevel> lv0;
     if (mem > 0) {
       size_all(t_aa_seed, t_aa_update, t_aa_solve, t_aa_apply, t_aa_diffsq, t_fin_safe, t_aa_restore, t_gather_aa);
@@ -427,6 +464,20 @@ struct GroupSolve {
       if (t_exp_p.used) t_exp_p.set(g, uy + w->cone.off_ep, w->cone.ep, 0, nostall);
       if (t_exp_d.used) t_exp_d.set(g, uy + w->cone.off_ed, w->cone.ed, 1, nostall);
       if (t_pow.used) t_pow.set(g, uy + w->cone.off_p, w->pow_a.p, (int)w->cone.p.size(), nostall);
+      if (t_soc_big.used) t_soc_big.set(g, uy, w->soc_off.p, w->soc_dim.p, w->soc_big.p, w->n_soc_big, nostall);
+      if (t_cs_expand.used) {  // each member stages its embeddings in its own cs_stage; their PSD scratch / warm state at cs_woff
+        const CsBatch C{w->cs_off.p, w->cs_order.p, w->cs_soff.p, w->n_cs};
+        t_cs_expand.set(g, uy, C, w->cs_stage.p, nostall);
+        t_cs_psd.set(g, w->cs_stage.p, PsdBatch{w->cs_poff.p, w->cs_porder.p, w->cs_woff.p, w->n_cs}, w->psd_scratch.p, w->psd_warm,
+                     nostall, (const double *)(par + P_PSD_TOL2));
+        t_cs_extract.set(g, uy, C, w->cs_stage.p, nostall);
+      }
+      // the ADMM loop projects onto K* (project_nonlinear_cones(.., dual = 1))
+      if (t_spec_d.used) t_spec_d.set(g, uy, w->spec_d, 1, 1, nostall);
+      if (t_spec_sl.used) t_spec_sl.set(g, uy, w->spec_sl, 0, 1, nostall);
+      if (t_spec_nuc.used) t_spec_nuc.set(g, uy, w->spec_nuc, 1, nostall);
+      if (t_spec_ell1.used) t_spec_ell1.set(g, uy, w->spec_ell1, 1, nostall);
+      if (t_spec_ell1_long.used) t_spec_ell1_long.set(g, uy, w->spec_ell1_long, 1, nostall);
       t_v_update.set(g, w->v.p, w->u.p, w->ut.p, w->stgs.alpha, l, w->part_v.p, nostall);
       t_rsk.set(g, w->rsk.p, w->v.p, w->u.p, w->ut.p, w->diag_r.p, l);
       const double *tau_ptr = w->u.p + (l - 1);
@@ -503,6 +554,16 @@ struct GroupSolve {
     t_exp_p.gx = ceil_div(c0.ep, kConeThreads);
     t_exp_d.gx = ceil_div(c0.ed, kConeThreads);
     t_pow.gx = ceil_div((long)c0.p.size(), kConeThreads);
+    t_soc_big.gx = w0->n_soc_big;
+    t_cs_expand.gx = t_cs_psd.gx = t_cs_extract.gx = w0->n_cs;
+    t_spec_d.gx = w0->spec_d.count;
+    t_spec_d.lds = w0->spec_d_lds;
+    t_spec_sl.gx = w0->spec_sl.count;
+    t_spec_sl.lds = w0->spec_sl_lds;
+    t_spec_nuc.gx = w0->spec_nuc.count;
+    t_spec_nuc.lds = w0->spec_nuc_lds;
+    t_spec_ell1.gx = ceil_div(w0->spec_ell1.count, kSpecThreads / kWave);
+    t_spec_ell1_long.gx = w0->spec_ell1_long.count;
     if (mem > 0) t_aa_seed.gx = t_aa_update.gx = t_aa_apply.gx = t_aa_diffsq.gx = t_aa_restore.gx = w0->aa.nbl();
     upload_all();
     {  // seed the group's flag array from the members' own blocks (the step parity F_STEP carries over)
@@ -516,7 +577,8 @@ struct GroupSolve {
   template <class F> void for_tables(F &&f) {
     f(t_sumsq); f(t_prep); f(t_spmv_y); f(t_spmv_pws); f(t_spmv_p); f(t_res_px); f(t_spmv_ax); f(t_spmv_r0); f(t_fin_head);
     f(t_spmv_a); f(t_spmv_at); f(t_cg_update[0]); f(t_cg_update[1]); f(t_cg_dir[0]); f(t_cg_dir[1]); f(t_tau_dots);
-    f(t_cone_pre); f(t_box); f(t_soc); f(t_psd); f(t_soc_psd); f(t_exp_p); f(t_exp_d); f(t_pow); f(t_v_update); f(t_rsk); f(t_res_pri);
+    f(t_cone_pre); f(t_box); f(t_soc); f(t_psd); f(t_soc_psd); f(t_exp_p); f(t_exp_d); f(t_pow); f(t_soc_big);
+    f(t_cs_expand); f(t_cs_psd); f(t_cs_extract); f(t_spec_d); f(t_spec_sl); f(t_spec_nuc); f(t_spec_ell1); f(t_spec_ell1_long); f(t_v_update); f(t_rsk); f(t_res_pri);
     f(t_res_dual); f(t_fin_multi_p); f(t_fin_multi_d); f(t_gather_res); f(t_gather_fl); f(t_set_diag_r); f(t_precond);
     f(t_g_rhs); f(t_kkt_prep); f(t_spmv_rhs); f(t_zero_part); f(t_fin_tol); f(t_cg_init); f(t_fin_cg_init); f(t_zero_iters);
     f(t_kkt_y); f(t_copy_g); f(t_gather_aa); f(t_gg); f(t_fin_gg); f(t_v_rescale); f(t_aa_seed); f(t_aa_update);
@@ -599,9 +661,18 @@ struct GroupSolve {
     go(t_box, list, count);
     go(t_soc_psd, list, count);
     go(t_soc, list, count);
+    go(t_soc_big, list, count);
     go(t_psd, list, count);
+    go(t_cs_expand, list, count);  // (in this order, as in project_nonlinear_cones)
+    go(t_cs_psd, list, count);
+    go(t_cs_extract, list, count);
     go(t_exp_p, list, count);
     go(t_exp_d, list, count);
+    go(t_spec_d, list, count);
+    go(t_spec_nuc, list, count);
+    go(t_spec_ell1, list, count);
+    go(t_spec_ell1_long, list, count);
+    go(t_spec_sl, list, count);
     go(t_pow, list, count);
   }
 

@@ -69,13 +69,13 @@ __global__ __launch_bounds__(kConeThreads) void k_proj_soc_wave(double *x, const
 // workgroups of k_proj_soc_wave for ncones cones in groups of G lanes
 inline int soc_wave_blocks(int ncones, int G) { return ceil_div(ceil_div(ncones, 64 / G), kConeThreads / 64); }
 
-// one workgroup per big cone
-__global__ __launch_bounds__(kConeThreads) void k_proj_soc_block(double *x, const int *__restrict__ off,
-                                                                 const int *__restrict__ dim, const int *__restrict__ big, int nbig, const int *stall) {
+// one workgroup per big cone (blk: which of them)
+__device__ __forceinline__ void d_proj_soc_block(double *x, const int *__restrict__ off, const int *__restrict__ dim,
+                                                 const int *__restrict__ big, int nbig, const int *stall, int blk) {
   SCS_STALL_GUARD(stall);
   __shared__ double sm[kConeThreads / 64];
   __shared__ double bc;
-  const int c = big[blockIdx.x];
+  const int c = big[blk];
   const int q = dim[c];
   double *v = x + off[c];
   double ss = 0.;
@@ -93,6 +93,10 @@ __global__ __launch_bounds__(kConeThreads) void k_proj_soc_block(double *x, cons
   const double alpha = 0.5 * (s + t), f = alpha / s;
   for (int i = 1 + threadIdx.x; i < q; i += kConeThreads) v[i] *= f;
   if (threadIdx.x == 0) v[0] = alpha;
+}
+__global__ __launch_bounds__(kConeThreads) void k_proj_soc_block(double *x, const int *__restrict__ off,
+                                                                 const int *__restrict__ dim, const int *__restrict__ big, int nbig, const int *stall) {
+  d_proj_soc_block(x, off, dim, big, nbig, stall, (int)blockIdx.x);
 }
 
 // ------------------------------------------------------------ power cone

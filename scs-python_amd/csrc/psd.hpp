@@ -2379,9 +2379,9 @@ struct CsBatch {
 __device__ __forceinline__ long cs_col_start(long j, long k) { return j * (2 * k - j); }
 __device__ __forceinline__ long packed_idx(long I, long J, long N) { return J * N - J * (J - 1) / 2 + (I - J); }  // I >= J
 
-__global__ __launch_bounds__(256) void k_cs_expand(const double *__restrict__ x, CsBatch B, double *stage, const int *stall) {
+// (bodies d_cs_* take the cone index from the caller: the one-problem kernels pass blockIdx.x, the grouped solve its own)
+__device__ __forceinline__ void d_cs_expand(const double *__restrict__ x, CsBatch B, double *stage, const int *stall, int c) {
   SCS_STALL_GUARD(stall);
-  const int c = blockIdx.x;
   const long k = B.order[c], N = 2 * k;
   const double *X = x + B.off[c];
   double *P = stage + B.soff[c];
@@ -2400,10 +2400,12 @@ __global__ __launch_bounds__(256) void k_cs_expand(const double *__restrict__ x,
     P[packed_idx(I, J, N)] = v;
   }
 }
+__global__ __launch_bounds__(256) void k_cs_expand(const double *__restrict__ x, CsBatch B, double *stage, const int *stall) {
+  d_cs_expand(x, B, stage, stall, (int)blockIdx.x);
+}
 
-__global__ __launch_bounds__(256) void k_cs_extract(double *x, CsBatch B, const double *__restrict__ stage, const int *stall) {
+__device__ __forceinline__ void d_cs_extract(double *x, CsBatch B, const double *__restrict__ stage, const int *stall, int c) {
   SCS_STALL_GUARD(stall);
-  const int c = blockIdx.x;
   const long k = B.order[c], N = 2 * k;
   double *X = x + B.off[c];
   const double *P = stage + B.soff[c];
@@ -2418,6 +2420,9 @@ __global__ __launch_bounds__(256) void k_cs_extract(double *x, CsBatch B, const 
       X[cj + 2 + 2 * (i - j - 1)] = 0.5 * (P[packed_idx(k + i, j, N)] - P[packed_idx(k + j, i, N)]);
     }
   }
+}
+__global__ __launch_bounds__(256) void k_cs_extract(double *x, CsBatch B, const double *__restrict__ stage, const int *stall) {
+  d_cs_extract(x, B, stage, stall, (int)blockIdx.x);
 }
 
 }  // namespace scship

@@ -205,18 +205,11 @@ static scs_int solve_one_group(ScsWork **works, ScsSolution **sols, ScsInfo **in
   return rc;
 }
 
-scs_int scs_hip_solve_batch(ScsWork **works, ScsSolution **sols, ScsInfo **infos, scs_int count, scs_int warm_start) {
-  if (!works || !sols || !infos || count < 0) return -1;
-  set_last_error("");
-  InterruptListener ctrlc;  // for the whole call: members solved one after the other all see the same Ctrl-C
-  for (int i = 0; i < count; ++i) {
-    if (!works[i] || !sols[i] || !infos[i]) { set_last_error("scs_hip_solve_batch: null entry"); return -1; }
-    for (int j = 0; j < i; ++j)
-      if (works[j] == works[i]) { set_last_error("scs_hip_solve_batch: a workspace appears twice"); return -1; }
-  }
-  refresh_options();
+// The jobs of a batch: shape classes of members that can share launches (GroupSolve::member_ok / same_shape), in the order of
+// their first member, each cut into contiguous, near-equal parts; a job of one member is solved by scs_solve.  Both
+// scs_hip_solve_batch and scs_hip_batch_plan take their groups from here (options as refresh_options() last read them).
+static std::vector<std::vector<int>> plan_batch(ScsWork *const *works, int count) {
   const int group_max = opts().group_max, lanes = opts().group_lanes, group_min = opts().group_min;  // (labs knobs: several concurrently driven groups lost)
-  // shape classes, then groups
   std::vector<std::vector<int>> jobs;
   std::vector<char> taken((size_t)count, 0);
   for (int i = 0; i < count; ++i) {
@@ -237,6 +230,40 @@ scs_int scs_hip_solve_batch(ScsWork **works, ScsSolution **sols, ScsInfo **infos
       jobs.emplace_back(cls.begin() + lo, cls.begin() + hi);
     }
   }
+  return jobs;
+}
+
+// What scs_hip_solve_batch(works, .., count, ..) would do with each member (include/scs_hip.h): group_of[i] = the index of its
+// group, -1 for a member solved alone.  Returns the number of groups, -1 on bad arguments.
+int scs_hip_batch_plan(ScsWork **works, scs_int count, scs_int *group_of) {
+  if (!works || !group_of || count < 0) return -1;
+  set_last_error("");
+  for (int i = 0; i < count; ++i) {
+    if (!works[i]) { set_last_error("scs_hip_batch_plan: null entry"); return -1; }
+    for (int j = 0; j < i; ++j)
+      if (works[j] == works[i]) { set_last_error("scs_hip_batch_plan: a workspace appears twice"); return -1; }
+  }
+  refresh_options();
+  int groups = 0;
+  for (const std::vector<int> &job : plan_batch(works, (int)count)) {
+    const int id = job.size() > 1 ? groups++ : -1;
+    for (int i : job) group_of[i] = id;
+  }
+  return groups;
+}
+
+scs_int scs_hip_solve_batch(ScsWork **works, ScsSolution **sols, ScsInfo **infos, scs_int count, scs_int warm_start) {
+  if (!works || !sols || !infos || count < 0) return -1;
+  set_last_error("");
+  InterruptListener ctrlc;  // for the whole call: members solved one after the other all see the same Ctrl-C
+  for (int i = 0; i < count; ++i) {
+    if (!works[i] || !sols[i] || !infos[i]) { set_last_error("scs_hip_solve_batch: null entry"); return -1; }
+    for (int j = 0; j < i; ++j)
+      if (works[j] == works[i]) { set_last_error("scs_hip_solve_batch: a workspace appears twice"); return -1; }
+  }
+  refresh_options();
+  const int lanes = opts().group_lanes;
+  std::vector<std::vector<int>> jobs = plan_batch(works, (int)count);
   std::stable_sort(jobs.begin(), jobs.end(), [](const std::vector<int> &a, const std::vector<int> &b) { return a.size() > b.size(); });
   const int nthreads = std::max(1, std::min(lanes, (int)jobs.size()));
   std::atomic<size_t> next{0};

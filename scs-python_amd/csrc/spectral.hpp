@@ -103,10 +103,12 @@ __device__ double spec_ell1_lambda(Acc a, int n, double t, int lane) {
   return lam;
 }
 
-__global__ __launch_bounds__(kSpecThreads) void k_proj_ell1(double *y, SpecBatch B, int dual, const int *stall) {
+// Every kernel below is a __device__ body d_X(..., blk) that takes its workgroup index from the caller, plus the one-problem
+// kernel k_X that passes blockIdx.x; the grouped solve (batch.hpp) calls the same bodies from its own launch.
+__device__ __forceinline__ void d_proj_ell1(double *y, SpecBatch B, int dual, const int *stall, int blk) {
   SCS_STALL_GUARD(stall);
   const int lane = threadIdx.x & 63;
-  const int c = blockIdx.x * (kSpecThreads / kWave) + (threadIdx.x >> 6);
+  const int c = blk * (kSpecThreads / kWave) + (threadIdx.x >> 6);
   if (c >= B.count) return;  // (no workgroup barrier below)
   double *x = y + B.off[c];
   const int n = B.a[c];
@@ -120,18 +122,21 @@ __global__ __launch_bounds__(kSpecThreads) void k_proj_ell1(double *y, SpecBatch
   }
   if (lane == 0) x[0] = dual ? x[0] + (t + lam) : t + lam;
 }
+__global__ __launch_bounds__(kSpecThreads) void k_proj_ell1(double *y, SpecBatch B, int dual, const int *stall) {
+  d_proj_ell1(y, B, dual, stall, (int)blockIdx.x);
+}
 
 // Long ell1 cones (n > kSpecEll1WaveMax): one 1024-lane workgroup per cone, the same fixed point with fixed-order block sums.
 constexpr int kSpecEll1WaveMax = 2048;
 constexpr int kSpecEll1BlockThreads = 1024;
-__global__ __launch_bounds__(kSpecEll1BlockThreads) void k_proj_ell1_block(double *y, SpecBatch B, int dual, const int *stall) {
+__device__ __forceinline__ void d_proj_ell1_block(double *y, SpecBatch B, int dual, const int *stall, int cidx) {
   SCS_STALL_GUARD(stall);
   constexpr int NT = kSpecEll1BlockThreads;
   __shared__ double sm[NT / kWave];
   __shared__ double bc[2];
   const int tid = threadIdx.x;
-  double *x = y + B.off[blockIdx.x];
-  const int n = B.a[blockIdx.x];
+  double *x = y + B.off[cidx];
+  const int n = B.a[cidx];
   const double sg = dual ? -1. : 1.;
   const double t = sg * x[0];
   double s1 = 0., mx = 0.;
@@ -178,6 +183,9 @@ __global__ __launch_bounds__(kSpecEll1BlockThreads) void k_proj_ell1_block(doubl
     x[1 + i] = dual ? x[1 + i] + p : p;
   }
   if (tid == 0) x[0] = dual ? x[0] + (t + lam) : t + lam;
+}
+__global__ __launch_bounds__(kSpecEll1BlockThreads) void k_proj_ell1_block(double *y, SpecBatch B, int dual, const int *stall) {
+  d_proj_ell1_block(y, B, dual, stall, (int)blockIdx.x);
 }
 
 // ------------------------------------------------------------ eigen-solve
@@ -403,11 +411,11 @@ __device__ SpecLogdetOut spec_logdet_solve(double x, int n, double t, double v, 
 }
 
 // kind 0: sl (header t; B.a = n, B.b = k), kind 1: d (header t, v; B.a = n).  One workgroup per matrix.
-__global__ __launch_bounds__(kSpecThreads) void k_proj_eig_cone(double *y, SpecBatch B, int kind, int dual, const int *stall) {
+__device__ __forceinline__ void d_proj_eig_cone(double *y, SpecBatch B, int kind, int dual, const int *stall, int cidx) {
   SCS_STALL_GUARD(stall);
   extern __shared__ double spec_lds[];
   __shared__ double cs[kSpecMaxOrder / 2], sn[kSpecMaxOrder / 2], red[8], mu[kSpecMaxOrder], ls[kWave + 1], ps[kWave + 1], hd[2];
-  const int tid = threadIdx.x, cidx = blockIdx.x, ld = kSpecLd;
+  const int tid = threadIdx.x, ld = kSpecLd;
   const int n = B.a[cidx], N = (n + 1) & ~1, hdr = kind == 1 ? 2 : 1;
   double *S = spec_lds, *V = spec_lds + (size_t)ld * N;
   double *x = y + B.off[cidx];
@@ -454,18 +462,21 @@ __global__ __launch_bounds__(kSpecThreads) void k_proj_eig_cone(double *y, SpecB
   }
   if (tid < hdr) x[tid] = dual ? x[tid] + hd[tid] : hd[tid];
 }
+__global__ __launch_bounds__(kSpecThreads) void k_proj_eig_cone(double *y, SpecBatch B, int kind, int dual, const int *stall) {
+  d_proj_eig_cone(y, B, kind, dual, stall, (int)blockIdx.x);
+}
 
 // ------------------------------------------------------- nuclear norm
 // One workgroup per matrix.  Y = X (m >= n) or X' (m < n): R x C, R >= C, column-major in LDS.  One-sided Jacobi: a round
 // rotates N/2 disjoint column pairs (rr_pair on N = C rounded up to even; a pair with the padding index is skipped) by the
 // rotation that diagonalises their 2x2 Gram matrix (jacobi_rot), V <- V J; sweeps until no pair needed a rotation.  Then
 // sigma_j = |y_j|, U_j = y_j / sigma_j and X+ = Y diag(sigma+ / sigma) V' (transposed back when m < n).
-__global__ __launch_bounds__(kSpecThreads) void k_proj_nuc(double *y, SpecBatch B, int dual, const int *stall) {
+__device__ __forceinline__ void d_proj_nuc(double *y, SpecBatch B, int dual, const int *stall, int cidx) {
   SCS_STALL_GUARD(stall);
   extern __shared__ double spec_lds[];
   __shared__ double cs[kSpecMaxOrder / 2], sn[kSpecMaxOrder / 2], ratio[kSpecMaxOrder], sig[kSpecMaxOrder], hd[1];
   __shared__ int rotated;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, cidx = blockIdx.x, ld = kSpecLd;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, ld = kSpecLd;
   const int m = B.a[cidx], n = B.b[cidx];
   const bool tr = m < n;
   const int R = tr ? n : m, C = tr ? m : n, N = (C + 1) & ~1, H = N / 2;
@@ -558,6 +569,9 @@ __global__ __launch_bounds__(kSpecThreads) void k_proj_nuc(double *y, SpecBatch 
     x[1 + e] = dual ? x[1 + e] + acc : acc;
   }
   if (tid == 0) x[0] = dual ? x[0] + hd[0] : hd[0];
+}
+__global__ __launch_bounds__(kSpecThreads) void k_proj_nuc(double *y, SpecBatch B, int dual, const int *stall) {
+  d_proj_nuc(y, B, dual, stall, (int)blockIdx.x);
 }
 
 }  // namespace scship

@@ -225,3 +225,14 @@ def solve_batch(solvers, warm_start=False):
       raise TypeError("solve_batch needs scs.SCS objects created with LinearSolver.HIP_INDIRECT")
     raw.append(sv._solver)
   return _scs_hip.solve_batch(raw, warm_start)
+
+
+def batch_plan(solvers):
+  """How `solve_batch(solvers)` would split the batch, without solving: one int per solver, the index of the group it would
+  share launches with, or -1 where it would be solved alone (a shape of its own, or a cone the grouped kernels do not cover)."""
+  raw = []
+  for sv in solvers:
+    if not isinstance(sv, SCS) or not isinstance(sv._solver, _scs_hip.SCS):
+      raise TypeError("batch_plan needs scs.SCS objects of the HIP backend")
+    raw.append(sv._solver)
+  return _scs_hip.batch_plan(raw)

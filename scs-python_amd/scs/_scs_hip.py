@@ -155,6 +155,8 @@ def _load():
     lib.scs_hip_solve_batch.restype = c_int
     lib.scs_hip_solve_batch.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.POINTER(_ScsSolution)),
                                         C.POINTER(C.POINTER(_ScsInfo)), c_int, c_int]
+    lib.scs_hip_batch_plan.restype = c_int
+    lib.scs_hip_batch_plan.argtypes = [C.POINTER(C.c_void_p), c_int, C.POINTER(c_int)]
     lib.scs_update.restype = c_int
     lib.scs_update.argtypes = [C.c_void_p, _PD, _PD]
     lib.scs_finish.restype = None
@@ -757,6 +759,36 @@ def solve_batch(solvers, warm_start=False):
     if rc != 0 and any(o["info"]["status_val"] == 0 for o in out):
         raise RuntimeError("libscs_hip: " + err)
     return out
+
+
+def batch_plan(solvers):
+    """The grouping solve_batch(solvers) would use (include/scs_hip.h: scs_hip_batch_plan), without solving: a list with,
+    for each solver, the index of the group it would join, or -1 where it would be solved alone."""
+    solvers = list(solvers)
+    if not solvers:
+        return []
+    if len(set(id(sv) for sv in solvers)) != len(solvers):
+        raise ValueError("batch_plan: a solver appears twice")
+    for sv in solvers:
+        if not isinstance(sv, SCS):
+            raise TypeError("batch_plan expects scs._scs_hip.SCS objects")
+    ordered = sorted(solvers, key=id)  # (the lock order of solve_batch)
+    for sv in ordered:
+        sv._lock.acquire()
+    try:
+        for sv in solvers:
+            if not sv._work:
+                raise ValueError("Workspace not initialized!")
+        cnt = len(solvers)
+        works = (C.c_void_p * cnt)(*[sv._work for sv in solvers])
+        out = (c_int * cnt)()
+        rc = _lib.scs_hip_batch_plan(works, cnt, out)
+    finally:
+        for sv in ordered:
+            sv._lock.release()
+    if rc < 0:
+        raise RuntimeError("libscs_hip: " + last_error())
+    return [int(v) for v in out]
 
 
 # ---------------------------------------------------------------- kernel-level entry points (tests, bench)
