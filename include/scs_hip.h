@@ -192,6 +192,15 @@ int scs_hip_time_psd(ScsWork *w, int reps, double *out);
  * to the driver: for a process that shares its GPUs with allocators this library does not see (torch, RCCL, other processes). */
 void scs_hip_trim_pool(void);
 
+/* The block pool's account, read under the pool's lock (host counters only: no device work).  held_* = what the pool caches now;
+ * live_bytes = device bytes this library obtained from hipMalloc and has not handed back with hipFree yet (held blocks included: with no
+ * workspace alive live_bytes == held_bytes, and both are 0 after scs_hip_trim_pool); hits / misses = allocations since the process
+ * started that the pool served / that went to hipMalloc. */
+typedef struct {
+  size_t held_bytes, held_blocks, live_bytes, hits, misses;
+} ScsHipPoolStats;
+void scs_hip_pool_stats(ScsHipPoolStats *out);
+
 /* How many solves of this process were restarted because a spinning multi-workgroup kernel (multi-CU PSD sweeps, persistent CG)
  * timed out at a barrier — another process held part of the GPU — and were then finished without such kernels (tests). */
 long scs_hip_spin_fallbacks(void);

@@ -53,6 +53,10 @@ struct DevPool {
   std::mutex m;
   std::vector<std::pair<std::pair<int, size_t>, void *>> blocks;  // ((device, bytes), pointer)
   size_t cached = 0, cap = 0;
+  // the pool's account (scs_hip_pool_stats; host integers under `m`): live = bytes dev_malloc obtained from hipMalloc that no hipFree
+  // (dev_free, put()'s cap eviction, trim()) has returned yet — with no workspace alive, live == cached; hits / misses = allocations
+  // served from the pool / sent to hipMalloc since the process started
+  size_t live = 0, hits = 0, misses = 0;
   bool cap_read = false;
   static DevPool &inst() { static DevPool p; return p; }
   size_t capacity() {
@@ -68,7 +72,11 @@ struct DevPool {
         void *p = blocks[i].second;
         blocks.erase(blocks.begin() + (long)i);
         cached -= bytes;
-        if (opts().pool_poison)  // (labs: recycled blocks arrive poisoned) { (void)hipMemset(p, 0xFF, bytes); (void)hipDeviceSynchronize(); }
+        ++hits;
+        if (opts().pool_poison) {  // (labs: recycled blocks arrive poisoned)
+          (void)hipMemset(p, 0xFF, bytes);
+          (void)hipDeviceSynchronize();
+        }
         return p;
       }
     return nullptr;
@@ -84,6 +92,7 @@ struct DevPool {
     while (drop < blocks.size() && cached + bytes > capacity()) {
       (void)hipFree(blocks[drop].second);
       cached -= blocks[drop].first.second;
+      live -= blocks[drop].first.second;
       ++drop;
     }
     if (drop) blocks.erase(blocks.begin(), blocks.begin() + (long)drop);
@@ -99,7 +108,25 @@ struct DevPool {
     std::lock_guard<std::mutex> lk(m);
     for (auto &b : blocks) (void)hipFree(b.second);  // (blocks of other devices: hipFree takes any device's pointer)
     blocks.clear();
+    live -= cached;
     cached = 0;
+  }
+  void note_malloc(size_t bytes) {
+    std::lock_guard<std::mutex> lk(m);
+    live += bytes;
+    ++misses;
+  }
+  void note_free(size_t bytes) {
+    std::lock_guard<std::mutex> lk(m);
+    live -= bytes;
+  }
+  void stats(ScsHipPoolStats *out) {
+    std::lock_guard<std::mutex> lk(m);
+    out->held_bytes = cached;
+    out->held_blocks = blocks.size();
+    out->live_bytes = live;
+    out->hits = hits;
+    out->misses = misses;
   }
 };
 static thread_local int t_pool_release = 0;  // > 0: DevBuf / Arena releases on this thread go to the pool (see DevPool)
@@ -113,12 +140,14 @@ inline void *dev_malloc(size_t bytes) {
     e = hipMalloc(&p, bytes);
   }
   HIP_CHECK(e);
+  DevPool::inst().note_malloc(bytes);
   return p;
 }
 inline void dev_free(void *p, size_t bytes) {
   if (!p) return;
   if (t_pool_release > 0 && DevPool::inst().put(p, bytes)) return;
   (void)hipFree(p);
+  DevPool::inst().note_free(bytes);
 }
 
 // Workspace arena: small problems (a batch of them: BASELINE.json configs[4]) pay more for the ~100 hipMalloc /

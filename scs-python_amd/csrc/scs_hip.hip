@@ -499,6 +499,7 @@ void scs_hip_get_mark(const ScsWork *w, double *out) {
 long scs_hip_spin_fallbacks(void) { return g_spin_fallbacks.load(); }
 
 void scs_hip_trim_pool(void) { DevPool::inst().trim(); }
+void scs_hip_pool_stats(ScsHipPoolStats *out) { if (out) DevPool::inst().stats(out); }
 
 int scs_hip_psd_refine_stats(ScsWork *w, double *out, int cap) {
   if (!w || !out || cap < 0) return -1;

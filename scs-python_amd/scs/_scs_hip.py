@@ -88,6 +88,11 @@ class _ScsInfo(C.Structure):
                 ("aa_stats", _ScsAaStats), ("cg_iters", c_int)]
 
 
+class _ScsHipPoolStats(C.Structure):
+    _fields_ = [("held_bytes", C.c_size_t), ("held_blocks", C.c_size_t), ("live_bytes", C.c_size_t),
+                ("hits", C.c_size_t), ("misses", C.c_size_t)]
+
+
 # ---------------------------------------------------------------- library loading
 def _preload_hip_runtime():
     """Make sure exactly ONE HIP runtime ends up in the process.
@@ -204,6 +209,8 @@ def _load():
     lib.scs_hip_time_psd.argtypes = [C.c_void_p, c_int, _PD]
     lib.scs_hip_trim_pool.restype = None
     lib.scs_hip_trim_pool.argtypes = []
+    lib.scs_hip_pool_stats.restype = None
+    lib.scs_hip_pool_stats.argtypes = [C.POINTER(_ScsHipPoolStats)]
     lib.scs_hip_spin_fallbacks.restype = C.c_long
     lib.scs_hip_spin_fallbacks.argtypes = []
     lib.scs_hip_psd_refine_stats.restype = c_int
@@ -872,6 +879,13 @@ def proj_cone(z, cone, dual=False):
 def trim_pool():
     """return the library's cached device blocks to the driver (include/scs_hip.h scs_hip_trim_pool)"""
     _lib.scs_hip_trim_pool()
+
+
+def pool_stats():
+    """the block pool's account (include/scs_hip.h scs_hip_pool_stats): dict of held_bytes, held_blocks, live_bytes, hits, misses"""
+    st = _ScsHipPoolStats()
+    _lib.scs_hip_pool_stats(C.byref(st))
+    return {name: int(getattr(st, name)) for name, _ in _ScsHipPoolStats._fields_}
 
 
 def spin_fallbacks():
