@@ -150,7 +150,6 @@ struct GroupSolve {
   long l = 0;
   hipStream_t s = nullptr;
   bool has_P = false;
-  std::vector<char> mr_allowed_saved;
 
   // tables (one per kernel of the path; names follow the kernels)
   SCS_GTABLE(kVecThreads, d_sumsq) t_sumsq;
@@ -272,7 +271,7 @@ struct GroupSolve {
   static bool member_ok(const ScsHipWork *w) {
     if (w->At.cs.ok || w->Ar.cs.ok || w->At.has_slab || w->Ar.has_slab) return false;
     if (w->has_P && (w->Pf.cs.ok || w->Pf.has_slab)) return false;
-    if (w->persist_wgs > 0 || !w->log_csv_filename.empty() || w->mark_iter >= 0 || w->stgs.verbose) return false;  // (a verbose member prints its own table: solved by scs_solve)
+    if (!w->log_csv_filename.empty() || w->mark_iter >= 0 || w->stgs.verbose) return false;  // (a verbose member prints its own table: solved by scs_solve)
     if (w->n_psd_big > 0 || w->n_cs_big > 0 || w->cone.bsize > kBoxMultiMin) return false;
     if (w->aa.mem > 0 && !w->aa.tsqr) return false;
     return true;
@@ -763,15 +762,7 @@ struct GroupSolve {
       }
     }
     t_start = now_ms();  // behind the deferred setup: solve_time is the solve (ScsInfo as the reference fills it)
-    mr_allowed_saved.assign((size_t)G, 0);
-    for (int g = 0; g < G; ++g) {
-#ifdef SCS_HIP_LABS
-      mr_allowed_saved[(size_t)g] = W[(size_t)g]->mr_allowed ? 1 : 0;
-      W[(size_t)g]->mr_allowed = false;  // the grouped loop drives PCG steps through its own tables (minres.hpp: one workspace at a time)
-      W[(size_t)g]->mr_active = false;   // (a member that had switched to MINRES in a solve of its own runs PCG here, and may switch again later)
-#endif
-      W[(size_t)g]->begin_solve(sols[(size_t)g], infos[(size_t)g], warm_start);
-    }
+    for (int g = 0; g < G; ++g) W[(size_t)g]->begin_solve(sols[(size_t)g], infos[(size_t)g], warm_start);
     for (int g = 0; g < G; ++g) {
       if (dense)
         std::snprintf(infos[(size_t)g]->lin_sys_solver, sizeof(infos[(size_t)g]->lin_sys_solver),
@@ -1012,13 +1003,6 @@ struct GroupSolve {
       }
     }
     HIP_CHECK(hipStreamSynchronize(s));
-#ifdef SCS_HIP_LABS
-    for (int g = 0; g < G; ++g) {  //  what the group took from its members' Krylov state goes back
-      ScsHipWork *w = W[(size_t)g];
-      w->mr_allowed = mr_allowed_saved[(size_t)g] != 0;
-      if (w->mr_ready) w->mr_precond_stale = true;  // scale updates inside the group went through t_set_diag_r / t_precond only
-    }
-#endif
     if (opts().debug & DBG_GROUP)
       std::fprintf(stderr, "[scs-hip group] members %d, lock-step iterations %d, grouped launches %ld (%.1f per iteration), host syncs %d, %.1f ms (%.1f ms of it finishing members: un-scaling, s'y, downloads)\n",
                    G, lockstep_iters, launches, (double)launches / std::max(lockstep_iters, 1), syncs, now_ms() - t_start, t_finish);

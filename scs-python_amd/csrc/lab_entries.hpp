@@ -217,7 +217,6 @@ static void oneshot_cone_work(ScsHipWork &w, const ScsCone *k, scs_int m, int wa
   HIP_CHECK(hipGetDevice(&dev));
   w.device = dev;  // (spin_chain(), the occupancy query of psd_mc_members)
   w.stream = s;
-  w.owns_stream = false;
   w.m = m;
   w.psd_warm = warm;
   if (no_spin) w.psd_mc_cap = 0;
@@ -344,7 +343,6 @@ static int kkt_solve_entry(const ScsMatrix *A, const ScsMatrix *P, const scs_flo
     TmpStream ts;
     hipStream_t s = ts.s;
     w.stream = s;
-    w.owns_stream = false;
     const int n = A->n, m = A->m;
     w.n = n; w.m = m; w.l = (long)n + m + 1;
     w.has_P = P != nullptr;

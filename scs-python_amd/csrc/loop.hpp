@@ -86,12 +86,7 @@ static scs_int solve_impl(ScsHipWork *w, ScsSolution *sol, ScsInfo *info, scs_in
 
   int i;
   const int max_iters = w->stgs.max_iters;
-  // hipGraphs pay off when the iteration is launch/latency-bound (measured 8-14 % at l <= 1e4, nothing at
-  // l >= 3e5) and cost ~0.1 s to capture: build them lazily, only for small problems and long solves.
-  const long graph_max_l = opts().graph_max_l;  // (labs)
-  const bool graphs_wanted = w->graphs_enabled && !w->profile && l <= graph_max_l && !w->pipelined && !w->dense();
-  bool use_graphs = graphs_wanted && w->graphs_ready;
-  const bool run_ahead = w->pipelined && w->persist_wgs == 0 && !w->dense();  // (in-situ profiling samples ride along: enqueue_plain_iteration)
+  const bool run_ahead = w->pipelined && !w->dense();  // (in-situ profiling samples ride along: enqueue_plain_iteration)
   // an iteration is "plain" when the host has nothing to decide in it: no convergence check / print / log row,
   // no Anderson step, not the last one.  Plain iterations may be enqueued whole, and one ahead (run-ahead mode).
   auto is_plain = [&](int it) {
@@ -124,18 +119,14 @@ static scs_int solve_impl(ScsHipWork *w, ScsSolution *sol, ScsInfo *info, scs_in
     }
     if (run_ahead && (enq_upto >= i || is_plain(i))) {  // (already queued: is_plain may have changed its mind since)
       double t = now_ms();
-      if (enq_upto < i) { w->enqueue_plain_iteration(i, true); enq_upto = i; }
-      if (is_plain(i + 1) && enq_upto < i + 1) { w->enqueue_plain_iteration(i + 1, false); enq_upto = i + 1; }
+      if (enq_upto < i) { w->enqueue_plain_iteration(i); enq_upto = i; }
+      if (is_plain(i + 1) && enq_upto < i + 1) { w->enqueue_plain_iteration(i + 1); enq_upto = i + 1; }
       if (!w->finish_plain_iteration(i)) {
         w->recover_stalled_iteration(i);
         enq_upto = i;  // whatever was queued behind the stall did nothing
       }
       t_lin += now_ms() - t;
       continue;
-    }
-    if (graphs_wanted && !use_graphs && i == 64) {
-      w->build_graphs();
-      use_graphs = w->graphs_ready;
     }
     const bool aa_now = w->aa.mem > 0 && i > 0 && (i % w->stgs.acceleration_interval == 0);
     double t = now_ms();
@@ -148,39 +139,33 @@ static scs_int solve_impl(ScsHipWork *w, ScsSolution *sol, ScsInfo *info, scs_in
     const bool last = (i == max_iters - 1);
     const bool plain_iter = !(check || print_now || last || csv);
     t = now_ms();
-    w->project_lin_sys(i, use_graphs);  // ends with a stream sync (CG convergence flags)
+    w->project_lin_sys(i);  // ends with a stream sync (CG convergence flags)
     t_lin += now_ms() - t;
     t = now_ms();
-    if (use_graphs && plain_iter) {
-      HIP_CHECK(hipGraphLaunch(w->g_post, s));  // y, tau, cones, v += alpha (u - u_t)
-      w->v_norm_fresh = true;
-      t_cone += now_ms() - t;
-    } else {
-      w->enqueue_lin_sys_tail();
-      w->enqueue_cones();
-      if (!plain_iter)
-        hipLaunchKernelGGL(k_rsk, dim3(w->vb(l)), dim3(kVecThreads), 0, s, w->rsk.p, w->v.p, w->u.p, w->ut.p, w->diag_r.p, l);
-      t_cone += now_ms() - t;
-      if (csv) w->populate_residuals(i);
-      if (check) {
-        w->populate_residuals(i);
-        w->note_check_residuals();
-        if ((info->status_val = w->has_converged(i)) != 0) {
-          if (csv) w->log_csv_row(csv, i, now_ms() - t_start);
-          break;
-        }
-        if (w->stgs.time_limit_secs > 0 && (now_ms() - t_start) > 1e3 * w->stgs.time_limit_secs) break;
+    w->enqueue_lin_sys_tail();
+    w->enqueue_cones();
+    if (!plain_iter)
+      hipLaunchKernelGGL(k_rsk, dim3(w->vb(l)), dim3(kVecThreads), 0, s, w->rsk.p, w->v.p, w->u.p, w->ut.p, w->diag_r.p, l);
+    t_cone += now_ms() - t;
+    if (csv) w->populate_residuals(i);
+    if (check) {
+      w->populate_residuals(i);
+      w->note_check_residuals();
+      if ((info->status_val = w->has_converged(i)) != 0) {
+        if (csv) w->log_csv_row(csv, i, now_ms() - t_start);
+        break;
       }
-      if (print_now) {
-        w->populate_residuals(i);
-        std::printf("%6d|%9.2e|%9.2e|%9.2e|%9.2e|%9.2e|%9.2e\n", i, w->r.res_pri, w->r.res_dual, w->r.gap,
-                    0.5 * (w->r.pobj + w->r.dobj), w->scale, (now_ms() - t_start) / 1e3);
-        std::fflush(stdout);
-      }
-      if (w->stgs.adaptive_scale && check && i == w->r.last_iter) w->update_scale(i);
-      w->enqueue_v_update();
-      if (csv) w->log_csv_row(csv, i, now_ms() - t_start);
+      if (w->stgs.time_limit_secs > 0 && (now_ms() - t_start) > 1e3 * w->stgs.time_limit_secs) break;
     }
+    if (print_now) {
+      w->populate_residuals(i);
+      std::printf("%6d|%9.2e|%9.2e|%9.2e|%9.2e|%9.2e|%9.2e\n", i, w->r.res_pri, w->r.res_dual, w->r.gap,
+                  0.5 * (w->r.pobj + w->r.dobj), w->scale, (now_ms() - t_start) / 1e3);
+      std::fflush(stdout);
+    }
+    if (w->stgs.adaptive_scale && check && i == w->r.last_iter) w->update_scale(i);
+    w->enqueue_v_update();
+    if (csv) w->log_csv_row(csv, i, now_ms() - t_start);
     if (aa_now) {
       t = now_ms();
       w->aa_safeguard();

@@ -3,10 +3,10 @@
 // The product has 17 runtime knobs (INTEGRATION.md "Runtime knobs"; the Python loader adds SCS_HIP_LIB, SCS_HIP_RUNTIME and shares
 // SCS_HIP_RUNTIME_ENV).  They are parsed HERE, once per scs_init / kernel-level entry point (refresh_options(): a test may change the
 // environment between two workspaces of one process; a workspace keeps what it was created with), never at the point of use.
-// Everything else that rounds 1-5 could switch at run time — the experiments that lost (K2 without p, MINRES, the persistent CG kernel,
-// hipGraph replay, cooperative launches, the in-kernel combine of split layouts, the gather-ahead schedule ...) and the lab switches of
-// the kernels — is a compile-time default in the product and only reads the environment in the `-DSCS_HIP_LABS` build
-// (scs-python_amd/Makefile `make labs` -> libscs_hip_labs.so, used by tools/ and by the tests marked `labs`).
+// Everything else that rounds 1-5 could switch at run time — the experiments that lost and still have code (cooperative launches, the
+// in-kernel combine of split layouts, the gather-ahead schedule ...) and the lab switches of the kernels — is a compile-time default in
+// the product and only reads the environment in the `-DSCS_HIP_LABS` build (scs-python_amd/Makefile `make labs` -> libscs_hip_labs.so,
+// used by tools/ and by the tests marked `labs`).  Four closed experiments of the CG path have no code any more: DESIGN.md §4.
 #pragma once
 #include <atomic>
 #include <cstdlib>
@@ -41,13 +41,6 @@ struct Options {
   // (process-wide, read once where they are used: SCS_HIP_STREAMS, SCS_HIP_POOL_MB, SCS_HIP_CTRLC, SCS_HIP_RUNTIME_ENV)
 
   // ------------------------------------------------------------------ labs (compile-time defaults in the product)
-  bool k1dot = false;          // p'Gp from K1 (cg_k1dot.hpp): K2 3 us faster, the iteration 1.7 % slower
-  int krylov = 0;              // 1 MINRES, 2 auto (minres.hpp): 2.1 x slower on whole config-3 solves
-  double mr_tolf = 1.0;
-  bool mr_check = false;
-  int persist_w = 0, persist_g = 1;  // persistent one-launch CG (cg_persist.hpp): not faster than launch-per-kernel
-  bool graph = false;          // hipGraph replay of the iteration (SCS_HIP_PIPELINE=0 only): 5 % slower than eager at config 2
-  long graph_max_l = 1000000L;
   bool psd_coop = false;       // hipLaunchCooperativeKernel for the multi-CU sweeps: ~2 ms per launch in a warm process
   int cs_sched = 3;            // 1 gather-ahead kernel, 2 braid, 3 braid + stream loads before the barrier (shipped)
   bool cs_combine = false;     // in-kernel combine of split layouts: eats the gather gain
@@ -95,16 +88,6 @@ struct Options {
 #ifdef SCS_HIP_LABS
     auto pos_int = [](const char *name, int dflt) { const char *e = getenv(name); const int v = e ? atoi(e) : 0; return v > 0 ? v : dflt; };
     auto pos_dbl = [](const char *name, double dflt) { const char *e = getenv(name); const double v = e ? atof(e) : 0.; return v > 0. ? v : dflt; };
-    o.k1dot = is1(getenv("SCS_HIP_K1DOT"));
-    if (const char *e = getenv("SCS_HIP_KRYLOV")) o.krylov = e[0] == 'm' ? 1 : e[0] == 'a' ? 2 : 0;
-    o.mr_tolf = pos_dbl("SCS_HIP_MR_TOLF", 1.0);
-    o.mr_check = getenv("SCS_HIP_MR_CHECK") != nullptr;
-    if (const char *e = getenv("SCS_HIP_PERSIST")) {  // "W" or "WxG": W workgroups of G x 256 lanes
-      o.persist_w = atoi(e);
-      if (const char *x = strchr(e, 'x')) o.persist_g = atoi(x + 1);
-    }
-    o.graph = !is0(getenv("SCS_HIP_GRAPH"));
-    if (const char *e = getenv("SCS_HIP_GRAPH_MAX_L")) o.graph_max_l = atol(e);
     o.psd_coop = is1(getenv("SCS_HIP_PSD_COOP"));
     if (const char *e = getenv("SCS_HIP_CS_SCHED")) o.cs_sched = atoi(e);
     o.cs_combine = is1(getenv("SCS_HIP_CS_COMBINE"));

@@ -31,18 +31,11 @@
 #include "normalize_dev.hpp"
 #include "psd.hpp"
 #include "spectral.hpp"
-#ifdef SCS_HIP_LABS  // experiments that lost their measurement (options.hpp): compiled into libscs_hip_labs.so only
-#include "cg_persist.hpp"
-#include "minres.hpp"
-#endif
 #include "dense.hpp"
 #include "setup_dev.hpp"
 #include "setup_cs_dev.hpp"
 #include "spmv.hpp"
 #include "vec.hpp"
-#ifdef SCS_HIP_LABS
-#include "cg_k1dot.hpp"
-#endif
 
 #include "runtime.hpp"
 #include "device_csr.hpp"
@@ -406,27 +399,13 @@ int scs_hip_time_matvec(ScsWork *w, int reps, double *out) {
     HIP_CHECK(hipSetDevice(w->device));
     hipStream_t s = w->stream;
     w->finish_pending_setup();  // (R lives in the products)
-    // the products exactly as the CG step of this workspace launches them (k1dot: cg_k1dot.hpp)
-    for (int i = 0; i < 2; ++i) {
-#ifdef SCS_HIP_LABS
-      if (w->k1dot) { w->matvec_k1dot(w->cg_p.p, nullptr, nullptr); continue; }
-#endif
-      w->matvec(w->cg_p.p, nullptr);
-    }
+    // the products exactly as the CG step of this workspace launches them
+    for (int i = 0; i < 2; ++i) w->matvec(w->cg_p.p, nullptr);
     HIP_CHECK(hipEventRecord(w->ev[0], s));
-    for (int i = 0; i < reps; ++i) {
-#ifdef SCS_HIP_LABS
-      if (w->k1dot) { launch_spmv(w->Ar.view(), w->cg_p.p, EpiDivRDot{w->tmp_m.p, w->rdy(), w->part_k1.p}, nullptr, s); continue; }
-#endif
-      launch_spmv(w->Ar.view(), w->cg_p.p, EpiDivR{w->tmp_m.p, w->rdy()}, nullptr, s);
-    }
+    for (int i = 0; i < reps; ++i) launch_spmv(w->Ar.view(), w->cg_p.p, EpiDivR{w->tmp_m.p, w->rdy()}, nullptr, s);
     HIP_CHECK(hipEventRecord(w->ev[1], s));
-    for (int i = 0; i < reps; ++i) {
-#ifdef SCS_HIP_LABS
-      if (w->k1dot) { launch_spmv(w->At.view(), w->tmp_m.p, EpiAtRaw{w->cg_Gp.p, w->gp2()}, nullptr, s); continue; }
-#endif
+    for (int i = 0; i < reps; ++i)
       launch_spmv(w->At.view(), w->tmp_m.p, EpiGp{w->cg_Gp.p, w->cg_p.p, w->rdx(), w->has_P ? 1 : 0, w->part.p, w->gp2()}, nullptr, s);
-    }
     HIP_CHECK(hipEventRecord(w->ev[2], s));
     HIP_CHECK(hipEventSynchronize(w->ev[2]));
     float a = 0, b = 0, c = 0;

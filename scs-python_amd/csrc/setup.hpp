@@ -188,19 +188,10 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
   for (double x : w->b_orig) w->nm_b_orig = std::max(w->nm_b_orig, std::fabs(x));
   for (double x : w->c_orig) w->nm_c_orig = std::max(w->nm_c_orig, std::fabs(x));
 
-  {
-#ifdef SCS_HIP_LABS
-    w->graphs_enabled = opts().graph;   // hipGraph replay of the iteration when the host looks at every iteration
-#endif
-    w->pipelined = opts().pipeline;     // SCS_HIP_PIPELINE=0: the host looks at the CG flags in every iteration
-    w->pipe_chunk_override = opts().pipe_chunk;
-  }
-  if (!w->pipelined && w->graphs_enabled) {  // hipGraph capture needs a stream nobody else enqueues on: a private one
-    HIP_CHECK(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
-  } else {
-    w->stream = g_streams.acquire(w->device, &w->stream_shared);
-    w->pooled_stream = true;
-  }
+  w->pipelined = opts().pipeline;     // SCS_HIP_PIPELINE=0: the host looks at the CG flags in every iteration
+  w->pipe_chunk_override = opts().pipe_chunk;
+  w->stream = g_streams.acquire(w->device, &w->stream_shared);
+  w->pooled_stream = true;
   for (auto &e : w->ev) HIP_CHECK(hipEventCreate(&e));
   {  // one pinned, device-mapped block: [h_pin 256 f64 | AA h_pin 256 f64 | params 2 x P_COUNT f64 | flags 3 x F_COUNT i32]
     char *blk = (char *)g_pinned.acquire();
@@ -342,28 +333,6 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
   w->part.alloc_zero(w->part_len, s);
   w->part2.alloc_zero(2 * kMaxVecBlocks, s);
   w->part_v.alloc_zero(kMaxVecBlocks, s);
-  {
-    // Persistent one-launch CG (cg_persist.hpp): bit-identical to the launch-per-kernel path, but NOT faster on
-    // this GPU (a grid barrier costs what a kernel boundary costs: the L2 invalidate + the dependent-load chain
-    // of the next phase; measured r01: 0.22 ms/iter either way on a config-5 problem with 16 workgroups, 2x slower
-    // with one) => off unless asked for.  SCS_HIP_PERSIST = "W" or "WxG": W workgroups of G (1, 2, 4) 256-lane groups.
-    const bool eligible = !w->At.has_slab && !w->Ar.has_slab && (!w->has_P || !w->Pf.has_slab) && !w->At.cs.ok && !w->Ar.cs.ok &&
-                          (!w->has_P || !w->Pf.cs.ok) &&
-                          2 * vec_blocks(l) + 2 * vec_blocks(std::max(n, m)) <= 2 * kMaxVecBlocks;
-#ifdef SCS_HIP_LABS
-    int wgs = 0, ng = 2;
-    if (opts().persist_w > 0) {
-      wgs = eligible ? std::max(0, std::min(opts().persist_w, kCgPersistMaxWgs)) : 0;
-      const int b = opts().persist_g;
-      if (b == 1 || b == 2 || b == 4) ng = b;
-    }
-    w->persist_wgs = wgs;
-    w->persist_ng = ng;
-    if (wgs > 0) w->persist_bar.alloc_zero(2, s);
-#else
-    (void)eligible;
-#endif
-  }
   w->sc.alloc_zero(S_COUNT, s);
   w->out.alloc_zero(256, s);
   w->fl.alloc_zero(F_COUNT, s);
@@ -394,13 +363,7 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
              stgs->acceleration_relaxation, /*safeguard_factor=*/1.0, /*max_weight_norm=*/1e10, s);
   mark("vectors, b/c scaling, cones, AA workspace");
   // ---- R, preconditioner (or G^{-1}), pre-solved g ----
-  if (w->dense()) {
-    w->dense_alloc();
-#ifdef SCS_HIP_LABS
-    w->persist_wgs = 0;
-#endif
-  }
-  w->decide_k1dot(s);
+  if (w->dense()) w->dense_alloc();
   {
     // Round 5, late: the indirect path defers it too (SCS_HIP_LAZY_SETUP=0: inside scs_init) — its cold PCG for g is ~50 steps = 150 dependent
     // launches, three quarters of the dispatch chain of a small problem's scs_init; a batch runs it as ONE grouped cold solve (batch.hpp

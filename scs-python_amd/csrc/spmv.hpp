@@ -241,10 +241,10 @@ struct EpiResDual {
 
 // One row block of the CSR-stream mat-vec, executed by kSpmvThreads consecutive lanes (tid = 0..255 inside the
 // group).  `nb` = number of row blocks of the whole product = stride of the epilogue's partial arrays.
-// Shared by the one-launch-per-product kernel below and by the persistent CG kernel (cg_persist.hpp), so both
-// paths produce the same bits.  sync() must synchronise the lanes that share `prod` / `red`.
-// UNIFORM: several groups share one hardware barrier (persistent kernel), so every call — short-row block,
-// long-row block or idle (`active` = false) — executes the same number of sync() calls.
+// Called by the one-launch-per-product kernel below.  sync() must synchronise the lanes that share `prod` / `red`.
+// UNIFORM: for a caller whose groups share one hardware barrier, so every call — short-row block, long-row block or
+// idle (`active` = false) — executes the same number of sync() calls.  (Its one user, the persistent CG kernel, is
+// gone: DESIGN.md §4.)
 template <class Epi, bool UNIFORM = false, class Sync>
 __device__ __forceinline__ void spmv_stream_block(const CsrView &A, const double *__restrict__ x, const Epi &epi, int b, int nb,
                                                   double *prod, double *red, int tid, Sync sync, bool active = true) {

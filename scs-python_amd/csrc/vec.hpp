@@ -40,7 +40,7 @@ enum : int {
 // queued behind it returns at once (the CG-step kernels through F_DONE, the others through F_STALL), so nothing is
 // computed from an unconverged linear solve; the host then lowers both flags and resumes from the intact CG state.
 
-// per-iteration host scalars, kept in mapped pinned memory so that captured hipGraphs stay static
+// per-iteration host scalars, kept in mapped pinned memory: queued kernels read them in place, the launch arguments never change
 enum : int { P_DO_SCALE = 0, P_RES_MIN, P_IPOW, P_FIRST, P_PSD_TOL2, P_COUNT = 8 };
 
 __host__ __device__ inline int vec_blocks(long n) {
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(kVecThreads) void k_fin_head(const double *prep_par
 // itself (a few hundred L2-resident doubles, fixed order => identical alpha everywhere), so no separate
 // single-workgroup "finalize" launch sits between the SpMV and this kernel.  z'r comes from the slot of the
 // current CG step (two slots, selected by F_STEP, which workgroup 0 of the A kernel bumps once per step).
-// Body of one (virtual) block b of nb: shared with the persistent CG kernel (cg_persist.hpp).
+// Body of one (virtual) block b of nb (virtual: a caller may run several blocks per workgroup; the kernels here run one).
 // `alpha_of()` is called AFTER the first element of every lane's two loops has been requested: those loads do not depend on
 // alpha, so the reduction of the partials that alpha comes from (a dependent chain of ~2 us) no longer runs in front of an idle
 // memory pipe (round 4; same operations on the same operands in the same order: same bits).

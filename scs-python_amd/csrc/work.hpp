@@ -8,7 +8,7 @@ using namespace scship;
 static void write_csv_row(FILE *f, int iter, const Residuals &r, double scale, const double *diffs, double aa_norm,
                           double time_s);
 
-// A spinning multi-workgroup kernel (k_psd_sweep_mc, k_cg_persist) gave up at a barrier: scs_solve restarts the solve without them
+// A spinning multi-workgroup kernel (k_psd_sweep_mc) gave up at a barrier: scs_solve restarts the solve without it
 struct SpinTimeout : std::runtime_error {
   using std::runtime_error::runtime_error;
 };
@@ -51,7 +51,7 @@ struct ScsHipWork {
   std::string log_csv_filename, write_data_filename;
 
   hipStream_t stream = nullptr;
-  bool owns_stream = true, pooled_stream = false, stream_shared = false;
+  bool pooled_stream = false, stream_shared = false;  // pooled_stream: a real workspace (scs_init: g_streams); the stack workspaces of the kernel-level entry points borrow theirs
   void *pinned_block = nullptr;  // all pinned host scalars / flags of the workspace (g_pinned)
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // [3]: behind K3 in a sampled CG step of a problem with P
   double *h_pin = nullptr;  // pinned scalars
@@ -71,27 +71,6 @@ struct ScsHipWork {
   bool cone_sampled[2] = {false, false};
   double prof_cone_ms = 0;
   long prof_cone_n = 0;
-
-  // hipGraphs of the launch-bound inner loop (built lazily at the first solve):
-  //   g_pre[i] : iterate normalisation, rhs, CG start + kGraphSteps[i] CG steps + flag read-back
-  //   g_cg[i]  : kGraphSteps[i] further CG steps + flag read-back
-  //   g_post   : y recovery, tau, cone projections, dual update (iterations without a convergence check)
-  static constexpr int kNumGraphs = 5;
-  const int kGraphSteps[kNumGraphs] = {1, 2, 4, 8, 16};
-  hipGraphExec_t g_pre[kNumGraphs] = {}, g_cg[kNumGraphs] = {}, g_post = nullptr;
-  bool graphs_ready = false;
-#ifdef SCS_HIP_LABS
-  bool graphs_enabled = true;
-#else
-  static constexpr bool graphs_enabled = false;  // (hipGraph replay lives in the labs build: 5 % slower than eager launches at config 2)
-#endif
-  // small problems: the whole PCG solve of an iteration is one persistent launch (cg_persist.hpp)
-#ifdef SCS_HIP_LABS
-  int persist_wgs = 0, persist_ng = 1;  // 0 = launch-per-kernel path
-  DevBuf<unsigned> persist_bar;
-#else
-  static constexpr int persist_wgs = 0, persist_ng = 1;  // (the persistent kernel lives in the labs build: never faster than launch-per-kernel)
-#endif
 
   DeviceCsr At;  // CSR(A') == caller's CSC(A): rows n, cols m   (x-space outputs)
   DeviceCsr Ar;  // CSR(A): rows m, cols n                        (y-space outputs)
@@ -212,7 +191,7 @@ struct ScsHipWork {
                            psd_refine_default(false), 0);
         hipLaunchKernelGGL(k_psd_gemm<PSD_G1>, gg, gb, 0, stream, base, B, psd_scratch.p, psd_warm, stall, gper);
         hipLaunchKernelGGL(k_psd_gemm<PSD_G2>, gg, gb, 0, stream, base, B, psd_scratch.p, psd_warm, stall, gper);
-        int mc = (in_capture || !fl.p) ? 1 : psd_mc_members(big);  // (the multi-CU kernel polls the workspace's error flag at its barriers)
+        int mc = !fl.p ? 1 : psd_mc_members(big);  // (the multi-CU kernel polls the workspace's error flag at its barriers)
         PsdRefineCfg R = psd_refine;
         if ((size_t)32 * psd_max_np * sizeof(double) > 160 * 1024) R.on = 0;  // k_psd_apply_q keeps two 16-row strips in LDS
         std::unique_ptr<SpinLink> link;
@@ -370,7 +349,6 @@ struct ScsHipWork {
     }
     return std::max(G, 1);
   }
-  bool in_capture = false;
   // stopping level of the PSD sweeps (psd.hpp psd_offtol2): inside the ADMM loop the iteration's P_PSD_TOL2, else nullptr = fixed 1e-8
   const double *psd_tol2 = nullptr;
   static bool psd_tol_adaptive() { return opts().psd_tol_adaptive; }  // SCS_HIP_PSD_TOL=fixed: A/B
@@ -442,7 +420,7 @@ struct ScsHipWork {
   void note_cg_sample(hipEvent_t *e) {
     float a = 0, b = 0, c = 0;
     if (hipEventElapsedTime(&a, e[0], e[1]) != hipSuccess) return;
-    if (has_P) {  // (the labs-only k1dot path excludes P)
+    if (has_P) {
       if (hipEventElapsedTime(&c, e[1], e[3]) != hipSuccess || hipEventElapsedTime(&b, e[3], e[2]) != hipSuccess) return;
       prof_ms[2] += c; prof_n[2]++;
     } else if (hipEventElapsedTime(&b, e[1], e[2]) != hipSuccess) {
@@ -462,14 +440,11 @@ struct ScsHipWork {
   ~ScsHipWork() {
     // nothing of this workspace is in flight once its stream is idle: its blocks may be handed to the next workspace without hipFree
     // (real workspaces only: the stack workspaces of the kernel-level entry points borrow a stream that is gone by now)
-    if (stream && (pooled_stream || owns_stream) && hipStreamSynchronize(stream) == hipSuccess) {
+    if (stream && pooled_stream && hipStreamSynchronize(stream) == hipSuccess) {
       pool_window_end.armed = true;
       ++t_pool_release;
     }
     spin_unregister();
-    for (auto &g : g_pre) if (g) (void)hipGraphExecDestroy(g);
-    for (auto &g : g_cg) if (g) (void)hipGraphExecDestroy(g);
-    if (g_post) (void)hipGraphExecDestroy(g_post);
     if (pinned_block) {
       g_pinned.release(pinned_block);
     } else {  // (stack workspaces of the kernel-level entry points allocate what they need themselves)
@@ -485,7 +460,6 @@ struct ScsHipWork {
     for (auto &es : ev_cone) for (auto &e : es) if (e) (void)hipEventDestroy(e);
     for (auto &e : ev) if (e) (void)hipEventDestroy(e);
     if (stream && pooled_stream) g_streams.release(device, stream);
-    else if (stream && owns_stream) (void)hipStreamDestroy(stream);
   }
 
 #include "work_linsys.inl"

@@ -1,5 +1,5 @@
 // work_admm.inl — members of ScsHipWork (work.hpp): the steps of an ADMM iteration as enqueue functions, the run-ahead queue and its stall
-// recovery, (labs) graph capture, project_lin_sys and the cone projections
+// recovery, project_lin_sys and the cone projections
   // ------------------------------------------------------------ ADMM steps
   void set_iter_params(int iter, int slot = 0) {
     h_params = h_params_base + slot * P_COUNT;
@@ -27,11 +27,6 @@
     // tolerance, ||r0||, r0'M r0, step counter, zero-rhs short circuit: one finalize launch
     hipLaunchKernelGGL(k_fin_head, dim3(1), dim3(kVecThreads), 0, stream, part2.p, nbl, part.p, At.nwg(), d_params, sc.p, fl.p,
                        ut.p, (long)n + m, stall);
-    // (k1dot: the first step's alpha needs sum r_x p0^2 of the p0 = M r0 the start has just formed)
-#ifdef SCS_HIP_LABS
-    if (k1dot) hipLaunchKernelGGL(k_pp_part, dim3(vb(n)), dim3(kVecThreads), 0, stream, (const double *)cg_p.p, rdx(), n, part_pp.p, stall);
-#endif
-    if (mr_active) enqueue_mr_start();
   }
   // dense direct variant of the linear solve of an iteration: rhs = R_x v_x - A' v_y;  u~_x = G^{-1} rhs;  u~_y = v_y + R_y^{-1} A u~_x.
   // Three dependent launches behind k_prep, no convergence flag: nothing here (or behind it) waits for the device.
@@ -49,38 +44,6 @@
     hipLaunchKernelGGL(k_sumsq, dim3(vb(l)), dim3(kVecThreads), 0, stream, v.p, l, part_v.p);
     v_norm_fresh = true;
   }
-#ifdef SCS_HIP_LABS
-  // small-problem variant: same normalisation / warm start, then ONE launch for tolerance, CG start and CG loop
-  void enqueue_lin_sys_persist() {
-    std::unique_ptr<SpinLink> link;
-    if (!in_capture) link.reset(new SpinLink(this));  // (a captured launch is replayed outside any chain: SCS_HIP_PERSIST is a lab switch)
-    const int nbl = vb(l);
-    hipLaunchKernelGGL(k_prep, dim3(nbl), dim3(kVecThreads), 0, stream, v.p, v_prev.p, ut.p, ws.p, u.p, g.p, diag_r.p, n, m,
-                       d_params, part_v.p, nbl, sc.p, part2.p, stall);
-    CgPersistArgs a{};
-    a.Ar = Ar.view().csr; a.At = At.view().csr;
-    if (has_P) a.Pf = Pf.view().csr;
-    a.has_P = has_P ? 1 : 0; a.n = n; a.m = m;
-    a.diag_r = diag_r.p; a.v = v.p; a.ws = ws.p; a.ut = ut.p;
-    a.r = cg_r.p; a.p = cg_p.p; a.Gp = cg_Gp.p; a.z = tmp_m.p; a.M = cg_M.p;
-    a.part = part.p; a.part2 = part2.p + 2 * nbl; a.part_p = part2.p; a.np_p = nbl;
-    a.params = d_params; a.sc = sc.p; a.fl = fl.p; a.max_its = 10 * n; a.bar = persist_bar.p;
-    if (persist_ng == 4)
-      hipLaunchKernelGGL(k_cg_persist<4>, dim3(persist_wgs), dim3(4 * kVecThreads), cg_persist_lds<4>(), stream, a);
-    else if (persist_ng == 2)
-      hipLaunchKernelGGL(k_cg_persist<2>, dim3(persist_wgs), dim3(2 * kVecThreads), cg_persist_lds<2>(), stream, a);
-    else
-      hipLaunchKernelGGL(k_cg_persist<1>, dim3(persist_wgs), dim3(kVecThreads), cg_persist_lds<1>(), stream, a);
-    enqueue_flag_readback();
-  }
-  void finish_lin_sys_persist() {
-    sync_flags();
-    if (h_flags[F_PERSIST_ERR]) throw SpinTimeout("persistent CG kernel: grid barrier timed out");
-    last_cg_iters = h_flags[F_ITERS];
-    note_cg_iters(last_cg_iters);
-    tot_cg_iters += last_cg_iters;
-  }
-#endif
   // tau (the y block is already in ut_y: it was carried along the CG recurrence)
   void enqueue_lin_sys_tail() {
     const int nb1 = vb(l - 1);
@@ -112,14 +75,10 @@
 
   // ---- run-ahead mode: one whole plain iteration (no convergence check, no AA, no logging) in the queue ----
   // head + CG chunk + tau/cones/v update + flag copy + event; nothing here waits for the device.
-  // queue_empty: nothing of an earlier iteration is still in the queue.  Only then may the Krylov method change: a
-  // stalled iteration i is finished by run_cg(mode 2) with the method of the workspace, and a switch made while i + 1 was being
-  // enqueued would continue i's PCG recurrence with MINRES steps that never had their start.
-  void enqueue_plain_iteration(int iter, bool queue_empty) {
+  void enqueue_plain_iteration(int iter) {
     const int slot = iter & 1;
     set_iter_params(iter, slot);
     ensure_v_norm();
-    if (queue_empty) mr_decide();
     stall = fl.p + F_STALL;
     stall_fl = fl.p;
     enqueue_lin_sys_head();
@@ -129,9 +88,7 @@
     if (pipe_chunk_override > 0) chunk = pipe_chunk_override;
     prof_step[slot] = -1;
     for (int k = 0; k < chunk; ++k) {
-      if (mr_active) {
-        enqueue_mr_step(k);
-      } else if (profile && k == chunk / 2) {  // one CG step of the queued iteration bracketed by events: nothing waits for them here
+      if (profile && k == chunk / 2) {  // one CG step of the queued iteration bracketed by events: nothing waits for them here
         for (auto &e : ev_prof[slot]) if (!e) HIP_CHECK(hipEventCreate(&e));
         enqueue_cg_step(ut.p, ut.p + n, ev_prof[slot]);
         prof_step[slot] = k;
@@ -139,7 +96,6 @@
         enqueue_cg_step(ut.p, ut.p + n);
       }
     }
-    if (mr_active) enqueue_mr_finish();
     enqueue_lin_sys_tail();
     cone_sampled[slot] = false;
     if (profile) {  // the nonlinear cone projections of this queued iteration between two events (read when it is finished)
@@ -223,61 +179,12 @@
     v_norm_fresh = true;
   }
 
-#ifdef SCS_HIP_LABS
-  hipGraphExec_t capture(const std::function<void()> &body) {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    in_capture = true;
-    try {
-      body();
-    } catch (...) {
-      in_capture = false;
-      (void)hipStreamEndCapture(stream, &graph);
-      if (graph) (void)hipGraphDestroy(graph);
-      throw;
-    }
-    in_capture = false;
-    HIP_CHECK(hipStreamEndCapture(stream, &graph));
-    HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    HIP_CHECK(hipGraphDestroy(graph));
-    return exec;
-  }
-  void build_graphs() {
-    if (graphs_ready || !graphs_enabled) return;
-    const bool keep_fresh = v_norm_fresh;  // capturing enqueues nothing: host-side state must not move
-    if (persist_wgs > 0) g_pre[0] = capture([&] { enqueue_lin_sys_persist(); });
-    for (int i = 0; i < kNumGraphs && persist_wgs == 0; ++i) {
-      const int c = kGraphSteps[i];
-      g_pre[i] = capture([&] {
-        enqueue_lin_sys_head();
-        for (int k = 0; k < c; ++k) enqueue_cg_step(ut.p, ut.p + n);
-        enqueue_flag_readback();
-      });
-      g_cg[i] = capture([&] {
-        for (int k = 0; k < c; ++k) enqueue_cg_step(ut.p, ut.p + n);
-        enqueue_flag_readback();
-      });
-    }
-    g_post = capture([&] {
-      enqueue_lin_sys_tail();
-      enqueue_cones();
-      enqueue_v_update();
-    });
-    v_norm_fresh = keep_fresh;
-    graphs_ready = true;
-  }
-#else
-  void build_graphs() {}
-#endif
-
-  void project_lin_sys(int iter, bool graph) {
+  void project_lin_sys(int iter) {
     // The parameter block is host memory the kernels read in place, and the cones of the previous iteration (enqueued, not
     // waited for) read P_PSD_TOL2 from this slot.  It moves after convergence checks (the stream is idle then) and ONCE
     // more, when the residual-tied level is switched off (psd_tol2_for): wait before overwriting it.  (Run-ahead
     // iterations alternate between two slots instead: enqueue_plain_iteration.)
     if (n_psd + n_cs > 0 && psd_tol2_for(iter) != h_params_base[P_PSD_TOL2]) HIP_CHECK(hipStreamSynchronize(stream));
-    mr_decide();
     set_iter_params(iter);
     ensure_v_norm();
     if (dense()) {
@@ -285,25 +192,8 @@
       last_cg_iters = 0;
       return;
     }
-#ifdef SCS_HIP_LABS
-    if (persist_wgs > 0) {
-      if (graph) HIP_CHECK(hipGraphLaunch(g_pre[0], stream));
-      else enqueue_lin_sys_persist();
-      finish_lin_sys_persist();
-      return;
-    }
-#endif
-    if (kLabsBuild && graph && !mr_active) {
-      int gi = 0;
-      const int want = std::max(1, std::min(last_cg_iters + 2, kGraphSteps[kNumGraphs - 1]));
-      while (gi + 1 < kNumGraphs && kGraphSteps[gi] < want) ++gi;  // smallest captured chunk that covers `want`
-      HIP_CHECK(hipGraphLaunch(g_pre[gi], stream));
-      sync_flags();
-      run_cg(ut.p, ws.p, 10 * n, 2);
-    } else {
-      enqueue_lin_sys_head();
-      run_cg(ut.p, ws.p, 10 * n, 1);  // the CG start is already enqueued: continue eagerly
-    }
+    enqueue_lin_sys_head();
+    run_cg(ut.p, ws.p, 10 * n, 1);  // the CG start is already enqueued: continue eagerly
   }
 
   // in-place projection of the m-slice y onto K (dual=0) or K* (dual=1), rows z/l excluded (handled by caller)

@@ -108,12 +108,8 @@
     (void)hipStreamSynchronize(stream);
     (void)hipGetLastError();
     psd_mc_cap = 0;
-#ifdef SCS_HIP_LABS
-    if (persist_wgs > 0) { persist_wgs = 0; graphs_ready = false; }
-#endif
     stall = nullptr;
     stall_fl = nullptr;
-    in_capture = false;
     HIP_CHECK(hipMemsetAsync(fl.p, 0, sizeof(int) * F_COUNT, stream));
     std::memset(h_flags, 0, sizeof(int) * F_COUNT);
     for (auto &hf : h_flags_slot) if (hf) std::memset(hf, 0, sizeof(int) * F_COUNT);

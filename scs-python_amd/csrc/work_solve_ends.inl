@@ -2,23 +2,18 @@
   // ---- the two ends of a solve, shared by scs_solve and the grouped solve (batch.hpp) ----
   // per-solve state, info header and the initial iterate (cold: v = [0; 0; 1]; warm: from sol)
   void begin_solve(ScsSolution *sol, ScsInfo *info, int warm_start) {
-    if (krylov_mode() == 1) mr_decide();  // (forced: from the first iteration, and named in the banner)
     std::memset(info, 0, sizeof(*info));
     info->setup_time = setup_time;
     if (dense())
       std::snprintf(info->lin_sys_solver, sizeof(info->lin_sys_solver), "dense-direct HIP gfx950 (explicit inverse of the reduced KKT matrix, order %d; fp64 MFMA Gauss-Jordan)", n);
-    else if (persist_wgs > 0)
-      std::snprintf(info->lin_sys_solver, sizeof(info->lin_sys_solver), "sparse-indirect HIP gfx950 (PCG, persistent %dx%d-wave kernel)",
-                    persist_wgs, 4 * persist_ng);
     else {
       // what became of rows too long for the pass layout's count fields (A / A' / P): cut into pieces that ride in the passes, or
       // peeled off and summed from the plain CSR by the side launch
       const bool pieces = (Ar.cs.ok && Ar.cs.npieces > 0) || (At.cs.ok && At.cs.npieces > 0) || (has_P && Pf.cs.ok && Pf.cs.npieces > 0);
       const bool peeled = !pieces && ((Ar.cs.ok && Ar.npeel > 0) || (At.cs.ok && At.npeel > 0) || (has_P && Pf.cs.ok && Pf.npeel > 0));
-      std::snprintf(info->lin_sys_solver, sizeof(info->lin_sys_solver), "sparse-indirect HIP gfx950 (%s SpMV%s, %s)",
+      std::snprintf(info->lin_sys_solver, sizeof(info->lin_sys_solver), "sparse-indirect HIP gfx950 (%s SpMV%s, PCG)",
                     At.cs.ok ? "column-sorted pass" : At.has_slab ? "L2-blocked slab" : "CSR-stream",
-                    pieces ? ", long rows in pieces" : peeled ? ", long rows peeled" : "",
-                    mr_active ? "MINRES, zero-cone block un-eliminated" : "PCG");
+                    pieces ? ", long rows in pieces" : peeled ? ", long rows peeled" : "");
     }
     // per-solve state
     sum_log_scale_factor = 0; n_log_scale_factor = 0; last_scale_update_iter = 0; scale_updates = 0;
@@ -66,10 +61,6 @@
   // the verdict of the last convergence check (SCS_UNFINISHED: none fired).
   void finish_solve(ScsSolution *sol, ScsInfo *info, int i, double t_start, double t_lin, double t_cone, double t_acc,
                     bool grouped = false) {
-    if (mr_active && !std::strstr(info->lin_sys_solver, "MINRES")) {  // the auto mode switched inside this solve
-      char *at = std::strstr(info->lin_sys_solver, "PCG)");
-      if (at) std::snprintf(at, sizeof(info->lin_sys_solver) - (size_t)(at - info->lin_sys_solver), "PCG, then MINRES)");
-    }
     // ---- finalize ----
     const int max_iters = stgs.max_iters;
     if (!grouped) {  // (the grouped solve has read this problem's flags and residuals already)

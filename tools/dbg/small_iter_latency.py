@@ -1,4 +1,4 @@
-"""per-iteration latency of ONE config-5 problem (the straggler of the batch): run-ahead loop, hipGraph loop, and a grouped solve of 2"""
+"""per-iteration latency of ONE config-5 problem (the straggler of the batch): run-ahead loop (argument: anything), dense direct (dense), and a grouped solve of 2 (group2 / dense_group2)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "scs-python_amd"), os.path.join(ROOT, "tests")]
