@@ -154,6 +154,19 @@ scs_int scs_hip_solve_batch(ScsWork **w, ScsSolution **sol, ScsInfo **info, scs_
  * a workspace twice; scs_hip_last_error).  scs_hip_solve_batch forms its groups with the same code. */
 int scs_hip_batch_plan(ScsWork **w, scs_int count, scs_int *group_of);
 
+/* One matrix, many (b, c): a workspace in the state scs_init left `w` in — w's ORIGINAL b, c and settings (not what scs_update or a
+ * solve made of them since), cold start, empty Anderson history — that SHARES w's resident matrix data (every layout of A', A and P,
+ * the diagonal of P, the equilibration vectors) and allocates only per-solve state.  The shared set is read-only after scs_init and
+ * reference-counted: it is released by whichever of its users is finished last, so w may be finished before its clones.  A clone is a
+ * workspace like any other (scs_update, scs_solve, scs_finish, scs_hip_solution_to_device, scs_hip_solve_batch, scs_hip_clone);
+ * w and its clones may be solved from different threads at the same time (users of a set with column-sorted layouts take turns).
+ * Inside a scs_hip_solve_batch group, members that share a set read one copy of the matrix, with iterates bit-identical to
+ * separate solves (the labs build can launch their products per tile of four members: csrc/batch.hpp, SCS_HIP_SHARED_TILE=1).  The file names of
+ * write_data_filename / log_csv_filename are not inherited.  Returns NULL on error (scs_hip_last_error). */
+ScsWork *scs_hip_clone(ScsWork *w);
+/* 1 when a and b hold the same matrix set (a workspace and its clones, clones of clones), else 0. */
+int scs_hip_shares_matrix(const ScsWork *a, const ScsWork *b);
+
 /* bench.py: a timestamp inside the next scs_solve calls.  When ADMM iteration `iter` is about to start, the stream is
  * drained and out[4] = {ms since the start of the solve, CG steps so far, Anderson calls so far, accepted so far} is
  * recorded (out[0] < 0: the solve ended before that iteration); iter < 0 switches it off. */
@@ -204,6 +217,9 @@ void scs_hip_pool_stats(ScsHipPoolStats *out);
 /* How many solves of this process were restarted because a spinning multi-workgroup kernel (multi-CU PSD sweeps, persistent CG)
  * timed out at a barrier — another process held part of the GPU — and were then finished without such kernels (tests). */
 long scs_hip_spin_fallbacks(void);
+/* How many tiled CSR-stream launches (one read of a shared matrix per tile of members, csrc/batch.hpp) grouped solves of this
+ * process have issued (tests, tools/shared_batch_bench.py). */
+long scs_hip_tiled_launches(void);
 
 /* K9's refinement stage (csrc/psd.hpp psd_stop_test), diagnostics for tests and bench: for each of the first `cap` PSD matrices of
  * order > 32 of the workspace EIGHT doubles {calls that took the refinement stage so far, refinements whose a-posteriori test sent the

@@ -91,6 +91,139 @@ struct GTable {
 template <auto Fn, int Threads, class... A> GTable<Fn, Threads, A...> gtable_of(void (*)(A...));
 #define SCS_GTABLE(threads, ...) decltype(gtable_of<__VA_ARGS__, threads>(__VA_ARGS__))
 
+// ---- runs: members of a group that share one matrix set (scs_hip_clone) ---------------------------------------
+// Their CSR-stream products are launched per TILE of up to kSpmvTile members (blockIdx.y = tile): a workgroup reads its row block's
+// blk / rowptr / col / val ONCE into registers — at most kNnzPerWg / kSpmvThreads = 8 nonzeros per lane — and then, for every live member
+// of the tile, gathers THAT member's x, stages v[k] * x[c[k]] in that member's own LDS buffer, sums the rows in the order of
+// spmv_stream_block (the shared stream_rows) and calls that member's own epilogue with that member's own partial slots
+// (stream_partials).  Per member the floating-point sequence is the one of the one-member kernel => bit-identical iterates; what is
+// saved is (T - 1) / T of the matrix stream and of the row-block metadata.  kSpmvTile x 16 KiB of products + the reduction scratch:
+// two workgroups per CU of 160 KiB LDS, eight wavefronts — each with four members' gathers in flight.
+constexpr int kSpmvTile = 4;
+template <class Epi> using SpmvRec = Pack<CsrView, const double *, Epi, const int *, int *>;  // the record of a d_spmv_stream<Epi> table
+
+template <class Epi>
+__device__ __forceinline__ void d_spmv_stream_tiled(const SpmvRec<Epi> *__restrict__ tab, const int *__restrict__ tiles) {
+  constexpr int T = kSpmvTile;
+  const int tid = (int)threadIdx.x;
+  // the tile's members (uniform: scalar loads).  -1 = empty slot, and — as d_spmv_stream returns at once for it — a member whose
+  // done flag is up (its CG has converged)
+  int mem[T], first = -1;
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    int g = tiles[(size_t)blockIdx.y * T + t];
+    if (g >= 0) {
+      const int *done = tab[g].tail.tail.tail.head;
+      if (done && *done) g = -1;
+    }
+    mem[t] = g;
+    if (g >= 0 && first < 0) first = g;
+  }
+  if (first < 0) return;
+  const CsrView A = tab[first].head;  // the run's matrix: every member's record holds this view
+  if ((int)blockIdx.x >= A.nblk) return;
+  if (blockIdx.x == 0 && tid == 0) {
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+      if (mem[t] >= 0) {
+        int *step_counter = tab[mem[t]].tail.tail.tail.tail.head;
+        if (step_counter) *step_counter += 1;  // one CG step of that member begins
+      }
+  }
+  __shared__ double prod[T][kNnzPerWg];
+  __shared__ double red[kSpmvThreads / 64];
+  const int b = A.pbase + (int)blockIdx.x, nb = A.pstride > 0 ? A.pstride : (int)gridDim.x;
+  const int4 bi = A.blk[blockIdx.x];
+  const int r0 = bi.x, r1 = bi.y, p0 = bi.z, p1 = bi.w;
+  const int nnz = p1 - p0;
+  constexpr int NS = Epi::kSums > 0 ? Epi::kSums : 1, NM = Epi::kMaxs > 0 ? Epi::kMaxs : 1;
+  const BlockSync sync{};
+  if (nnz <= kNnzPerWg) {
+    constexpr int NK = kNnzPerWg / kSpmvThreads;
+    const double *__restrict__ v = A.val + p0;
+    const int *__restrict__ c = A.col + p0;
+    int ra[kRowsPerLane], re[kRowsPerLane];
+#pragma unroll
+    for (int j = 0; j < kRowsPerLane; ++j) {
+      const int r = r0 + tid + j * kSpmvThreads;
+      ra[j] = r < r1 ? A.rowptr[r] - p0 : 0;
+      re[j] = r < r1 ? A.rowptr[r + 1] - p0 : 0;
+    }
+    double vv[NK];
+    int cc[NK];
+#pragma unroll
+    for (int i = 0; i < NK; ++i) {
+      const int k = tid + i * kSpmvThreads;
+      vv[i] = k < nnz ? v[k] : 0.;
+      cc[i] = k < nnz ? c[k] : 0;
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      if (mem[t] < 0) continue;
+      const double *__restrict__ x = tab[mem[t]].tail.head;
+#pragma unroll
+      for (int i = 0; i < NK; ++i) {
+        const int k = tid + i * kSpmvThreads;
+        if (k < nnz) prod[t][k] = vv[i] * x[cc[i]];
+      }
+    }
+    sync();
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      if (mem[t] < 0) continue;
+      const Epi epi = tab[mem[t]].tail.tail.head;
+      double sums[NS], maxs[NM];
+#pragma unroll
+      for (int i = 0; i < NS; ++i) sums[i] = 0.;
+#pragma unroll
+      for (int i = 0; i < NM; ++i) maxs[i] = 0.;
+      stream_rows(epi, prod[t], ra, re, r0, r1, tid, sums, maxs);
+      stream_partials(epi, sums, maxs, b, nb, red, tid, sync);
+    }
+  } else {  // one long row: each nonzero is read once and feeds every live member's running sum (a member's own order: k = tid, tid + 256, ..)
+    const double *xs[T];
+    double acc[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      xs[t] = mem[t] >= 0 ? tab[mem[t]].tail.head : nullptr;
+      acc[t] = 0.;
+    }
+    for (int k = p0 + tid; k < p1; k += kSpmvThreads) {
+      const double a = A.val[k];
+      const int col = A.col[k];
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+        if (xs[t]) acc[t] += a * xs[t][col];
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      if (mem[t] < 0) continue;
+      const Epi epi = tab[mem[t]].tail.tail.head;
+      double sums[NS], maxs[NM];
+#pragma unroll
+      for (int i = 0; i < NS; ++i) sums[i] = 0.;
+#pragma unroll
+      for (int i = 0; i < NM; ++i) maxs[i] = 0.;
+      const double s = group_sum<kSpmvThreads>(acc[t], red, tid, sync);
+      if (tid == 0) epi(r0, s, sums, maxs);
+      stream_partials(epi, sums, maxs, b, nb, red, tid, sync);
+    }
+  }
+}
+template <class Epi>
+__global__ __launch_bounds__(kSpmvThreads) void k_spmv_stream_tiled(const SpmvRec<Epi> *tab, const int *tiles) {
+  d_spmv_stream_tiled<Epi>(tab, tiles);
+}
+// the tiled launch of a d_spmv_stream<Epi> table: gridDim.y = tiles (the table's records and blockIdx.x extent as they are)
+template <auto Fn, int Threads, class Epi>
+inline void launch_tiled(const GTable<Fn, Threads, CsrView, const double *, Epi, const int *, int *> &t, const int *tiles, int ntiles,
+                         hipStream_t s) {
+  static_assert(Threads == kSpmvThreads, "CSR-stream tables only");
+  if (!t.used || ntiles <= 0 || t.gx <= 0) return;
+  hipLaunchKernelGGL(k_spmv_stream_tiled<Epi>, dim3((unsigned)t.gx, (unsigned)ntiles), dim3(kSpmvThreads), 0, s,
+                     (const SpmvRec<Epi> *)t.dev.p, tiles);
+}
+
 // table bodies take their workgroup index from the launch
 __device__ __forceinline__ void d_soc_wave_blk(double *x, const int *__restrict__ off, const int *__restrict__ dim, int ncones, int G,
                                                const int *stall) {
@@ -140,6 +273,8 @@ __device__ __forceinline__ void d_gather_res(const double *__restrict__ out, con
   else if (t == 32) dst[32] = *utau;
   else if (t == 33) dst[33] = *rtau;
 }
+
+static std::atomic<long> g_tiled_launches{0};  // scs_hip_tiled_launches(): tests, the bench tool
 
 // ---- the group ---------------------------------------------------------------------------------------------
 struct GroupSolve {
@@ -241,6 +376,16 @@ struct GroupSolve {
   int *flags_h = nullptr, *lists_h = nullptr, *active_h = nullptr;  // (all pinned: every copy here is asynchronous)
   static constexpr int kListSlots = 64;
   int list_slot = 0, lists_since_sync = 0;
+  // runs (members on one matrix set): set_of[g] = index of member g's set among the group's sets.  Every member list that is uploaded
+  // gets, next to it, its tiles (kSpmvTile member indices each, -1 = empty) and the members that are alone on their set in that list.
+  std::vector<int> set_of;
+  std::vector<std::vector<int>> by_set;  // scratch of stage_tiles
+  bool has_runs = false;     // tiles are formed (some set has two members and the tiled kernel is on)
+  bool shared_sets = false;  // some matrix set has two members
+  struct Tiles { const int *tiles = nullptr; int ntiles = 0; const int *lone = nullptr; int nlone = 0; };
+  Tiles list_tiles[kListSlots], active_tiles;
+  DevBuf<int> tiles_d;     // (kListSlots + 1) x 3 G: [tiles: <= G / 2 of them | lone members], the last slot is the active list's
+  int *tiles_h = nullptr;  // (pinned stage, same discipline as lists_h)
   bool soc_psd_fused = false;     // short SOCs and small PSD matrices of a member in one launch
   const int *active_d = nullptr;  // device copy of `active`
   double t_finish = 0.;           // host time inside finish_solve (SCS_HIP_DEBUG=group)
@@ -255,12 +400,25 @@ struct GroupSolve {
   int syncs = 0, lockstep_iters = 0;
 
   ~GroupSolve() {
+    // a group with clones in it (SCS.solve_many in a sweep): once its stream is idle the group's own device blocks go to the block pool
+    // like a workspace's (common.hpp DevPool), so the next batch of the same size takes them from there instead of hipMalloc.  Groups
+    // of independent workspaces free theirs as ever.
+    if (shared_sets && s && hipStreamSynchronize(s) == hipSuccess) {
+      ++t_pool_release;
+      for_tables([](auto &t) { t.dev.release(); });
+      for (DevBuf<double> *b : {&params_d, &res_d, &aa_res_d}) b->release();
+      for (DevBuf<int> *b : {&flags_d, &lists_d, &active_buf, &tiles_d}) b->release();
+      dmat_d.release();
+      dsrc_d.release();
+      --t_pool_release;
+    }
     if (params_h) (void)hipHostFree(params_h);
     if (res_h) (void)hipHostFree(res_h);
     if (aa_res_h) (void)hipHostFree(aa_res_h);
     if (flags_h) (void)hipHostFree(flags_h);
     if (lists_h) (void)hipHostFree(lists_h);
     if (active_h) (void)hipHostFree(active_h);
+    if (tiles_h) (void)hipHostFree(tiles_h);
   }
 
   // Can these workspaces advance as one group?  Same dimensions and cone structure (every launch geometry follows
@@ -292,10 +450,47 @@ struct GroupSolve {
   int *fl_of(int g) const { return flags_d.p + (size_t)g * F_COUNT; }
 
   // ---- lists: a ring of device slots; a slot is not reused before the host has synchronised at least once
+  Tiles stage_tiles(const std::vector<int> &v, int slot) {
+    Tiles t;
+    if (!has_runs) return t;
+    int *stage = tiles_h + (size_t)slot * 3 * G, *dev = tiles_d.p + (size_t)slot * 3 * G;
+    int *lone = stage + 2 * (size_t)G;
+    for (int g : v) by_set[(size_t)set_of[(size_t)g]].push_back(g);
+    int nt = 0, nl = 0;
+    for (std::vector<int> &mb : by_set) {
+      const int cnt = (int)mb.size();
+      if (cnt == 1) lone[nl++] = mb[0];
+      else
+        for (int i = 0; i < cnt; i += kSpmvTile, ++nt)
+          for (int k = 0; k < kSpmvTile; ++k) stage[nt * kSpmvTile + k] = i + k < cnt ? mb[(size_t)(i + k)] : -1;
+      mb.clear();
+    }
+    if (nt == 0) return t;  // (no two members of this list share a set: the per-member launch over the list itself)
+    HIP_CHECK(hipMemcpyAsync(dev, stage, sizeof(int) * (size_t)nt * kSpmvTile, hipMemcpyHostToDevice, s));
+    if (nl) HIP_CHECK(hipMemcpyAsync(dev + 2 * (size_t)G, lone, sizeof(int) * (size_t)nl, hipMemcpyHostToDevice, s));
+    t.tiles = dev; t.ntiles = nt; t.lone = dev + 2 * (size_t)G; t.nlone = nl;
+    return t;
+  }
+  const Tiles *tiles_of(const int *list) const {
+    if (!has_runs || !list) return nullptr;
+    if (list == active_d) return &active_tiles;
+    return &list_tiles[(size_t)(list - lists_d.p) / (size_t)G];
+  }
+  // a CSR-stream product over a member list: runs go tile by tile (k_spmv_stream_tiled), everyone else member by member as ever
+  template <class T> void go_mv(const T &t, const int *list, int count) {
+    const Tiles *tl = tiles_of(list);
+    if (!tl || tl->ntiles == 0) { go(t, list, count); return; }
+    if (!t.used || count <= 0) return;
+    launch_tiled(t, tl->tiles, tl->ntiles, s);
+    ++launches;
+    g_tiled_launches.fetch_add(1, std::memory_order_relaxed);
+    go(t, tl->lone, tl->nlone);
+  }
   const int *upload_list(const std::vector<int> &v) {
     if (v.empty()) return nullptr;
     if (++lists_since_sync >= kListSlots) sync();  // (never in practice: every iteration synchronises)
     int *dst = lists_d.p + (size_t)list_slot * G, *stage = lists_h + (size_t)list_slot * G;
+    list_tiles[list_slot] = stage_tiles(v, list_slot);
     list_slot = (list_slot + 1) % kListSlots;
     std::copy(v.begin(), v.end(), stage);
     HIP_CHECK(hipMemcpyAsync(dst, stage, sizeof(int) * v.size(), hipMemcpyHostToDevice, s));
@@ -308,6 +503,7 @@ struct GroupSolve {
     if (!active.empty())
       HIP_CHECK(hipMemcpyAsync(active_buf.p, active_h, sizeof(int) * active.size(), hipMemcpyHostToDevice, s));
     active_d = active_buf.p;
+    active_tiles = stage_tiles(active, kListSlots);
   }
   void sync() {
     HIP_CHECK(hipGetLastError());  // (launches are not checked one by one)
@@ -362,6 +558,24 @@ struct GroupSolve {
     aa_res_d.alloc_zero((size_t)AA_R_COUNT * G, s);
     flags_d.alloc_zero((size_t)F_COUNT * G, s);
     lists_d.alloc_zero((size_t)kListSlots * G, s);
+    {  // runs: members that hold the same matrix set (scs_hip_clone); SCS_HIP_SHARED_TILE=0 (labs): per-member launches for them too
+      std::vector<const MatrixSet *> sets;
+      set_of.assign((size_t)G, 0);
+      for (int g = 0; g < G; ++g) {
+        const MatrixSet *ms = W[(size_t)g]->mats.get();
+        size_t k = 0;
+        while (k < sets.size() && sets[k] != ms) ++k;
+        if (k == sets.size()) sets.push_back(ms);
+        set_of[(size_t)g] = (int)k;
+      }
+      shared_sets = (int)sets.size() < G;
+      has_runs = shared_sets && opts().shared_tile;
+      if (has_runs) {
+        by_set.assign(sets.size(), {});
+        HIP_CHECK(hipHostMalloc((void **)&tiles_h, sizeof(int) * (size_t)(kListSlots + 1) * 3 * G));
+        tiles_d.alloc_zero((size_t)(kListSlots + 1) * 3 * G, s);
+      }
+    }
     cg_res_min.assign((size_t)G, 0.0);
     aa_mode.assign((size_t)G, 0);
     aa_len.assign((size_t)G, 0);
@@ -604,9 +818,9 @@ struct GroupSolve {
     }
   }
   void cg_step(const int *list, int count, int variant) {
-    go(t_spmv_a, list, count);
-    if (has_P) go(t_spmv_p, list, count);
-    go(t_spmv_at, list, count);
+    go_mv(t_spmv_a, list, count);
+    if (has_P) go_mv(t_spmv_p, list, count);
+    go_mv(t_spmv_at, list, count);
     go(t_cg_update[variant], list, count);
     go(t_cg_dir[variant], list, count);
   }
@@ -689,9 +903,9 @@ struct GroupSolve {
       for (int g : su) W[(size_t)g]->dense_factorisations++;
       go(t_g_rhs, ld, cnt);
       go(t_kkt_prep, ld, cnt);
-      go(t_spmv_rhs, ld, cnt);
+      go_mv(t_spmv_rhs, ld, cnt);
       go_dense_gemv(ld, cnt, true);
-      go(t_spmv_ax, ld, cnt);
+      go_mv(t_spmv_ax, ld, cnt);
       go(t_kkt_y, ld, cnt);
       go(t_copy_g, ld, cnt);
       go(t_gg, ld, cnt);
@@ -706,7 +920,7 @@ struct GroupSolve {
     // update_work_cache: g = (R + M)^{-1} [c; -b] by a cold PCG to 1e-12, then g'Rg
     go(t_g_rhs, ld, cnt);
     go(t_kkt_prep, ld, cnt);
-    go(t_spmv_rhs, ld, cnt);
+    go_mv(t_spmv_rhs, ld, cnt);
     go(t_zero_part, ld, cnt);
     go(t_fin_tol, ld, cnt);
     go(t_cg_init, ld, cnt);
@@ -718,7 +932,7 @@ struct GroupSolve {
       w->last_cg_iters = flags_of(g)[F_ITERS];
       w->tot_cg_iters += w->last_cg_iters;
     }
-    go(t_spmv_ax, ld, cnt);
+    go_mv(t_spmv_ax, ld, cnt);
     go(t_kkt_y, ld, cnt);
     go(t_copy_g, ld, cnt);
     go(t_gg, ld, cnt);
@@ -878,9 +1092,9 @@ struct GroupSolve {
       if (dense) {
         // three dependent launches, nothing to wait for: the host only synchronises where it has something to decide
         // (an Anderson step's outcome, a convergence check) — plain iterations are enqueued back to back
-        go(t_dense_rhs, active_d, na);
+        go_mv(t_dense_rhs, active_d, na);
         go_dense_gemv(active_d, na, false);
-        go(t_dense_y, active_d, na);
+        go_mv(t_dense_y, active_d, na);
         if (aa_now) {
           read_flags(active_d, na);
           sync();
@@ -889,9 +1103,9 @@ struct GroupSolve {
         }
         for (int g : active) W[(size_t)g]->last_cg_iters = 0;
       } else {
-      go(t_spmv_y, active_d, na);
-      if (has_P) go(t_spmv_pws, active_d, na);
-      go(t_spmv_r0, active_d, na);
+      go_mv(t_spmv_y, active_d, na);
+      if (has_P) go_mv(t_spmv_pws, active_d, na);
+      go_mv(t_spmv_r0, active_d, na);
       go(t_fin_head, active_d, na);
       const int pred_mode = opts().group_predict;  // (labs) 0: max + 1
       finish_cg(active, active_d, 0, [&](int g) { return pred_mode ? W[(size_t)g]->recent_cg_q3() : W[(size_t)g]->recent_cg_max() + 1; }, deferred_host_work);
@@ -920,10 +1134,10 @@ struct GroupSolve {
         const int *ld = C.size() == active.size() ? active_d : upload_list(C);
         const int cnt = (int)C.size();
         go(t_rsk, ld, cnt);
-        go(t_res_pri, ld, cnt);
+        go_mv(t_res_pri, ld, cnt);
         go(t_fin_multi_p, ld, cnt);
-        if (has_P) go(t_res_px, ld, cnt);
-        go(t_res_dual, ld, cnt);
+        if (has_P) go_mv(t_res_px, ld, cnt);
+        go_mv(t_res_dual, ld, cnt);
         go(t_fin_multi_d, ld, cnt);
         go(t_gather_res, ld, cnt);
         HIP_CHECK(hipMemcpyAsync(res_h, res_d.p, sizeof(double) * kResRec * G, hipMemcpyDeviceToHost, s));

@@ -49,6 +49,7 @@ static scs_int solve_impl(ScsHipWork *w, ScsSolution *sol, ScsInfo *info, scs_in
   std::lock_guard<std::mutex> lock(w->mtx);
   InterruptListener ctrlc;
   HIP_CHECK(hipSetDevice(w->device));
+  ScsHipWork::ScratchTurn turn(w);  // (layouts with scratch inside: one user of a shared matrix set at a time; work.hpp MatrixSet)
   const int n = w->n, m = w->m;
   const long l = w->l;
   hipStream_t s = w->stream;

@@ -52,6 +52,8 @@ struct Options {
   double psd_gate_k = 0., psd_gate_off = 0., psd_gate_omega = 0., psd_tol_k = 1e-2, psd_tol_max = 1e-3;
   bool psd_la = true, psd_mc_nocheck = false, psd_small_one_wave = false;
   bool pool_poison = false;
+  bool shared_tile = false;    // SCS_HIP_SHARED_TILE=1: members of a group on one matrix set read it once per tile of four (batch.hpp
+                               // k_spmv_stream_tiled) instead of per-member launches over the shared storage; not measured to win yet
 
   static bool is0(const char *e) { return e && e[0] == '0'; }
   static bool is1(const char *e) { return e && e[0] == '1'; }
@@ -122,6 +124,7 @@ struct Options {
     o.psd_mc_nocheck = getenv("SCS_HIP_PSD_MC_NOCHECK") != nullptr;
     o.psd_small_one_wave = is1(getenv("SCS_HIP_PSD_SMALL_WAVES"));
     o.pool_poison = is1(getenv("SCS_HIP_POOL_POISON"));
+    if (const char *e = getenv("SCS_HIP_SHARED_TILE")) o.shared_tile = e[0] != '0';
 #endif
     return o;
   }

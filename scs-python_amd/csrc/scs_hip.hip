@@ -103,6 +103,16 @@ ScsWork *scs_hip_init_linsys_spectral(const ScsData *d, const ScsCone *k, const 
     return nullptr;
   }
 }
+ScsWork *scs_hip_clone(ScsWork *w) {
+  try {
+    set_last_error("");
+    return clone_impl(w);
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return nullptr;
+  }
+}
+int scs_hip_shares_matrix(const ScsWork *a, const ScsWork *b) { return a && b && a->mats == b->mats ? 1 : 0; }
 int scs_hip_linsys_kind(const ScsWork *w) { return w ? (w->dense() ? 2 : 1) : 0; }
 
 scs_int scs_solve(ScsWork *w, ScsSolution *sol, ScsInfo *info, scs_int warm_start) {
@@ -293,6 +303,7 @@ scs_int scs_update(ScsWork *w, scs_float *b, scs_float *c) {
   try {
     std::lock_guard<std::mutex> lock(w->mtx);
     HIP_CHECK(hipSetDevice(w->device));
+    ScsHipWork::ScratchTurn turn(w);
     const int n = w->n, m = w->m;
     if (b) w->b_orig.assign(b, b + m);
     if (c) w->c_orig.assign(c, c + n);
@@ -398,6 +409,7 @@ int scs_hip_time_matvec(ScsWork *w, int reps, double *out) {
     std::lock_guard<std::mutex> lock(w->mtx);
     HIP_CHECK(hipSetDevice(w->device));
     hipStream_t s = w->stream;
+    ScsHipWork::ScratchTurn turn(w);
     w->finish_pending_setup();  // (R lives in the products)
     // the products exactly as the CG step of this workspace launches them
     for (int i = 0; i < 2; ++i) w->matvec(w->cg_p.p, nullptr);
@@ -476,6 +488,7 @@ void scs_hip_get_mark(const ScsWork *w, double *out) {
  * out[4] = {ms per projection, number of matrices, largest order, flops of a LAPACK-style eigensolve of them all
  * (16/3 n^3 + 2 n^3 per matrix)}.  Returns 0 on success, 1 when the problem has no PSD cone. */
 long scs_hip_spin_fallbacks(void) { return g_spin_fallbacks.load(); }
+long scs_hip_tiled_launches(void) { return g_tiled_launches.load(); }
 
 void scs_hip_trim_pool(void) { DevPool::inst().trim(); }
 void scs_hip_pool_stats(ScsHipPoolStats *out) { if (out) DevPool::inst().stats(out); }

@@ -142,6 +142,114 @@ static void upload_cone_meta(ScsHipWork *w) {
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// first chunk of a workspace arena: ~40 doubles per row / column of vectors + the Anderson history + 3 matrix layouts of 12 B per nonzero
+// (annz = 0: a clone, which holds no matrix), rounded up to a power of two
+static size_t arena_first_chunk(long l, long lookback, long annz) {
+  const long mem = std::max(0L, lookback);
+  const size_t est = (size_t)(8 * (40 + 3 * mem) * l + 3 * 12 * annz + (256 << 10));
+  size_t c = 256 << 10;
+  while (c < est && c < Arena::kChunkBytes) c <<= 1;
+  return c;
+}
+
+// the stream, events and pinned host block of a workspace (scs_init and scs_hip_clone)
+static void init_streams_and_pinned(ScsHipWork *w) {
+  w->pipelined = opts().pipeline;     // SCS_HIP_PIPELINE=0: the host looks at the CG flags in every iteration
+  w->pipe_chunk_override = opts().pipe_chunk;
+  w->stream = g_streams.acquire(w->device, &w->stream_shared);
+  w->pooled_stream = true;
+  for (auto &e : w->ev) HIP_CHECK(hipEventCreate(&e));
+  {  // one pinned, device-mapped block: [h_pin 256 f64 | AA h_pin 256 f64 | params 2 x P_COUNT f64 | flags 3 x F_COUNT i32]
+    char *blk = (char *)g_pinned.acquire();
+    w->pinned_block = blk;
+    std::memset(blk, 0, kPinnedBlockBytes);
+    w->h_pin = (double *)blk;
+    w->aa.h_pin = (double *)blk + 256;
+    w->aa.owns_pin = false;
+    w->h_params_base = (double *)blk + 512;
+    w->h_flags = (int *)((double *)blk + 512 + 2 * P_COUNT);
+    w->h_flags_slot[0] = w->h_flags + F_COUNT;
+    w->h_flags_slot[1] = w->h_flags + 2 * F_COUNT;
+    static_assert((512 + 2 * P_COUNT) * sizeof(double) + 3 * F_COUNT * sizeof(int) <= kPinnedBlockBytes, "pinned block too small");
+    HIP_CHECK(hipHostGetDevicePointer((void **)&w->d_params_base, w->h_params_base, 0));
+  }
+  w->h_params = w->h_params_base;
+  w->d_params = w->d_params_base;
+  for (int i = 0; i < 2; ++i) HIP_CHECK(hipEventCreateWithFlags(&w->ev_iter[i], hipEventDisableTiming));
+}
+
+// Everything of scs_init behind the matrix set: vectors, the scaled b / c, cone metadata, the Anderson workspace and (unless deferred)
+// R, the preconditioner or G^{-1}, and g.  scs_hip_clone runs exactly this on the shared set, from the b, c and settings scs_init got.
+template <class Mark>
+static void init_state(ScsHipWork *w, Mark &&mark) {
+  hipStream_t s = w->stream;
+  const int n = w->n, m = w->m;
+  // ---- vectors ----
+  const long l = w->l;
+  for (DevBuf<double> *b : {&w->v, &w->v_prev, &w->u, &w->ut, &w->rsk, &w->diag_r}) b->alloc_zero(l, s);
+  w->g.alloc_zero(l, s);
+  w->h.alloc_zero(l, s);
+  for (DevBuf<double> *b : {&w->cg_b, &w->cg_p, &w->cg_r, &w->cg_Gp, &w->cg_M, &w->ws}) b->alloc_zero(n, s);
+  w->cg_ticket.alloc_zero(1, s);
+  w->tmp_m.alloc_zero(m, s);
+  w->ensure_solution_mirror();
+  w->solx.alloc_zero(n, s);
+  w->soly.alloc_zero(m, s);
+  w->sols.alloc_zero(m, s);
+  // (x 8 until round 3: the residual epilogues leave 9 and 10 values per workgroup — with more than 1638 workgroups, i.e. the CSR-stream
+  // layout of a matrix beyond ~3.4 M nonzeros, their partials ran past the buffer: a memory fault at 9419 row blocks)
+  w->part_len = std::max({w->At.nblk, w->Ar.nblk, w->At.nwg(), w->Ar.nwg(), w->has_P ? std::max(w->Pf.nblk, w->Pf.nwg()) : 0, kMaxVecBlocks}) *
+                kMaxEpiReductions;
+  w->part.alloc_zero(w->part_len, s);
+  w->part2.alloc_zero(2 * kMaxVecBlocks, s);
+  w->part_v.alloc_zero(kMaxVecBlocks, s);
+  w->sc.alloc_zero(S_COUNT, s);
+  w->out.alloc_zero(256, s);
+  w->fl.alloc_zero(F_COUNT, s);
+  {
+    std::vector<double> hh(l, 0.0);
+    std::copy(w->c_orig.begin(), w->c_orig.end(), hh.begin());
+    std::copy(w->b_orig.begin(), w->b_orig.end(), hh.begin() + n);
+    w->h.upload(hh.data(), l, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  if (w->normalized) {
+    w->scal.sigma = device_normalize_b_c(w->h, n, m, w->D, w->E, w->part, w->h_pin, s);
+    std::vector<double> di(m), ei(n);
+    for (int i = 0; i < m; ++i) di[i] = 1.0 / (w->scal.D[i] * w->scal.sigma);
+    for (int i = 0; i < n; ++i) ei[i] = 1.0 / (w->scal.E[i] * w->scal.sigma);
+    w->Dinv.upload(di.data(), m, s);
+    w->Einv.upload(ei.data(), n, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  upload_cone_meta(w);
+  {
+    const double one = 1.0;
+    HIP_CHECK(hipMemcpyAsync(w->sc.p + S_BOX_T, &one, sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  // ---- AA workspace ----
+  w->aa.init(l, w->stgs.acceleration_lookback, w->stgs.acceleration_type_1, w->stgs.acceleration_regularization,
+             w->stgs.acceleration_relaxation, /*safeguard_factor=*/1.0, /*max_weight_norm=*/1e10, s);
+  mark("vectors, b/c scaling, cones, AA workspace");
+  // ---- R, preconditioner (or G^{-1}), pre-solved g ----
+  if (w->dense()) w->dense_alloc();
+  {
+    // Round 5, late: the indirect path defers it too (SCS_HIP_LAZY_SETUP=0: inside scs_init) — its cold PCG for g is ~50 steps = 150 dependent
+    // launches, three quarters of the dispatch chain of a small problem's scs_init; a batch runs it as ONE grouped cold solve (batch.hpp
+    // apply_scale_updates, the path of an adaptive-scale update: bit-identical to the solo one), a lone workspace at its first solve.
+    // (small problems only, n + m <= 32768: there the chain is what scs_init costs; a large problem keeps its cold solve out of scs_solve)
+    const bool small_indirect = !w->dense() && (long)n + m <= 32768;
+    w->setup_pending = (w->dense() || small_indirect) && w->mats->lazy_setup;
+  }
+  if (!w->setup_pending) {
+    w->set_diag_r();
+    w->update_work_cache();
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  mark("R, preconditioner, g = KKT^-1 h");
+}
+
 static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys = 0) {
   const double t0 = now_ms();
   refresh_options();  // the environment as it is NOW: this workspace keeps what it is created with (options.hpp)
@@ -187,29 +295,14 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
   w->c_orig.assign(d->c, d->c + n);
   for (double x : w->b_orig) w->nm_b_orig = std::max(w->nm_b_orig, std::fabs(x));
   for (double x : w->c_orig) w->nm_c_orig = std::max(w->nm_c_orig, std::fabs(x));
+  w->mats->b0 = w->b_orig;  // (host copies for scs_hip_clone: a clone starts from what scs_init was given)
+  w->mats->c0 = w->c_orig;
+  w->mats->bl0 = w->cone.bl;
+  w->mats->bu0 = w->cone.bu;
+  w->mats->stgs0 = w->stgs;
+  w->mats->lazy_setup = opts().lazy_setup;
 
-  w->pipelined = opts().pipeline;     // SCS_HIP_PIPELINE=0: the host looks at the CG flags in every iteration
-  w->pipe_chunk_override = opts().pipe_chunk;
-  w->stream = g_streams.acquire(w->device, &w->stream_shared);
-  w->pooled_stream = true;
-  for (auto &e : w->ev) HIP_CHECK(hipEventCreate(&e));
-  {  // one pinned, device-mapped block: [h_pin 256 f64 | AA h_pin 256 f64 | params 2 x P_COUNT f64 | flags 3 x F_COUNT i32]
-    char *blk = (char *)g_pinned.acquire();
-    w->pinned_block = blk;
-    std::memset(blk, 0, kPinnedBlockBytes);
-    w->h_pin = (double *)blk;
-    w->aa.h_pin = (double *)blk + 256;
-    w->aa.owns_pin = false;
-    w->h_params_base = (double *)blk + 512;
-    w->h_flags = (int *)((double *)blk + 512 + 2 * P_COUNT);
-    w->h_flags_slot[0] = w->h_flags + F_COUNT;
-    w->h_flags_slot[1] = w->h_flags + 2 * F_COUNT;
-    static_assert((512 + 2 * P_COUNT) * sizeof(double) + 3 * F_COUNT * sizeof(int) <= kPinnedBlockBytes, "pinned block too small");
-    HIP_CHECK(hipHostGetDevicePointer((void **)&w->d_params_base, w->h_params_base, 0));
-  }
-  w->h_params = w->h_params_base;
-  w->d_params = w->d_params_base;
-  for (int i = 0; i < 2; ++i) HIP_CHECK(hipEventCreateWithFlags(&w->ev_iter[i], hipEventDisableTiming));
+  init_streams_and_pinned(w.get());
   hipStream_t s = w->stream;
   // small problems (config 5: a batch of them) take their device memory from one arena (common.hpp) instead of ~100
   // separate allocations; SCS_HIP_ARENA=0 restores exact allocations (A/B)
@@ -217,14 +310,9 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
     const long annz = d->A->p[n];
     if (opts().arena && annz <= (1L << 18) && w->l <= (1L << 17)) {
       w->arena.reset(new Arena());
+      w->mats->home = w->arena;  // (the set's buffers live in it: it stays until the last user of the set is gone)
       w->arena->stream = s;
-      {  // ~40 doubles per row / column of vectors + 3 matrix layouts of 12 B per nonzero + the Anderson history, rounded up to a power of two
-        const long mem = std::max(0, stgs->acceleration_lookback);
-        size_t est = (size_t)(8 * (40 + 3 * mem) * w->l + 3 * 12 * annz + (256 << 10));
-        size_t c = 256 << 10;
-        while (c < est && c < Arena::kChunkBytes) c <<= 1;
-        w->arena->first_chunk = c;
-      }
+      w->arena->first_chunk = arena_first_chunk(w->l, stgs->acceleration_lookback, annz);
     }
   }
   ArenaScope arena_scope(w->arena.get());
@@ -314,71 +402,54 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
     hipLaunchKernelGGL(k_csr_diag, dim3(vec_blocks(n)), dim3(kVecThreads), 0, s, w->Pf.rowptr.p, w->Pf.col.p, w->Pf.val.p, n,
                        w->Pdiag.p);
   }
-  // ---- vectors ----
-  const long l = w->l;
-  for (DevBuf<double> *b : {&w->v, &w->v_prev, &w->u, &w->ut, &w->rsk, &w->diag_r}) b->alloc_zero(l, s);
-  w->g.alloc_zero(l, s);
-  w->h.alloc_zero(l, s);
-  for (DevBuf<double> *b : {&w->cg_b, &w->cg_p, &w->cg_r, &w->cg_Gp, &w->cg_M, &w->ws}) b->alloc_zero(n, s);
-  w->cg_ticket.alloc_zero(1, s);
-  w->tmp_m.alloc_zero(m, s);
-  w->ensure_solution_mirror();
-  w->solx.alloc_zero(n, s);
-  w->soly.alloc_zero(m, s);
-  w->sols.alloc_zero(m, s);
-  // (x 8 until round 3: the residual epilogues leave 9 and 10 values per workgroup — with more than 1638 workgroups, i.e. the CSR-stream
-  // layout of a matrix beyond ~3.4 M nonzeros, their partials ran past the buffer: a memory fault at 9419 row blocks)
-  w->part_len = std::max({w->At.nblk, w->Ar.nblk, w->At.nwg(), w->Ar.nwg(), w->has_P ? std::max(w->Pf.nblk, w->Pf.nwg()) : 0, kMaxVecBlocks}) *
-                kMaxEpiReductions;
-  w->part.alloc_zero(w->part_len, s);
-  w->part2.alloc_zero(2 * kMaxVecBlocks, s);
-  w->part_v.alloc_zero(kMaxVecBlocks, s);
-  w->sc.alloc_zero(S_COUNT, s);
-  w->out.alloc_zero(256, s);
-  w->fl.alloc_zero(F_COUNT, s);
-  {
-    std::vector<double> hh(l, 0.0);
-    std::copy(w->c_orig.begin(), w->c_orig.end(), hh.begin());
-    std::copy(w->b_orig.begin(), w->b_orig.end(), hh.begin() + n);
-    w->h.upload(hh.data(), l, s);
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
-  if (w->normalized) {
-    w->scal.sigma = device_normalize_b_c(w->h, n, m, w->D, w->E, w->part, w->h_pin, s);
-    std::vector<double> di(m), ei(n);
-    for (int i = 0; i < m; ++i) di[i] = 1.0 / (w->scal.D[i] * w->scal.sigma);
-    for (int i = 0; i < n; ++i) ei[i] = 1.0 / (w->scal.E[i] * w->scal.sigma);
-    w->Dinv.upload(di.data(), m, s);
-    w->Einv.upload(ei.data(), n, s);
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
-  upload_cone_meta(w.get());
-  {
-    const double one = 1.0;
-    HIP_CHECK(hipMemcpyAsync(w->sc.p + S_BOX_T, &one, sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
-  // ---- AA workspace ----
-  w->aa.init(l, stgs->acceleration_lookback, stgs->acceleration_type_1, stgs->acceleration_regularization,
-             stgs->acceleration_relaxation, /*safeguard_factor=*/1.0, /*max_weight_norm=*/1e10, s);
-  mark("vectors, b/c scaling, cones, AA workspace");
-  // ---- R, preconditioner (or G^{-1}), pre-solved g ----
-  if (w->dense()) w->dense_alloc();
-  {
-    // Round 5, late: the indirect path defers it too (SCS_HIP_LAZY_SETUP=0: inside scs_init) — its cold PCG for g is ~50 steps = 150 dependent
-    // launches, three quarters of the dispatch chain of a small problem's scs_init; a batch runs it as ONE grouped cold solve (batch.hpp
-    // apply_scale_updates, the path of an adaptive-scale update: bit-identical to the solo one), a lone workspace at its first solve.
-    // (small problems only, n + m <= 32768: there the chain is what scs_init costs; a large problem keeps its cold solve out of scs_solve)
-    const bool small_indirect = !w->dense() && (long)n + m <= 32768;
-    w->setup_pending = (w->dense() || small_indirect) && opts().lazy_setup;
-  }
-  if (!w->setup_pending) {
-    w->set_diag_r();
-    w->update_work_cache();
-  }
-  HIP_CHECK(hipStreamSynchronize(s));
-  mark("R, preconditioner, g = KKT^-1 h");
+  init_state(w.get(), mark);
   w->setup_time = now_ms() - t0;
   return w.release();
 }
 
+// scs_hip_clone: a workspace in the state scs_init left `src` in — its original b, c and settings, cold start — on src's matrix set.
+// The matrix part of scs_init is complete when scs_init returns (only R, the preconditioner / G^{-1} and g are ever deferred, and
+// those are per-solve state), so there is nothing to finish first.
+static ScsHipWork *clone_impl(ScsHipWork *src) {
+  const double t0 = now_ms();
+  if (!src) throw std::runtime_error("null argument");
+  std::lock_guard<std::mutex> lock(src->mtx);
+  HIP_CHECK(hipSetDevice(src->device));
+  std::unique_ptr<ScsHipWork> w(new ScsHipWork(src->mats));
+  const MatrixSet &ms = *w->mats;
+  w->device = src->device;
+  w->cone = src->cone;  // (box bounds already follow the row scaling; nothing changes them after scs_init)
+  w->n = src->n; w->m = src->m; w->l = src->l;
+  w->linsys = src->linsys;
+  w->stgs = ms.stgs0;   // (file names are not inherited: write_data_filename was served by scs_init, a log file has one writer)
+  w->scale = w->stgs.scale;
+  w->has_P = src->has_P;
+  w->normalized = src->normalized;
+  w->scal.D = src->scal.D;
+  w->scal.E = src->scal.E;
+  w->b_orig = ms.b0;
+  w->c_orig = ms.c0;
+  for (double x : w->b_orig) w->nm_b_orig = std::max(w->nm_b_orig, std::fabs(x));
+  for (double x : w->c_orig) w->nm_c_orig = std::max(w->nm_c_orig, std::fabs(x));
+  init_streams_and_pinned(w.get());
+  w->pipelined = src->pipelined;  // (what the parent was created with, not what the environment says now)
+  w->pipe_chunk_override = src->pipe_chunk_override;
+  hipStream_t s = w->stream;
+  const int n = w->n;
+  if (src->arena) {  // as the parent: its own arena, sized without the matrix layouts
+    w->arena.reset(new Arena());
+    w->arena->stream = s;
+    w->arena->first_chunk = arena_first_chunk(w->l, w->stgs.acceleration_lookback, 0);
+  }
+  ArenaScope arena_scope(w->arena.get());
+  ScsHipWork::ScratchTurn turn(w.get());
+  if (w->has_P) w->px.alloc_zero(n, s);
+  if (w->cone.bsize > 1) {  // the caller's box bounds (footer diagnostics)
+    w->box_bl_orig.upload(ms.bl0.data(), ms.bl0.size(), s);
+    w->box_bu_orig.upload(ms.bu0.data(), ms.bu0.size(), s);
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  init_state(w.get(), [](const char *) {});
+  w->setup_time = now_ms() - t0;
+  return w.release();
+}

@@ -239,6 +239,40 @@ struct EpiResDual {
   }
 };
 
+// Pieces of a row block that the one-member body below and the tiled body of a run of members on one matrix (batch.hpp
+// d_spmv_stream_tiled) share, so that a member's floating-point sequence is the same in both.
+// stream_rows: lane tid sums its (at most kRowsPerLane) rows out of the staged products, in CSR order, and hands each to the epilogue.
+template <class Epi>
+__device__ __forceinline__ void stream_rows(const Epi &epi, const double *prod, const int (&ra)[kRowsPerLane], const int (&re)[kRowsPerLane],
+                                            int r0, int r1, int tid, double *sums, double *maxs) {
+#pragma unroll
+  for (int j = 0; j < kRowsPerLane; ++j) {
+    const int r = r0 + tid + j * kSpmvThreads;
+    if (r < r1) {
+      double s = 0.;
+      for (int k = ra[j]; k < re[j]; ++k) s += prod[k];
+      epi(r, s, sums, maxs);
+    }
+  }
+}
+// stream_partials: the block's reduction partials of an epilogue, slot b of nb
+template <class Epi, class Sync>
+__device__ __forceinline__ void stream_partials(const Epi &epi, const double *sums, const double *maxs, int b, int nb, double *red, int tid,
+                                                Sync sync) {
+  if constexpr (Epi::kSums > 0 || Epi::kMaxs > 0) {
+#pragma unroll
+    for (int i = 0; i < Epi::kSums; ++i) {
+      const double t = group_sum<kSpmvThreads>(sums[i], red, tid, sync);
+      if (tid == 0) epi.partial[(size_t)i * nb + b] = t;
+    }
+#pragma unroll
+    for (int i = 0; i < Epi::kMaxs; ++i) {
+      const double t = group_max<kSpmvThreads>(maxs[i], red, tid, sync);
+      if (tid == 0) epi.partial[(size_t)(Epi::kSums + i) * nb + b] = t;
+    }
+  }
+}
+
 // One row block of the CSR-stream mat-vec, executed by kSpmvThreads consecutive lanes (tid = 0..255 inside the
 // group).  `nb` = number of row blocks of the whole product = stride of the epilogue's partial arrays.
 // Called by the one-launch-per-product kernel below.  sync() must synchronise the lanes that share `prod` / `red`.
@@ -278,15 +312,7 @@ __device__ __forceinline__ void spmv_stream_block(const CsrView &A, const double
 #pragma unroll 8
     for (int k = tid; k < nnz; k += kSpmvThreads) prod[k] = v[k] * x[c[k]];
     sync();
-#pragma unroll
-    for (int j = 0; j < kRowsPerLane; ++j) {
-      const int r = r0 + tid + j * kSpmvThreads;
-      if (r < r1) {
-        double s = 0.;
-        for (int k = ra[j]; k < re[j]; ++k) s += prod[k];
-        epi(r, s, sums, maxs);
-      }
-    }
+    stream_rows(epi, prod, ra, re, r0, r1, tid, sums, maxs);
     if (UNIFORM) { sync(); sync(); }
   } else {  // one long row: the whole group reduces it (fixed order)
     double s = 0.;
@@ -295,18 +321,7 @@ __device__ __forceinline__ void spmv_stream_block(const CsrView &A, const double
     s = group_sum<kSpmvThreads>(s, red, tid, sync);
     if (tid == 0) epi(r0, s, sums, maxs);
   }
-  if constexpr (Epi::kSums > 0 || Epi::kMaxs > 0) {
-#pragma unroll
-    for (int i = 0; i < Epi::kSums; ++i) {
-      const double t = group_sum<kSpmvThreads>(sums[i], red, tid, sync);
-      if (tid == 0) epi.partial[(size_t)i * nb + b] = t;
-    }
-#pragma unroll
-    for (int i = 0; i < Epi::kMaxs; ++i) {
-      const double t = group_max<kSpmvThreads>(maxs[i], red, tid, sync);
-      if (tid == 0) epi.partial[(size_t)(Epi::kSums + i) * nb + b] = t;
-    }
-  }
+  stream_partials(epi, sums, maxs, b, nb, red, tid, sync);
 }
 
 template <class Epi>

@@ -29,6 +29,25 @@ static SpinChain &spin_chain(int device) {
   return c[device & 63];
 }
 
+// ============================================================== shared matrix set
+// What a workspace holds that is a function of A, P, the cone boundaries and `normalize` alone: the resident layouts of A', A and P,
+// the diagonal of P and the equilibration vectors.  It is written by scs_init and read-only from then on, so scs_hip_clone hands the
+// SAME set to the workspace it makes: a clone allocates per-solve state only.  Reference-counted (std::shared_ptr); whichever user
+// dies last releases it, inside its own pool window (~ScsHipWork).
+struct MatrixSet {
+  std::shared_ptr<Arena> home;  // the arena of the workspace that built the set (FIRST member: destroyed last — the buffers below may live in it)
+  DeviceCsr At, Ar, Pf;
+  DevBuf<double> Pdiag, D, E;
+  // what scs_hip_clone rebuilds the state of scs_init from: the data and settings scs_init was called with (scs_update moves b_orig / c_orig)
+  std::vector<double> b0, c0, bl0, bu0;
+  ScsSettings stgs0{};
+  bool lazy_setup = true;  // SCS_HIP_LAZY_SETUP as scs_init read it: a clone defers what its parent deferred
+  // The column-sorted layouts keep scratch of a product inside the layout (partial row sums of split chunks, piece sums of virtual rows,
+  // combine tickets).  Workspaces that share such a set take turns: one solve / update at a time (small problems — CSR-stream — have none).
+  std::mutex scratch_mu;
+  bool has_scratch() const { return At.cs.ok || Ar.cs.ok || Pf.cs.ok; }
+};
+
 // ============================================================== workspace
 struct ScsHipWork {
   // first member = destroyed last: ends the window in which this workspace's device blocks go to the block pool (common.hpp DevPool)
@@ -36,7 +55,14 @@ struct ScsHipWork {
     bool armed = false;
     ~PoolWindowEnd() { if (armed) --t_pool_release; }
   } pool_window_end;
-  std::unique_ptr<Arena> arena;  // small problems: all device buffers of the workspace come from here (FIRST member: destroyed last)
+  std::shared_ptr<Arena> arena;  // small problems: all device buffers of the workspace come from here (FIRST member: destroyed last; the matrix set holds it too)
+  std::shared_ptr<MatrixSet> mats = std::make_shared<MatrixSet>();  // behind the arena: released before it, inside the pool window
+  ScsHipWork() = default;
+  explicit ScsHipWork(std::shared_ptr<MatrixSet> shared) : mats(std::move(shared)) {}  // scs_hip_clone
+  struct ScratchTurn {  // around everything that launches products of this workspace's matrices outside a grouped solve
+    std::unique_lock<std::mutex> lk;
+    explicit ScratchTurn(ScsHipWork *w) { if (w->mats->has_scratch()) lk = std::unique_lock<std::mutex>(w->mats->scratch_mu); }
+  };
   int device = 0;  // the HIP device this workspace (stream, buffers, events) lives on
   int n = 0, m = 0;
   long l = 0;
@@ -72,12 +98,14 @@ struct ScsHipWork {
   double prof_cone_ms = 0;
   long prof_cone_n = 0;
 
-  DeviceCsr At;  // CSR(A') == caller's CSC(A): rows n, cols m   (x-space outputs)
-  DeviceCsr Ar;  // CSR(A): rows m, cols n                        (y-space outputs)
-  DeviceCsr Pf;  // full symmetric CSR(P)
-  DevBuf<double> Pdiag;
+  // (the matrix set: shared with the clones of this workspace)
+  DeviceCsr &At = mats->At;  // CSR(A') == caller's CSC(A): rows n, cols m   (x-space outputs)
+  DeviceCsr &Ar = mats->Ar;  // CSR(A): rows m, cols n                        (y-space outputs)
+  DeviceCsr &Pf = mats->Pf;  // full symmetric CSR(P)
+  DevBuf<double> &Pdiag = mats->Pdiag;
+  DevBuf<double> &D = mats->D, &E = mats->E;
 
-  DevBuf<double> v, v_prev, u, ut, rsk, g, h, diag_r, D, E, Dinv, Einv;
+  DevBuf<double> v, v_prev, u, ut, rsk, g, h, diag_r, Dinv, Einv;  // (Dinv / Einv carry sigma, which follows b and c: per workspace)
   DevBuf<double> cg_b, cg_p, cg_r, cg_Gp, cg_M, tmp_m, ws, px;
   DevBuf<double> part, part2, sc, out;  // part2: partials of k_cg_update (read by k_cg_dir while `part` is reused), of k_prep
   DevBuf<double> part_v;                // sum-of-squares partials of v for the next k_prep

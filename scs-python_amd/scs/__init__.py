@@ -209,6 +209,25 @@ class SCS(object):
     self._solver.update(b, c)
 
 
+  def clone(self):
+    """A second solver over the SAME device matrix: the state this one had when it was constructed (its original b, c and
+    settings, cold start); only per-solve state is allocated.  Solve it on its own, from another thread, or in `solve_batch`."""
+    new = object.__new__(SCS)
+    new._settings = dict(self._settings)
+    new._solver = self._solver.clone()
+    return new
+
+  def shares_matrix(self, other):
+    """True when `other` reads the same device matrix data (a clone, the parent, a clone of a clone)."""
+    return isinstance(other, SCS) and self._solver.shares_matrix(other._solver)
+
+  def solve_many(self, b=None, c=None, warm_start=False, x=None, y=None, s=None):
+    """Solve K problems that differ in b (K, m) and / or c (K, n) only, as one batch over one device copy of the matrix.
+    Returns a list of K dicts like `solve()`; with warm_start=True a repeated call starts every member from its last solution
+    (or from the rows of x, y, s)."""
+    return self._solver.solve_many(b, c, warm_start, x, y, s)
+
+
 def solve(data, cone, **settings):
   """Legacy one-shot API; warm-start vectors may ride along in `data`."""
   solver = SCS(data, cone, **settings)

@@ -162,6 +162,10 @@ def _load():
                                         C.POINTER(C.POINTER(_ScsInfo)), c_int, c_int]
     lib.scs_hip_batch_plan.restype = c_int
     lib.scs_hip_batch_plan.argtypes = [C.POINTER(C.c_void_p), c_int, C.POINTER(c_int)]
+    lib.scs_hip_clone.restype = C.c_void_p
+    lib.scs_hip_clone.argtypes = [C.c_void_p]
+    lib.scs_hip_shares_matrix.restype = c_int
+    lib.scs_hip_shares_matrix.argtypes = [C.c_void_p, C.c_void_p]
     lib.scs_update.restype = c_int
     lib.scs_update.argtypes = [C.c_void_p, _PD, _PD]
     lib.scs_finish.restype = None
@@ -211,6 +215,8 @@ def _load():
     lib.scs_hip_trim_pool.argtypes = []
     lib.scs_hip_pool_stats.restype = None
     lib.scs_hip_pool_stats.argtypes = [C.POINTER(_ScsHipPoolStats)]
+    lib.scs_hip_tiled_launches.restype = C.c_long
+    lib.scs_hip_tiled_launches.argtypes = []
     lib.scs_hip_spin_fallbacks.restype = C.c_long
     lib.scs_hip_spin_fallbacks.argtypes = []
     lib.scs_hip_psd_refine_stats.restype = c_int
@@ -494,8 +500,7 @@ class SCS(object):
     def __init__(self, shape, Ax, Ai, Ap, Px, Pi, Pp, b, c, cone, **settings):
         if getattr(self, "_work", None):
             raise ValueError("Workspace already setup!")
-        self._work = None
-        self._lock = threading.Lock()
+        self._blank()
         # ---- shape "(ii)"
         if not isinstance(shape, tuple) or len(shape) != 2:
             raise TypeError("argument 1 must be 2-item sequence (m, n)")
@@ -505,7 +510,6 @@ class SCS(object):
         # ---- settings (keyword table R:scs/scsobject.h:467-495)
         st = _ScsSettings()
         _lib.scs_set_default_settings(C.byref(st))
-        self._fn_keep = []
         for key, val in settings.items():
             if key in _INT_SETTINGS:
                 setattr(st, key, _as_c_int(key, val))
@@ -523,7 +527,7 @@ class SCS(object):
             raise ValueError("m must be a positive integer")
         if n <= 0:
             raise ValueError("n must be a positive integer")
-        self.m, self.n = m, n
+        self._shape(m, n)
         # ---- data
         Axc = _float_array("Ax", Ax)
         Aic = _int_array("Ai", Ai)
@@ -592,9 +596,6 @@ class SCS(object):
         k = _ScsCone(z, lcone, _pd(bu), _pd(bl), (bu.size + 1) if bu.size > 0 else 0,
                      _pi(q), q.size, _pi(s), s.size, _pi(cs), cs.size, ep, ed, _pd(p), p.size)
         _set_spectral(k, spec)
-        self._x = np.zeros(n)
-        self._y = np.zeros(m)
-        self._s = np.zeros(m)
         if self._LINSYS:
             work = _lib.scs_hip_init_linsys_spectral(C.byref(d), C.byref(k), C.byref(st), self._LINSYS)
         else:
@@ -605,6 +606,17 @@ class SCS(object):
             self._init_error = last_error()
             raise ValueError("ScsWork allocation error!" + (" (%s)" % self._init_error if self._init_error else ""))
         self._work = work
+
+    # every attribute of an instance is set by these two: the constructor and clone() build their objects through them
+    def _blank(self):
+        self._work = None
+        self._lock = threading.Lock()
+        self._fn_keep = []
+        self._many = []  # solve_many's clones (members 1 .. K-1), kept for the next call
+
+    def _shape(self, m, n):
+        self.m, self.n = m, n
+        self._x, self._y, self._s = np.zeros(n), np.zeros(m), np.zeros(m)
 
     # ------------------------------------------------------------------ solve
     def _warm(self, name, dst, src):
@@ -656,6 +668,51 @@ class SCS(object):
                 raise ValueError("Workspace not initialized!")
             _lib.scs_update(self._work, _pd(bc) if bc is not None else None, _pd(cc) if cc is not None else None)
         return None
+
+    # ------------------------------------------------- one matrix, many (b, c)
+    def clone(self):
+        """A new solver in the state the constructor left this one in (its original b, c and settings, cold start) that SHARES this
+        one's matrix data on the device (include/scs_hip.h: scs_hip_clone) and allocates per-solve state only."""
+        with self._lock:
+            if not self._work:
+                raise ValueError("Workspace not initialized!")
+            work = _lib.scs_hip_clone(self._work)
+        if not work:
+            raise ValueError("ScsWork allocation error!" + (" (%s)" % last_error() if last_error() else ""))
+        new = object.__new__(type(self))
+        new._blank()
+        new._shape(self.m, self.n)
+        new._work = work
+        return new
+
+    def shares_matrix(self, other):
+        """True when `other` holds the same device matrix set (this solver's clone, its parent, a clone of a clone)."""
+        if not isinstance(other, SCS) or not self._work or not other._work:
+            return False
+        return bool(_lib.scs_hip_shares_matrix(self._work, other._work))
+
+    def solve_many(self, b=None, c=None, warm_start=False, x=None, y=None, s=None):
+        """K problems over this solver's matrix in one batch: b (K, m) and c (K, n) float64, either None = keep.  Member 0 is this
+        solver, members 1..K-1 are clones kept on it (made on demand, reused by the next call — with warm_start=True each member
+        starts from its own previous solution, or from row i of x / y / s).  Each member is `update`d, then ONE solve_batch runs over
+        all of them.  Returns the K result dicts `solve()` would return."""
+        K, rows = _many_args(self.m, self.n, b, c, warm_start, x, y, s)
+        if not self._work:
+            raise ValueError("Workspace not initialized!")
+        pool = self._many
+        while len(pool) < K - 1:
+            pool.append(self.clone())
+        members = [self] + pool[:K - 1]
+        for i, sv in enumerate(members):
+            bi, ci = rows["b"][i] if b is not None else None, rows["c"][i] if c is not None else None
+            if bi is not None or ci is not None:
+                sv.update(bi, ci)
+            if warm_start:
+                with sv._lock:
+                    for name, dst in (("x", sv._x), ("y", sv._y), ("s", sv._s)):
+                        if rows[name] is not None:
+                            sv._warm(name, dst, rows[name][i])
+        return solve_batch(members, bool(warm_start))
 
     # -------------------------------------------------- bench hooks (not part of the reference surface)
     def _set_profiling(self, on):
@@ -723,6 +780,41 @@ class SCS(object):
             with lock:
                 _lib.scs_finish(self._work)
                 self._work = None
+
+
+def _many_args(m, n, b, c, warm_start, x, y, s):
+    """Argument checks of SCS.solve_many, before anything touches the device: (K, {name: 2-D float64 array or None}).  The faults
+    `update` / `solve` know keep their messages."""
+    if not isinstance(warm_start, (bool, np.bool_)):
+        raise TypeError("argument 1 must be bool, not %s" % type(warm_start).__name__)
+    rows = {"b": None, "c": None, "x": None, "y": None, "s": None}
+    K = None
+    for name, arr, width in (("c", c, n), ("b", b, m)):
+        if arr is None:
+            continue
+        if not isinstance(arr, np.ndarray) or not np.issubdtype(arr.dtype, np.floating) or arr.ndim != 2:
+            raise TypeError("%s_new must be a 2-D numpy array of floats, one row per problem" % name)
+        if arr.shape[1] != width:
+            raise ValueError("%s_new has incompatible dimension with A" % name)
+        if K is not None and arr.shape[0] != K:
+            raise ValueError("b_new and c_new must have the same number of rows (one per problem)")
+        K = arr.shape[0]
+        rows[name] = np.array(arr, dtype=np.float64, order="C", copy=True)
+    for name, arr, width in (("x", x, n), ("y", y, m), ("s", s, m)):
+        if arr is None or not warm_start:
+            continue
+        if not isinstance(arr, np.ndarray) or not np.issubdtype(arr.dtype, np.floating) or arr.ndim != 2 or arr.shape[1] != width:
+            raise ValueError("Unable to parse %s warm-start" % name)
+        if K is not None and arr.shape[0] != K:
+            raise ValueError("Unable to parse %s warm-start" % name)
+        if K is None:
+            K = arr.shape[0]
+        rows[name] = np.ascontiguousarray(arr, dtype=np.float64)
+    if K is None:
+        K = 1
+    if K < 1:
+        raise ValueError("solve_many needs at least one problem")
+    return K, rows
 
 
 def solve_batch(solvers, warm_start=False):
@@ -886,6 +978,11 @@ def pool_stats():
     st = _ScsHipPoolStats()
     _lib.scs_hip_pool_stats(C.byref(st))
     return {name: int(getattr(st, name)) for name, _ in _ScsHipPoolStats._fields_}
+
+
+def tiled_launches():
+    """tiled CSR-stream launches (one read of a shared matrix per tile of members) issued by grouped solves of this process so far"""
+    return int(_lib.scs_hip_tiled_launches())
 
 
 def spin_fallbacks():
