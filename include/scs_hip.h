@@ -18,6 +18,9 @@
 extern "C" {
 #endif
 
+/* The library is compiled with hidden default visibility: what this header declares is all it exports. */
+#define SCS_HIP_API __attribute__((visibility("default")))
+
 typedef struct ScsHipWork ScsWork;
 
 /* ------------------------------------------------------------------ PART 1 */
@@ -26,118 +29,118 @@ typedef struct ScsHipWork ScsWork;
  * (the glue frees its views right after, :908).  Builds CSR(A) next to the
  * caller's CSC(A), equilibrates, uploads everything to HBM, pre-solves g.
  * Returns NULL on invalid data / allocation failure / no usable GPU. */
-ScsWork *scs_init(const ScsData *d, const ScsCone *k, const ScsSettings *stgs);
+SCS_HIP_API ScsWork *scs_init(const ScsData *d, const ScsCone *k, const ScsSettings *stgs);
 
 /* replaces scs_solve — called at R:scs/scsobject.h:986 with the GIL released.
  * Runs the whole ADMM loop device-resident; only info scalars and the final
  * x,y,s cross PCIe.  sol holds the warm start on entry when warm_start != 0. */
-scs_int scs_solve(ScsWork *w, ScsSolution *sol, ScsInfo *info, scs_int warm_start);
+SCS_HIP_API scs_int scs_solve(ScsWork *w, ScsSolution *sol, ScsInfo *info, scs_int warm_start);
 
 /* replaces scs_update — called at R:scs/scsobject.h:1217.  b and/or c may be NULL. */
-scs_int scs_update(ScsWork *w, scs_float *b, scs_float *c);
+SCS_HIP_API scs_int scs_update(ScsWork *w, scs_float *b, scs_float *c);
 
 /* replaces scs_finish — called at R:scs/scsobject.h:1240. */
-void scs_finish(ScsWork *w);
+SCS_HIP_API void scs_finish(ScsWork *w);
 
 /* replaces scs_set_default_settings — called at R:scs/scsobject.h:520. */
-void scs_set_default_settings(ScsSettings *stgs);
+SCS_HIP_API void scs_set_default_settings(ScsSettings *stgs);
 
 /* replaces scs_version — called at R:scs/scsmodule.h:5. */
-const char *scs_version(void);
+SCS_HIP_API const char *scs_version(void);
 
 /* sizeof(scs_int), sizeof(scs_float): what R:scs/scsmodule.h:16-23 report. */
-size_t scs_sizeof_int(void);
-size_t scs_sizeof_float(void);
+SCS_HIP_API size_t scs_sizeof_int(void);
+SCS_HIP_API size_t scs_sizeof_float(void);
 
 /* ------------------------------------------------------------------ PART 2 */
 
 /* number of visible HIP devices (0 => library unusable); does not initialise a context */
-int scs_hip_device_count(void);
+SCS_HIP_API int scs_hip_device_count(void);
 /* choose the device used by subsequent scs_init calls (and the kernel-level entry points below): the process-wide
  * default (0 at start), or — set_thread_device, dev < 0 clears it — a default of the calling thread only.  A workspace
  * remembers the device it was created on: scs_solve / scs_update / scs_finish select it themselves, so one process
  * may drive several GPUs. */
-int scs_hip_set_device(int dev);
-int scs_hip_set_thread_device(int dev);
+SCS_HIP_API int scs_hip_set_device(int dev);
+SCS_HIP_API int scs_hip_set_thread_device(int dev);
 /* 1 when this library is the -DSCS_HIP_LABS build (scs-python_amd/Makefile `make labs`: the experiments that lost their measurement and
  * the lab switches of the kernels compiled in and readable from the environment — csrc/options.hpp), 0 for the product. */
-int scs_hip_labs_build(void);
+SCS_HIP_API int scs_hip_labs_build(void);
 /* free and total HBM bytes of the device subsequent scs_init calls would use, plus the bytes this library's block pool holds for
  * reuse (they count as free for a new workspace).  What the Python layer's `LinearSolver.AUTO` asks before it picks the dense direct
  * solver (R:scs/py/__init__.py:45-54 resolves AUTO to the best DIRECT backend that is usable).  0 on success, -1 without a device. */
-int scs_hip_mem_info(size_t *free_bytes, size_t *total_bytes);
+SCS_HIP_API int scs_hip_mem_info(size_t *free_bytes, size_t *total_bytes);
 
 /* y (+)= A x or A' x through the hot-path SpMV kernels (row a3; plays the role
  * of scs_source/linsys/scs_matrix.c accum_by_a / accum_by_atrans, R:meson.build:199-202).
  * A is CSC with int32 indices; x,y are host pointers.  Returns 0 on success. */
-int scs_hip_spmv(const ScsMatrix *A, const scs_float *x, scs_float *y, int transpose);
+SCS_HIP_API int scs_hip_spmv(const ScsMatrix *A, const scs_float *x, scs_float *y, int transpose);
 
 /* HOST-ONLY check of the column-sorted pass layout the large-matrix SpMV kernels read (spmv_cs.hpp): builds the
  * layout of A (transpose=0) or A' (transpose=1) with the host builder (rows per lane `rpt` = 1, 2, 4, 8, 16, or 0 =
  * the geometry scs_init would pick; `split` = 1, or 2 workgroups per row chunk as scs_init uses for A') and
  * evaluates y += M x by walking it exactly as the kernel does (slot scatter, per-lane runs, pass order, partial sums).
  * No GPU needed.  Returns 0, 1 if the pattern does not fit the format, -1 on error. */
-int scs_hip_cs_layout_host_spmv(const ScsMatrix *A, const scs_float *x, scs_float *y, int transpose, int rpt, int split);
+SCS_HIP_API int scs_hip_cs_layout_host_spmv(const ScsMatrix *A, const scs_float *x, scs_float *y, int transpose, int rpt, int split);
 /* Same walk for the virtual-row variant of that layout (round 3): rows longer than max(piece_len, what a count field
  * holds) are cut into pieces of at most piece_len nonzeros that ride in the passes; the pieces of a row are then added
  * the way the device does it (64 lanes striding over them, shuffle tree).  Returns 1 when no row is that long. */
-int scs_hip_cs_layout_host_spmv_pieces(const ScsMatrix *A, const scs_float *x, scs_float *y, int transpose, int piece_len);
+SCS_HIP_API int scs_hip_cs_layout_host_spmv_pieces(const ScsMatrix *A, const scs_float *x, scs_float *y, int transpose, int piece_len);
 
 /* Time `reps` launches of the A (transpose=0) or A' (transpose=1) SpMV kernel
  * with HIP events on the launch stream; inputs already resident in HBM.
  * Returns average milliseconds per launch, <0 on error.  (bench.py roofline leg) */
-double scs_hip_spmv_bench(const ScsMatrix *A, int transpose, int reps);
+SCS_HIP_API double scs_hip_spmv_bench(const ScsMatrix *A, int transpose, int reps);
 
 /* In-place projection of x (length m, host pointer) onto K (dual=0) or K*
  * (dual=1) with the hot-path cone kernels (row a5; scs_source/src/cones.c,
  * exp_cone.c, R:meson.build:188,190). */
-int scs_hip_proj_cone(scs_float *x, const ScsCone *k, scs_int m, int dual);
+SCS_HIP_API int scs_hip_proj_cone(scs_float *x, const ScsCone *k, scs_int m, int dual);
 
 /* The same projection applied to `count` vectors one after the other (xs: count x m, row-major, in place) through ONE set of cone
  * workspaces, warm-started from call to call as inside the ADMM loop (K9: eigenvectors of the previous call, periodic
  * re-orthogonalisation, refinement stage; box cone: the previous t).  stats (may be NULL): scs_hip_psd_refine_stats records of the
  * first stats_cap large PSD matrices after the last call.  Returns the number of records written, -1 on error.  (parity tests) */
-int scs_hip_proj_cone_seq(scs_float *xs, const ScsCone *k, scs_int m, int dual, int count, scs_float *stats, int stats_cap);
+SCS_HIP_API int scs_hip_proj_cone_seq(scs_float *xs, const ScsCone *k, scs_int m, int dual, int count, scs_float *stats, int stats_cap);
 
 /* One indirect KKT solve [[R_x+P, A'],[A,-R_y]] z = rhs (in place, length n+m)
  * with the device PCG (row a4; scs_source/linsys/cpu/indirect/private.c,
  * R:meson.build:261).  cg_iters may be NULL. */
-int scs_hip_kkt_solve(const ScsMatrix *A, const ScsMatrix *P, const scs_float *diag_r, scs_float *rhs,
+SCS_HIP_API int scs_hip_kkt_solve(const ScsMatrix *A, const ScsMatrix *P, const scs_float *diag_r, scs_float *rhs,
                       scs_float tol, scs_int *cg_iters);
 
 /* Same system solved with the DENSE DIRECT linsys (csrc/dense.hpp): G = R_x + P + A' R_y^{-1} A is formed and inverted on
  * the device (blocked Gauss-Jordan on the fp64 MFMA), x = G^{-1}(rhs_x + A' R_y^{-1} rhs_y), y = R_y^{-1}(A x - rhs_y).  n <= 8192.
  * Plays the role of the reference's direct backends (QDLDL / cuDSS / the LAPACK dense module: R:meson.build:241-262,374-391). */
-int scs_hip_kkt_solve_dense(const ScsMatrix *A, const ScsMatrix *P, const scs_float *diag_r, scs_float *rhs);
+SCS_HIP_API int scs_hip_kkt_solve_dense(const ScsMatrix *A, const ScsMatrix *P, const scs_float *diag_r, scs_float *rhs);
 
 /* scs_init with an explicit choice of the linear-system solver: 1 = sparse indirect (PCG; what scs_init builds unless the
  * environment says SCS_HIP_LINSYS=dense), 2 = dense direct (n <= 8192: the explicit inverse of the reduced KKT matrix lives in
  * HBM, the linear solve of an ADMM iteration is three dependent launches and never waits for the host), 0 = the default.
  * The reference selects its linear solver by MODULE (R:scs/py/__init__.py:40-66: _scs_direct, _scs_indirect, _scs_gpu, ...);
  * scs._scs_hip binds 1, scs._scs_hip_dense binds 2.  Everything else is scs_init's contract. */
-ScsWork *scs_hip_init_linsys(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys);
+SCS_HIP_API ScsWork *scs_hip_init_linsys(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys);
 /* 1 / 2 as above for a live workspace (0: NULL) */
-int scs_hip_linsys_kind(const ScsWork *w);
+SCS_HIP_API int scs_hip_linsys_kind(const ScsWork *w);
 
 /* Equilibrate (A,P,b,c) exactly as scs_init does (row a7; scs_source/src/normalize.c,
  * R:meson.build:192).  A->x, P->x, b, c are overwritten; D (m), E (n), sigma (1) filled. */
-int scs_hip_normalize(ScsMatrix *A, ScsMatrix *P, scs_float *b, scs_float *c, const ScsCone *k,
+SCS_HIP_API int scs_hip_normalize(ScsMatrix *A, ScsMatrix *P, scs_float *b, scs_float *c, const ScsCone *k,
                       scs_float *D, scs_float *E, scs_float *sigma);
 
 /* Measured device-copy bandwidth ceiling in GB/s (float4 copy of `bytes` bytes). */
-double scs_hip_copy_bandwidth(size_t bytes, int reps);
+SCS_HIP_API double scs_hip_copy_bandwidth(size_t bytes, int reps);
 
 /* Live timing of the two dominant kernels inside scs_solve: when enabled, one CG step per
  * host sync is bracketed by HIP events on the solver's own stream.  out[12] =
  * {K1 total ms, K1 samples, K2 total ms, K2 samples, nnz(A), K1 workgroups, K2 workgroups, nnz(P full),
  *  nonlinear cone projections total ms, samples (one per queued iteration), K3 total ms, K3 samples}
  * where K1 = z <- R_y^{-1} A p,  K2 = Gp <- A' z + R_x p (+ P p)  and, for problems with P, K3 = P p (between K1 and K2). */
-void scs_hip_set_profiling(ScsWork *w, int on);
-void scs_hip_kernel_times(const ScsWork *w, double *out);
+SCS_HIP_API void scs_hip_set_profiling(ScsWork *w, int on);
+SCS_HIP_API void scs_hip_kernel_times(const ScsWork *w, double *out);
 /* The final (x, y, s) of the last scs_solve, copied from the workspace's HBM buffers to caller-provided DEVICE pointers
  * (any may be NULL; n, m, m doubles) on the workspace's stream, complete on return.  Same values, bit for bit, as the
  * host copies scs_solve returned (NaN where the status leaves a vector undefined).  scs/batch.py gathers from these. */
-int scs_hip_solution_to_device(ScsWork *w, scs_float *x_dev, scs_float *y_dev, scs_float *s_dev);
+SCS_HIP_API int scs_hip_solution_to_device(ScsWork *w, scs_float *x_dev, scs_float *y_dev, scs_float *s_dev);
 
 /* Grouped solve of `count` independent, already initialised workspaces (BASELINE.json configs[4]: a batch of small cone
  * programs; the reference's notion is "independent instances run concurrently", R:test/test_thread_safety.py:78-93 —
@@ -148,11 +151,11 @@ int scs_hip_solution_to_device(ScsWork *w, scs_float *x_dev, scs_float *y_dev, s
  * them — the grouped kernels run the same device code over the same block decomposition, so iterates, iteration and
  * CG-step counts are bit-identical to separate solves (timing fields are those of the group).  Returns 0, -1 on error
  * (scs_hip_last_error).  The workspaces must live on one device and must not be used by other threads meanwhile. */
-scs_int scs_hip_solve_batch(ScsWork **w, ScsSolution **sol, ScsInfo **info, scs_int count, scs_int warm_start);
+SCS_HIP_API scs_int scs_hip_solve_batch(ScsWork **w, ScsSolution **sol, ScsInfo **info, scs_int count, scs_int warm_start);
 /* The grouping scs_hip_solve_batch(w, .., count, ..) would use, without solving: group_of[i] = the index of the group member i
  * would join, -1 for a member it would solve alone by scs_solve.  Returns the number of groups, -1 on error (null arguments,
  * a workspace twice; scs_hip_last_error).  scs_hip_solve_batch forms its groups with the same code. */
-int scs_hip_batch_plan(ScsWork **w, scs_int count, scs_int *group_of);
+SCS_HIP_API int scs_hip_batch_plan(ScsWork **w, scs_int count, scs_int *group_of);
 
 /* One matrix, many (b, c): a workspace in the state scs_init left `w` in — w's ORIGINAL b, c and settings (not what scs_update or a
  * solve made of them since), cold start, empty Anderson history — that SHARES w's resident matrix data (every layout of A', A and P,
@@ -163,20 +166,20 @@ int scs_hip_batch_plan(ScsWork **w, scs_int count, scs_int *group_of);
  * Inside a scs_hip_solve_batch group, members that share a set read one copy of the matrix, with iterates bit-identical to
  * separate solves (the labs build can launch their products per tile of four members: csrc/batch.hpp, SCS_HIP_SHARED_TILE=1).  The file names of
  * write_data_filename / log_csv_filename are not inherited.  Returns NULL on error (scs_hip_last_error). */
-ScsWork *scs_hip_clone(ScsWork *w);
+SCS_HIP_API ScsWork *scs_hip_clone(ScsWork *w);
 /* 1 when a and b hold the same matrix set (a workspace and its clones, clones of clones), else 0. */
-int scs_hip_shares_matrix(const ScsWork *a, const ScsWork *b);
+SCS_HIP_API int scs_hip_shares_matrix(const ScsWork *a, const ScsWork *b);
 
 /* bench.py: a timestamp inside the next scs_solve calls.  When ADMM iteration `iter` is about to start, the stream is
  * drained and out[4] = {ms since the start of the solve, CG steps so far, Anderson calls so far, accepted so far} is
  * recorded (out[0] < 0: the solve ended before that iteration); iter < 0 switches it off. */
-void scs_hip_set_mark(ScsWork *w, int iter);
-void scs_hip_get_mark(const ScsWork *w, double *out);
+SCS_HIP_API void scs_hip_set_mark(ScsWork *w, int iter);
+SCS_HIP_API void scs_hip_get_mark(const ScsWork *w, double *out);
 /* `reps` back-to-back launches of K1, then of K2 and — problems with P — of K3 on the solver's own stream and HBM-resident
  * data, one HIP event pair per batch (the ~10-20 us per-event overhead is amortised).
  * out[4] = {K1 avg ms, K2 avg ms, K3 avg ms as the CG step runs it — between K1 and K2: (K1, K3, K2) x reps minus (K1, K2) x reps —, K3 avg ms
  * back to back (its matrix may then stay in the Infinity Cache)}; K3: 0 without P.  Returns 0 on success. */
-int scs_hip_time_matvec(ScsWork *w, int reps, double *out);
+SCS_HIP_API int scs_hip_time_matvec(ScsWork *w, int reps, double *out);
 
 /* Anderson acceleration as a standalone object on host vectors (row a6): the interface of scs_source/src/aa.c
  * (aa_init / aa_apply / aa_safeguard / aa_reset / aa_finish; named at R:meson.build:187, knobs R:README.md:98-104,
@@ -187,23 +190,23 @@ int scs_hip_time_matvec(ScsWork *w, int reps, double *out);
  *              pre-extrapolation pair when the fixed-point residual grew, else 0.
  *   last_gamma: weights of the most recent solve (returns their count; gamma may be NULL). */
 typedef struct ScsHipAa ScsHipAa;
-ScsHipAa *scs_hip_aa_init(scs_int dim, scs_int mem, scs_int type1, scs_float regularization, scs_float relaxation,
+SCS_HIP_API ScsHipAa *scs_hip_aa_init(scs_int dim, scs_int mem, scs_int type1, scs_float regularization, scs_float relaxation,
                           scs_float safeguard_factor, scs_float max_weight_norm);
-scs_float scs_hip_aa_apply(ScsHipAa *a, scs_float *f, const scs_float *x);
-scs_int scs_hip_aa_safeguard(ScsHipAa *a, scs_float *f_new, scs_float *x_new);
-void scs_hip_aa_reset(ScsHipAa *a);
-void scs_hip_aa_get_stats(const ScsHipAa *a, ScsAaStats *st);
-scs_int scs_hip_aa_last_gamma(const ScsHipAa *a, scs_float *gamma);
-void scs_hip_aa_finish(ScsHipAa *a);
+SCS_HIP_API scs_float scs_hip_aa_apply(ScsHipAa *a, scs_float *f, const scs_float *x);
+SCS_HIP_API scs_int scs_hip_aa_safeguard(ScsHipAa *a, scs_float *f_new, scs_float *x_new);
+SCS_HIP_API void scs_hip_aa_reset(ScsHipAa *a);
+SCS_HIP_API void scs_hip_aa_get_stats(const ScsHipAa *a, ScsAaStats *st);
+SCS_HIP_API scs_int scs_hip_aa_last_gamma(const ScsHipAa *a, scs_float *gamma);
+SCS_HIP_API void scs_hip_aa_finish(ScsHipAa *a);
 
 /* bench.py --workload config4_psd: average duration of one batched PSD projection (all `s` cones, warm-started as inside
  * the ADMM loop) on the solver's stream; out[4] = {ms per projection, matrices, largest order, reference flop count
  * ((16/3 + 2) n^3 per matrix)}.  0 on success, 1 when the problem has no PSD cone. */
-int scs_hip_time_psd(ScsWork *w, int reps, double *out);
+SCS_HIP_API int scs_hip_time_psd(ScsWork *w, int reps, double *out);
 
 /* Hands the device blocks this library caches for reuse (dead workspaces' buffers, at most SCS_HIP_POOL_MB = 1024 MiB by default) back
  * to the driver: for a process that shares its GPUs with allocators this library does not see (torch, RCCL, other processes). */
-void scs_hip_trim_pool(void);
+SCS_HIP_API void scs_hip_trim_pool(void);
 
 /* The block pool's account, read under the pool's lock (host counters only: no device work).  held_* = what the pool caches now;
  * live_bytes = device bytes this library obtained from hipMalloc and has not handed back with hipFree yet (held blocks included: with no
@@ -212,24 +215,24 @@ void scs_hip_trim_pool(void);
 typedef struct {
   size_t held_bytes, held_blocks, live_bytes, hits, misses;
 } ScsHipPoolStats;
-void scs_hip_pool_stats(ScsHipPoolStats *out);
+SCS_HIP_API void scs_hip_pool_stats(ScsHipPoolStats *out);
 
 /* How many solves of this process were restarted because a spinning multi-workgroup kernel (multi-CU PSD sweeps, persistent CG)
  * timed out at a barrier — another process held part of the GPU — and were then finished without such kernels (tests). */
-long scs_hip_spin_fallbacks(void);
+SCS_HIP_API long scs_hip_spin_fallbacks(void);
 /* How many tiled CSR-stream launches (one read of a shared matrix per tile of members, csrc/batch.hpp) grouped solves of this
  * process have issued (tests, tools/shared_batch_bench.py). */
-long scs_hip_tiled_launches(void);
+SCS_HIP_API long scs_hip_tiled_launches(void);
 
 /* K9's refinement stage (csrc/psd.hpp psd_stop_test), diagnostics for tests and bench: for each of the first `cap` PSD matrices of
  * order > 32 of the workspace EIGHT doubles {calls that took the refinement stage so far, refinements whose a-posteriori test sent the
  * matrix back to the sweeps, |K1|_F^2 at the last gate, mixed-sign off-norm^2 / |A|_F^2 after the last refinement, stage flag of the
  * last call (0 none, 1 refined, 2 refined + sweeps), and the gate's view of the last call's matrix as it arrived: |K1|_F^2,
  * |off|_F^2 / |A|_F^2, omega}.  Returns the number of matrices written, -1 on error. */
-int scs_hip_psd_refine_stats(ScsWork *w, double *out, int cap);
+SCS_HIP_API int scs_hip_psd_refine_stats(ScsWork *w, double *out, int cap);
 
 /* last error message of the calling thread ("" if none) */
-const char *scs_hip_last_error(void);
+SCS_HIP_API const char *scs_hip_last_error(void);
 
 /* ------------------------------------------------------- spectral cones
  * The same entry points for a cone that carries the spectral fields of ScsCone (scs_types.h, USE_SPECTRAL_CONES): they
@@ -237,9 +240,9 @@ const char *scs_hip_last_error(void);
  * reaches them through the plain names (the remapping below); one compiled without the flag keeps the short struct and
  * the plain entries.  INTEGRATION.md §B. */
 #if defined(USE_SPECTRAL_CONES)
-ScsWork *scs_init_spectral(const ScsData *d, const ScsCone *k, const ScsSettings *stgs);
-ScsWork *scs_hip_init_linsys_spectral(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys);
-int scs_hip_proj_cone_spectral(scs_float *x, const ScsCone *k, scs_int m, int dual);
+SCS_HIP_API ScsWork *scs_init_spectral(const ScsData *d, const ScsCone *k, const ScsSettings *stgs);
+SCS_HIP_API ScsWork *scs_hip_init_linsys_spectral(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys);
+SCS_HIP_API int scs_hip_proj_cone_spectral(scs_float *x, const ScsCone *k, scs_int m, int dual);
 #if !defined(SCS_HIP_BUILDING_LIBRARY)
 #define scs_init scs_init_spectral
 #define scs_hip_init_linsys scs_hip_init_linsys_spectral

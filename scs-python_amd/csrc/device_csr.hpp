@@ -120,14 +120,12 @@ struct DeviceCsr {
   // nonzeros per 128-byte line of the gather vector, i.e. fewer lines per gather instruction — the quantity that bounds
   // these kernels — at the price of partial row sums.  Default: only A' is split, in two, and hands its two partial
   // vectors to the CG update (EpiGp::split: Gp is linear in them) or to k_epi_finish — no combine pass.
-  // SCS_HIP_CS_COMBINE=1 (braided kernel only): the partial sums of up to 4 parts are added INSIDE the kernel by the
+  // SCS_HIP_CS_COMBINE=1: the partial sums of up to 4 parts are added INSIDE the kernel by the
   // last workgroup of a chunk to arrive, so every product — A too — may be split (SCS_HIP_CS_SPLIT_A / _AT / _P).
   // Measured at the bench size (tools/cs_lab.hip): the 48 MB of partial-sum traffic and the 16-rows-per-lane row sums
   // eat the gather gain (A: 91.5 us unsplit, 95 us split in two + combine; A': 93 us two partial vectors, 100 us four
   // parts + combine) => off by default.
-  static bool cs_combine_enabled() {  // (labs)
-    return opts().cs_combine && cs_schedule() >= 2;  // (round 5: the round-4 schedule too — k_spmv_cs_il<.., 6> carries the same combine code)
-  }
+  static bool cs_combine_enabled() { return opts().cs_combine; }  // (labs)
   int cs_pick_split(int kind) const {
     if (!cs_split_enabled() || opts().cs_rpt > 0) return 1;
     if (!cs_combine_enabled()) {

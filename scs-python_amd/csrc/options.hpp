@@ -4,9 +4,10 @@
 // SCS_HIP_RUNTIME_ENV).  They are parsed HERE, once per scs_init / kernel-level entry point (refresh_options(): a test may change the
 // environment between two workspaces of one process; a workspace keeps what it was created with), never at the point of use.
 // Everything else that rounds 1-5 could switch at run time — the experiments that lost and still have code (cooperative launches, the
-// in-kernel combine of split layouts, the gather-ahead schedule ...) and the lab switches of the kernels — is a compile-time default in
+// in-kernel combine of split layouts ...) and the lab switches of the kernels — is a compile-time default in
 // the product and only reads the environment in the `-DSCS_HIP_LABS` build (scs-python_amd/Makefile `make labs` -> libscs_hip_labs.so,
-// used by tools/ and by the tests marked `labs`).  Four closed experiments of the CG path have no code any more: DESIGN.md §4.
+// used by tools/ and by the tests marked `labs`).  Four closed experiments of the CG path and the older
+// schedules of the column-sorted SpMV have no code any more: DESIGN.md §4 and its column-sorted SpMV section.
 #pragma once
 #include <atomic>
 #include <cstdlib>
@@ -42,7 +43,6 @@ struct Options {
 
   // ------------------------------------------------------------------ labs (compile-time defaults in the product)
   bool psd_coop = false;       // hipLaunchCooperativeKernel for the multi-CU sweeps: ~2 ms per launch in a warm process
-  int cs_sched = 3;            // 1 gather-ahead kernel, 2 braid, 3 braid + stream loads before the barrier (shipped)
   bool cs_combine = false;     // in-kernel combine of split layouts: eats the gather gain
   int cs_rpt = 0, cs_split_a = 0, cs_split_at = 0, cs_split_p = 0;
   bool cs_peel = true, cs_peel_ladder = true, cs_virt = true;
@@ -91,7 +91,6 @@ struct Options {
     auto pos_int = [](const char *name, int dflt) { const char *e = getenv(name); const int v = e ? atoi(e) : 0; return v > 0 ? v : dflt; };
     auto pos_dbl = [](const char *name, double dflt) { const char *e = getenv(name); const double v = e ? atof(e) : 0.; return v > 0. ? v : dflt; };
     o.psd_coop = is1(getenv("SCS_HIP_PSD_COOP"));
-    if (const char *e = getenv("SCS_HIP_CS_SCHED")) o.cs_sched = atoi(e);
     o.cs_combine = is1(getenv("SCS_HIP_CS_COMBINE"));
     o.cs_rpt = pos_int("SCS_HIP_CS_RPT", 0);
     o.cs_split_a = pos_int("SCS_HIP_CS_SPLIT_A", 0);

@@ -45,7 +45,7 @@ struct CsView {
   const unsigned long long *meta;  // npass * kCsThreads * cs_meta_words(rpt)
   int rows, cols, nchunks, R, npass, rpt;  // R rows per chunk (<= 1024 * rpt), rpt = accumulators per lane (1, 2, 4, 8, 16)
   int split;                   // workgroups per chunk (1, 2, 4: the chunk's column-sorted stream cut into equal parts; partial row sums)
-  // In-kernel combine (k_spmv_cs_il only; nullptr = the workgroups hand their partial row sums to the epilogue's split()):
+  // In-kernel combine (nullptr = the workgroups hand their partial row sums to the epilogue's split()):
   // every workgroup of a chunk publishes its partial sums in `scratch` and takes a ticket; the LAST arriver adds the
   // parts in fixed order and runs the epilogue on the finished rows.  No spinning: nothing ever waits for a workgroup.
   double *scratch = nullptr;   // nchunks * split * 1024 * rpt doubles
@@ -325,247 +325,15 @@ __device__ __forceinline__ int cs_epilogue_row(const CsView &A, int c, int rl) {
   return (r < A.rows && !cs_is_peeled(A.peel, r)) ? r : -1;
 }
 
-// Row sums of one pass from the LDS product buffer: m = {first slot of the lane's run | the lane's RPT counts}.
-// (Measured alternative: level by level — the L-th product of several rows as one batch of independent LDS reads,
-// +0.0 for rows without one — is not faster than the plain per-row loops: 100-102 vs 99 us on the K1 shape.)
-template <int RPT>
-__device__ __forceinline__ void cs_row_sums(const double *__restrict__ pb, unsigned long long m, unsigned long long m1, double (&acc)[RPT]) {
-  constexpr int CB = RPT == 16 ? 6 : (48 / RPT < 13 ? 48 / RPT : 13);
-  constexpr unsigned CM = (1u << CB) - 1;
-  int o = (int)(m & 0xffff);
-  unsigned long long w = m >> 16;
-#pragma unroll
-  for (int j = 0; j < RPT; ++j) {
-    if (RPT == 16 && j == 8) w = m1;
-    const int n = (int)((unsigned)w & CM);
-    w >>= CB;
-    double t = acc[j];
-    for (int k = 0; k < n; ++k) t += pb[o + k];
-    acc[j] = t;
-    o += n;
-  }
-}
-
-template <class Epi, int RPT>
-__global__ __launch_bounds__(kCsThreads) void k_spmv_cs(CsView A, const double *__restrict__ x, Epi epi, const int *done_flag,
-                                                         int *step_counter) {
-  if (done_flag && *done_flag) return;
-  if (step_counter && blockIdx.x == 0 && threadIdx.x == 0) *step_counter += 1;  // one CG step begins
-  constexpr int NQ = kCsQuads;
-  __shared__ __attribute__((aligned(16))) double prod[2][kCsPass];
-  __shared__ double red[kCsThreads / 64];
-  const int tid = threadIdx.x, wg = blockIdx.x, c = wg / A.split, part = wg - c * A.split;
-  constexpr int NS = Epi::kSums > 0 ? Epi::kSums : 1, NM = Epi::kMaxs > 0 ? Epi::kMaxs : 1;
-  double sums[NS], maxs[NM], acc[RPT];
-#pragma unroll
-  for (int i = 0; i < NS; ++i) sums[i] = 0.;
-#pragma unroll
-  for (int i = 0; i < NM; ++i) maxs[i] = 0.;
-#pragma unroll
-  for (int j = 0; j < RPT; ++j) acc[j] = 0.;
-
-  const int g0 = A.passptr[wg], g1 = A.passptr[wg + 1];
-  uint4 ic[NQ], in[NQ];
-  double2 va[NQ], vb[NQ], na[NQ], nb[NQ];
-  unsigned long long mc = 0, mn = 0, mc1 = 0, mn1 = 0;
-  int2 pc{0, 0}, pn{0, 0};
-  // a lane's i-th quad belongs to the block of 256 sorted nonzeros (tid >> 6) + 16 i: blocks beyond the pass's
-  // nonzero count hold only padding and are skipped (wave-uniform)
-  auto load = [&](int g, uint4(&ii)[NQ], double2(&a)[NQ], double2(&b)[NQ], unsigned long long &m, unsigned long long &m1, int2 &pi) {
-    const uint4 *i4 = reinterpret_cast<const uint4 *>(A.idx + (size_t)g * kCsPass);
-    const double2 *v2 = reinterpret_cast<const double2 *>(A.val + (size_t)g * kCsPass);
-    pi = A.pinfo[g];
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      const int q = tid + i * kCsThreads;
-      if (((q >> 6) << 8) < pi.y) {
-        ii[i] = i4[q];
-        a[i] = v2[2 * q];
-        b[i] = v2[2 * q + 1];
-      }
-    }
-    m = A.meta[((size_t)g * kCsThreads + tid) * (RPT == 16 ? 2 : 1)];
-    if (RPT == 16) m1 = A.meta[((size_t)g * kCsThreads + tid) * 2 + 1];
-  };
-  if (g0 < g1) load(g0, ic, va, vb, mc, mc1, pc);
-  int buf = 0;
-  for (int g = g0; g < g1; ++g) {
-    // gathers of this pass first, then the streaming loads of the next one: the in-order return queue hands the
-    // gathered x back without waiting for the HBM latency of the stream
-    const double *xb = x + pc.x;
-    double xg[NQ][4];
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      if ((((tid + i * kCsThreads) >> 6) << 8) < pc.y) {
-        xg[i][0] = xb[ic[i].x >> kCsSlotBits];
-        xg[i][1] = xb[ic[i].y >> kCsSlotBits];
-        xg[i][2] = xb[ic[i].z >> kCsSlotBits];
-        xg[i][3] = xb[ic[i].w >> kCsSlotBits];
-      }
-    }
-    if (g + 1 < g1) load(g + 1, in, na, nb, mn, mn1, pn);
-    double *pb = prod[buf];
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      if ((((tid + i * kCsThreads) >> 6) << 8) < pc.y) {
-        pb[ic[i].x & (kCsPass - 1)] = va[i].x * xg[i][0];
-        pb[ic[i].y & (kCsPass - 1)] = va[i].y * xg[i][1];
-        pb[ic[i].z & (kCsPass - 1)] = vb[i].x * xg[i][2];
-        pb[ic[i].w & (kCsPass - 1)] = vb[i].y * xg[i][3];
-      }
-    }
-    __syncthreads();
-    cs_row_sums<RPT>(pb, mc, mc1, acc);
-    buf ^= 1;
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) { ic[i] = in[i]; va[i] = na[i]; vb[i] = nb[i]; }
-    mc = mn;
-    mc1 = mn1;
-    pc = pn;
-  }
-#pragma unroll
-  for (int j = 0; j < RPT; ++j) {
-    cs_slot_done(A, epi, part, c, j * kCsThreads + tid, acc[j], sums, maxs, false);
-  }
-  if constexpr (Epi::kSums > 0 || Epi::kMaxs > 0) {
-    const int nslot = A.pstride > 0 ? A.pstride : (int)gridDim.x, slot = A.pbase + wg;
-#pragma unroll
-    for (int i = 0; i < Epi::kSums; ++i) {
-      const double t = block_sum<kCsThreads>(sums[i], red);
-      if (tid == 0) epi.partial[(size_t)i * nslot + slot] = t;
-    }
-#pragma unroll
-    for (int i = 0; i < Epi::kMaxs; ++i) {
-      const double t = block_max<kCsThreads>(maxs[i], red);
-      if (tid == 0) epi.partial[(size_t)(Epi::kSums + i) * nslot + slot] = t;
-    }
-  }
-}
-
-
-// Gather-ahead schedule of the same pass loop (same data, same per-row order => same bits): the gathers of pass
-// g + 1 are issued right after the barrier of pass g, BEFORE its LDS row sums, and the streaming loads of pass g + 2
-// behind them, so the vector-memory pipe works through the LDS / barrier phase and every streamed pass has a whole
-// pass of time to arrive.  Two register sets alternate (the loop is unrolled by two: no copies of in-flight loads).
-template <int NQ>
-struct CsSet {
-  uint4 ic[NQ];
-  double2 va[NQ], vb[NQ];
-  unsigned long long meta, meta1;
-  int2 pi;
-};
-
-// ABL (tools/slab_lab.hip ablations, results intentionally wrong): 1 = gathers folded into a 2 KB table,
-// 2 = no LDS row sums, 3 = no LDS traffic at all, 4 = no streamed values (idx only)
-template <class Epi, int RPT, int ABL = 0>
-__global__ __launch_bounds__(kCsThreads) void k_spmv_cs_ga(CsView A, const double *__restrict__ x, Epi epi, const int *done_flag,
-                                                            int *step_counter) {
-  if (done_flag && *done_flag) return;
-  if (step_counter && blockIdx.x == 0 && threadIdx.x == 0) *step_counter += 1;  // one CG step begins
-  constexpr int NQ = kCsQuads;
-  __shared__ __attribute__((aligned(16))) double prod[2][kCsPass];
-  __shared__ double red[kCsThreads / 64];
-  const int tid = threadIdx.x, wg = blockIdx.x, c = wg / A.split, part = wg - c * A.split;
-  constexpr int NS = Epi::kSums > 0 ? Epi::kSums : 1, NM = Epi::kMaxs > 0 ? Epi::kMaxs : 1;
-  double sums[NS], maxs[NM], acc[RPT];
-#pragma unroll
-  for (int i = 0; i < NS; ++i) sums[i] = 0.;
-#pragma unroll
-  for (int i = 0; i < NM; ++i) maxs[i] = 0.;
-#pragma unroll
-  for (int j = 0; j < RPT; ++j) acc[j] = 0.;
-  const int g0 = A.passptr[wg], g1 = A.passptr[wg + 1];
-  CsSet<NQ> S0, S1;
-  double xg[NQ][4];
-  auto load = [&](int g, CsSet<NQ> &S) {
-    const uint4 *i4 = reinterpret_cast<const uint4 *>(A.idx + (size_t)g * kCsPass);
-    const double2 *v2 = reinterpret_cast<const double2 *>(A.val + (size_t)g * kCsPass);
-    S.pi = A.pinfo[g];
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      const int q = tid + i * kCsThreads;
-      if (((q >> 6) << 8) < S.pi.y) {
-        S.ic[i] = i4[q];
-        if (ABL == 4) { S.va[i] = double2{1., 1.}; S.vb[i] = double2{1., 1.}; }
-        else { S.va[i] = v2[2 * q]; S.vb[i] = v2[2 * q + 1]; }
-      }
-    }
-    S.meta = A.meta[((size_t)g * kCsThreads + tid) * (RPT == 16 ? 2 : 1)];
-    if (RPT == 16) S.meta1 = A.meta[((size_t)g * kCsThreads + tid) * 2 + 1];
-  };
-  auto gather = [&](const CsSet<NQ> &S) {
-    const double *xb = x + S.pi.x;
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      if ((((tid + i * kCsThreads) >> 6) << 8) < S.pi.y) {
-        constexpr unsigned GM = ABL == 1 ? 255u : 0xffffffffu;
-        xg[i][0] = xb[(S.ic[i].x >> kCsSlotBits) & GM];
-        xg[i][1] = xb[(S.ic[i].y >> kCsSlotBits) & GM];
-        xg[i][2] = xb[(S.ic[i].z >> kCsSlotBits) & GM];
-        xg[i][3] = xb[(S.ic[i].w >> kCsSlotBits) & GM];
-      }
-    }
-  };
-  // pass g lives in X (its gathers are in flight), pass g + 1 streams into Y
-  auto step = [&](int g, CsSet<NQ> &X, CsSet<NQ> &Y, int buf) {
-    double *pb = prod[buf];
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      if ((((tid + i * kCsThreads) >> 6) << 8) < X.pi.y) {
-        if (ABL == 3) {
-          acc[0] += X.va[i].x * xg[i][0] + X.va[i].y * xg[i][1] + X.vb[i].x * xg[i][2] + X.vb[i].y * xg[i][3];
-        } else {
-          pb[X.ic[i].x & (kCsPass - 1)] = X.va[i].x * xg[i][0];
-          pb[X.ic[i].y & (kCsPass - 1)] = X.va[i].y * xg[i][1];
-          pb[X.ic[i].z & (kCsPass - 1)] = X.vb[i].x * xg[i][2];
-          pb[X.ic[i].w & (kCsPass - 1)] = X.vb[i].y * xg[i][3];
-        }
-      }
-    }
-    const unsigned long long mc = X.meta, mc1 = RPT == 16 ? X.meta1 : 0;
-    __syncthreads();
-    if (g + 1 < g1) gather(Y);
-    if (g + 2 < g1) load(g + 2, X);
-    if (ABL == 2 || ABL == 3) { acc[0] += (double)(mc & 0xffffff); return; }
-    cs_row_sums<RPT>(pb, mc, mc1, acc);
-  };
-  if (g0 < g1) {
-    load(g0, S0);
-    gather(S0);
-    if (g0 + 1 < g1) load(g0 + 1, S1);
-  }
-  for (int g = g0; g < g1; g += 2) {
-    step(g, S0, S1, 0);
-    if (g + 1 < g1) step(g + 1, S1, S0, 1);
-  }
-#pragma unroll
-  for (int j = 0; j < RPT; ++j) {
-    cs_slot_done(A, epi, part, c, j * kCsThreads + tid, acc[j], sums, maxs, false);
-  }
-  if constexpr (Epi::kSums > 0 || Epi::kMaxs > 0) {
-    const int nslot = A.pstride > 0 ? A.pstride : (int)gridDim.x, slot = A.pbase + wg;
-#pragma unroll
-    for (int i = 0; i < Epi::kSums; ++i) {
-      const double t = block_sum<kCsThreads>(sums[i], red);
-      if (tid == 0) epi.partial[(size_t)i * nslot + slot] = t;
-    }
-#pragma unroll
-    for (int i = 0; i < Epi::kMaxs; ++i) {
-      const double t = block_max<kCsThreads>(maxs[i], red);
-      if (tid == 0) epi.partial[(size_t)(Epi::kSums + i) * nslot + slot] = t;
-    }
-  }
-}
-
-// Braided schedule (default): same passes, same per-row order => same bits as k_spmv_cs_ga.  What the timeline of
-// the gather-ahead kernel shows (tools/cs_lab.hip, s_memtime stamps): a wave spends 43 % of the launch ISSUING the
-// gathers of the next pass — the texture addresser takes ~2.3 clk per distinct 128-byte line and back-pressures the
+// The pass kernel.  Braided schedule: what the timeline of its predecessor, the gather-ahead kernel (all gathers of pass
+// g + 1 right after the barrier of pass g, then the LDS row sums; same bits), showed: a wave spends 43 % of the
+// launch ISSUING the gathers of the next pass — the texture addresser takes ~2.3 clk per distinct 128-byte line and back-pressures the
 // issue — then 20 % in the LDS row sums of the current pass while the addresser runs dry, then waits at the barrier for
-// the slowest issuer.  Here the two are braided: after the barrier every lane alternates "issue a slice of the memory
-// instructions of the coming passes" / "sum one of its rows from LDS", so the LDS latency hides behind the addresser
+// the slowest issuer.  Here the two are braided: after the barrier every lane alternates "issue a slice of the gathers
+// of the next pass" / "sum one of its rows from LDS", so the LDS latency hides behind the addresser
 // instead of following it.  Two details keep hipcc's wait-count insertion exact (a conditional load in one arm of a
 // branch makes it fall back to vmcnt(0), i.e. to draining the stream loads it just issued): full passes — all but the
-// last of a workgroup — run a branch-free body with unconditional loads (MASKED = false), and the per-pass header
+// last of a workgroup — run a branch-free body with unconditional loads (TAIL = false), and the per-pass header
 // {first column, count} comes through the scalar cache (constant address space) two passes ahead.
 typedef const int __attribute__((address_space(4))) *CsPinfoScalarPtr;
 
@@ -581,7 +349,7 @@ typedef const int __attribute__((address_space(4))) *CsPinfoScalarPtr;
 #define CS_TL_FLUSH()
 #endif
 
-template <class Epi, int RPT, int ABL = 0>
+template <class Epi, int RPT>
 __global__ __launch_bounds__(kCsThreads) void k_spmv_cs_il(CsView A, const double *__restrict__ x, Epi epi, const int *done_flag,
                                                             int *step_counter) {
   if (done_flag && *done_flag) return;
@@ -603,8 +371,7 @@ __global__ __launch_bounds__(kCsThreads) void k_spmv_cs_il(CsView A, const doubl
   for (int j = 0; j < RPT; ++j) acc[j] = 0.;
   const int g0 = A.passptr[wg], g1 = A.passptr[wg + 1];
   CS_TL_DECL;
-  // (the default schedule only: the register budget of the others is not worth touching)
-  constexpr bool kPre = epi_has_prefetch<Epi>::value && ABL == 6;
+  constexpr bool kPre = epi_has_prefetch<Epi>::value;
   double pre[kPre ? RPT : 1];
   bool pre_ok = false;
   if (g0 < g1) {
@@ -616,33 +383,19 @@ __global__ __launch_bounds__(kCsThreads) void k_spmv_cs_il(CsView A, const doubl
     };
     // Every load is unconditional: the padding of a pass holds zero values with their own slots beyond every run and
     // column offset 0, so it is harmless to process (build_cs balances the passes of a workgroup: < 2 % padding).
-    // Issue order inside a braid: the gathers of pass g + 1 FIRST, the stream loads of pass g + 2 behind them — a
-    // wave's loads return in order, and gathered lines that had to wait in the 32 KB L1 behind an HBM-latency load
-    // of the same wave would be evicted before they are consumed.
+    // Issue order of the prologue: the gathers of a pass BEFORE the stream loads of the pass after it — a wave's loads
+    // return in order, and gathered lines that had to wait in the 32 KB L1 behind an HBM-latency load of the same wave
+    // would be evicted before they are consumed.
     struct Set { uint4 ic[NQ]; double2 va[NQ], vb[NQ]; unsigned long long meta, meta1; };
     Set S0, S1;
     double xg[NQ][4];
-    // (lab ablation 5, tools/cs_lab.hip: the pass stream with the non-temporal cache policy — does keeping the HBM-latency stream lines
-    //  out of the L1 / L2 allocation help the gathers?  Round 4: no, profiles/r04_cs_stream_lab.txt)
-    typedef unsigned cs_u4 __attribute__((ext_vector_type(4)));
-    typedef double cs_f2 __attribute__((ext_vector_type(2)));
+    // (Round 4: the non-temporal cache policy on the pass stream does not help the gathers, profiles/r04_cs_stream_lab.txt)
     auto ld_idx = [&](int s, Set &S, int gl) {
-      if constexpr (ABL == 5) {
-        const cs_u4 t = __builtin_nontemporal_load(reinterpret_cast<const cs_u4 *>(A.idx + (size_t)gl * kCsPass) + (tid + s * kCsThreads));
-        S.ic[s] = uint4{t.x, t.y, t.z, t.w};
-      } else {
-        S.ic[s] = reinterpret_cast<const uint4 *>(A.idx + (size_t)gl * kCsPass)[tid + s * kCsThreads];
-      }
+      S.ic[s] = reinterpret_cast<const uint4 *>(A.idx + (size_t)gl * kCsPass)[tid + s * kCsThreads];
     };
     auto ld_val = [&](int s, Set &S, int gl) {  // s in [0, 2 NQ)
       const int i = s >> 1, h = s & 1;
-      double2 v;
-      if constexpr (ABL == 5) {
-        const cs_f2 t = __builtin_nontemporal_load(reinterpret_cast<const cs_f2 *>(A.val + (size_t)gl * kCsPass) + (2 * (tid + i * kCsThreads) + h));
-        v = double2{t.x, t.y};
-      } else {
-        v = reinterpret_cast<const double2 *>(A.val + (size_t)gl * kCsPass)[2 * (tid + i * kCsThreads) + h];
-      }
+      const double2 v = reinterpret_cast<const double2 *>(A.val + (size_t)gl * kCsPass)[2 * (tid + i * kCsThreads) + h];
       if (h == 0) S.va[i] = v; else S.vb[i] = v;
     };
     auto ld_meta = [&](Set &S, int gl) {
@@ -657,38 +410,20 @@ __global__ __launch_bounds__(kCsThreads) void k_spmv_cs_il(CsView A, const doubl
     auto gat = [&](int k, const Set &S, int col0) {  // k in [0, 4 NQ)
       const int i = k >> 2, e = k & 3;
       const unsigned id = e == 0 ? S.ic[i].x : e == 1 ? S.ic[i].y : e == 2 ? S.ic[i].z : S.ic[i].w;
-      constexpr unsigned GM = ABL == 1 ? 255u : 0xffffffffu;  // (lab ablation 1: gathers folded into a 2 KB table)
       // (uniform base + unsigned 32-bit byte offset: the saddr form of global_load, no 64-bit address arithmetic)
-      const unsigned off = ((id >> kCsSlotBits) & GM) << 3;
+      const unsigned off = (id >> kCsSlotBits) << 3;
       xg[i][e] = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(x + col0) + off);
     };
-    // memory instruction k of the braid of step g, in issue order: the gathers of pass g + 1 (in Y, first column c1),
-    // then index quads, values and run descriptor of pass g + 2 into X.  TAIL: the last two steps of the workgroup,
-    // where some of these passes do not exist (uniform branches).
-    // PRE (lab ablation 6, round 4): the stream loads of pass g + 2 are issued BEFORE the barrier of step g — into the registers the
-    // product scatter has just freed — instead of behind the gathers in the braid: while the workgroup waits at the barrier for its
-    // slowest wavefront nobody issues memory instructions and the vector-memory pipe drains (the barrier is 26 % of a wavefront's
-    // time, tools/cs_lab.hip timeline); loads that depend on nothing can fill that hole.
-    // PREG quads of the gathers of pass g + 1 go before the barrier too, each right behind the products that free its registers
-    // (7: one of the two quads, 9: both — then the braid issues nothing); 8: stream before the barrier, ALL gathers in the first row slot.
-    constexpr bool PRE = (ABL >= 6 && ABL <= 10) || ABL == 12 || ABL == 14;   // (10: as 6 with ONE gather per row slot; 12: as 6 with straight-line tail steps; 13: plain braid with them)
-    constexpr int PREG = ABL == 7 ? 1 : ABL == 9 ? NQ : 0;
-    constexpr int NGAT = 4 * NQ, NVAL = 2 * NQ, NMEM = PRE ? NGAT : NGAT + NQ + NVAL + 1;
-    // `tail` is a compile-time mode: 0 = passes g + 1 and g + 2 exist (steady state), 1 = test at run time (uniform branches — every
-    // load inside one costs the exact wait counts), 2 = pass g + 1 exists, g + 2 does not, 3 = neither (the workgroup's last pass)
-#define CS_HAS1 (TM == 0 || TM == 2 || (TM == 1 && g + 1 < g1))
-#define CS_HAS2 (TM == 0 || (TM == 1 && g + 2 < g1))
-    auto mem_op = [&](auto tail, int k, int g, const Set &Y, int c1, Set &X) {
-      constexpr int TM = (int)decltype(tail)::value;
-      if (k < 4 * PREG) return;
-      if (k < NGAT) { if (CS_HAS1) gat(k, Y, c1); }
-      else if (k < NGAT + NQ) { if (CS_HAS2) ld_idx(k - NGAT, X, g + 2); }
-      else if (k < NGAT + NQ + NVAL) { if (CS_HAS2) ld_val(k - NGAT - NQ, X, g + 2); }
-      else { if (CS_HAS2) ld_meta(X, g + 2); }
-    };
-    // products of pass g (in X) -> LDS, barrier, then the braid with the row sums of pass g
+    // One step: products of pass g (in X) -> LDS; the stream loads of pass g + 2 — index quads, values, run descriptor — into the
+    // registers the product scatter has just freed; barrier; then the braid: the gathers of pass g + 1 (in Y, first column c1) in
+    // slices between the row sums of pass g.  The stream loads go BEFORE the barrier (round 4) instead of behind the gathers in the
+    // braid: while the workgroup waits at the barrier for its slowest wavefront nobody issues memory instructions and the
+    // vector-memory pipe drains (the barrier is 26 % of a wavefront's time, tools/cs_lab.hip timeline); loads that depend on nothing
+    // fill that hole.  TAIL: the last two steps of the workgroup, where passes g + 1 / g + 2 may not exist (tested at run time,
+    // uniform branches — every load inside one costs the exact wait counts).
+    constexpr int NGAT = 4 * NQ, NVAL = 2 * NQ;
     auto step = [&](auto tail, int g, Set &X, const Set &Y, int c1, int buf) {
-      constexpr int TM = (int)decltype(tail)::value;
+      constexpr bool TAIL = decltype(tail)::value;
       double *pb = prod[buf];
 #pragma unroll
       for (int i = 0; i < NQ; ++i) {
@@ -696,44 +431,35 @@ __global__ __launch_bounds__(kCsThreads) void k_spmv_cs_il(CsView A, const doubl
         pb[X.ic[i].y & (kCsPass - 1)] = X.va[i].y * xg[i][1];
         pb[X.ic[i].z & (kCsPass - 1)] = X.vb[i].x * xg[i][2];
         pb[X.ic[i].w & (kCsPass - 1)] = X.vb[i].y * xg[i][3];
-        if constexpr (PREG > 0) {
-          if (i < PREG && CS_HAS1) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) gat(4 * i + e, Y, c1);
-          }
-        }
       }
       const unsigned long long mc = X.meta, mc1 = RPT == 16 ? X.meta1 : 0;
-      if constexpr (PRE) {
-        if (CS_HAS2) {
+      if (!TAIL || g + 2 < g1) {
 #pragma unroll
-          for (int s = 0; s < NQ; ++s) ld_idx(s, X, g + 2);
+        for (int s = 0; s < NQ; ++s) ld_idx(s, X, g + 2);
 #pragma unroll
-          for (int s = 0; s < NVAL; ++s) ld_val(s, X, g + 2);
-          ld_meta(X, g + 2);
-        }
+        for (int s = 0; s < NVAL; ++s) ld_val(s, X, g + 2);
+        ld_meta(X, g + 2);
       }
       CS_TL_STAMP(1);
       __syncthreads();
       CS_TL_STAMP(2);
       int o = (int)(mc & 0xffff);
       unsigned long long w = mc >> 16;
-      // memory instructions per row: at least two, so that the gathers are all with the addresser after a few rows
-      constexpr int PER = ABL == 8 ? NMEM : ABL == 10 ? (NMEM + RPT - 1) / RPT : (NMEM + RPT - 1) / RPT > 2 ? (NMEM + RPT - 1) / RPT : 2;
+      // gathers per row: at least two, so that they are all with the addresser after a few rows
+      constexpr int PER = (NGAT + RPT - 1) / RPT > 2 ? (NGAT + RPT - 1) / RPT : 2;
 #pragma unroll
       for (int j = 0; j < RPT; ++j) {
 #pragma unroll
-        for (int k = j * PER; k < (j + 1) * PER && k < NMEM; ++k) mem_op(tail, k, g, Y, c1, X);
+        for (int k = j * PER; k < (j + 1) * PER && k < NGAT; ++k) {
+          if (!TAIL || g + 1 < g1) gat(k, Y, c1);
+        }
         __builtin_amdgcn_sched_barrier(0);
         if (RPT == 16 && j == 8) w = mc1;
         const int n = (int)((unsigned)w & CM);
         w >>= CB;
         double t = acc[j];
-        if (ABL == 2) t += (double)n;  // (lab ablation 2: no LDS row sums)
-        else {
 #pragma nounroll
-          for (int k = 0; k < n; ++k) t += pb[o + k];  // (n is ~1: unrolling only costs registers)
-        }
+        for (int k = 0; k < n; ++k) t += pb[o + k];  // (n is ~1: unrolling only costs registers)
         acc[j] = t;
         o += n;
         __builtin_amdgcn_sched_barrier(0);
@@ -742,38 +468,21 @@ __global__ __launch_bounds__(kCsThreads) void k_spmv_cs_il(CsView A, const doubl
     };
     // first column of pass g + 1: scalar loads ahead of use
     int cn = get_pi(g0 + 1).x;
-    if constexpr (ABL == 14) {  // (lab, round 4: the first gathers as early as possible — index quads, gathers, THEN the values of pass g0)
+    // prologue: stream passes g0 and g0 + 1, gather g0
 #pragma unroll
-      for (int s = 0; s < NQ; ++s) ld_idx(s, S0, g0);
-      const int c0 = get_pi(g0).x;
+    for (int s = 0; s < NQ; ++s) ld_idx(s, S0, g0);
 #pragma unroll
-      for (int k = 0; k < NGAT; ++k) gat(k, S0, c0);
+    for (int s = 0; s < NVAL; ++s) ld_val(s, S0, g0);
+    ld_meta(S0, g0);
+    const int c0 = get_pi(g0).x;
 #pragma unroll
-      for (int s = 0; s < NVAL; ++s) ld_val(s, S0, g0);
-      ld_meta(S0, g0);
-      if (g0 + 1 < g1) {
+    for (int k = 0; k < NGAT; ++k) gat(k, S0, c0);
+    if (g0 + 1 < g1) {
 #pragma unroll
-        for (int s = 0; s < NQ; ++s) ld_idx(s, S1, g0 + 1);
+      for (int s = 0; s < NQ; ++s) ld_idx(s, S1, g0 + 1);
 #pragma unroll
-        for (int s = 0; s < NVAL; ++s) ld_val(s, S1, g0 + 1);
-        ld_meta(S1, g0 + 1);
-      }
-    } else {  // prologue: stream passes g0 and g0 + 1, gather g0
-#pragma unroll
-      for (int s = 0; s < NQ; ++s) ld_idx(s, S0, g0);
-#pragma unroll
-      for (int s = 0; s < NVAL; ++s) ld_val(s, S0, g0);
-      ld_meta(S0, g0);
-      const int c0 = get_pi(g0).x;
-#pragma unroll
-      for (int k = 0; k < NGAT; ++k) gat(k, S0, c0);
-      if (g0 + 1 < g1) {
-#pragma unroll
-        for (int s = 0; s < NQ; ++s) ld_idx(s, S1, g0 + 1);
-#pragma unroll
-        for (int s = 0; s < NVAL; ++s) ld_val(s, S1, g0 + 1);
-        ld_meta(S1, g0 + 1);
-      }
+      for (int s = 0; s < NVAL; ++s) ld_val(s, S1, g0 + 1);
+      ld_meta(S1, g0 + 1);
     }
     if constexpr (kPre) {
 #pragma unroll
@@ -792,31 +501,13 @@ __global__ __launch_bounds__(kCsThreads) void k_spmv_cs_il(CsView A, const doubl
       step(std::false_type{}, g + 1, S1, S0, cn, 1);  // pass g + 1 in S1, g + 2 in S0, g + 3 streams into S1
       cn = get_pi(g + 3).x;
     }
-    if constexpr (ABL == 12 || ABL == 13) {
-      // the last two or three passes: one straight-line step body per case instead of run-time tests around every load
-      using M0 = std::integral_constant<int, 0>; using M2 = std::integral_constant<int, 2>; using M3 = std::integral_constant<int, 3>;
-      for (; g < g1; g += 2) {
-        const int rem = g1 - g;
-        if (rem >= 3) step(M0{}, g, S0, S1, cn, 0);
-        else if (rem == 2) step(M2{}, g, S0, S1, cn, 0);
-        else step(M3{}, g, S0, S1, cn, 0);
-        cn = get_pi(g + 2).x;
-        if (rem >= 4) step(M0{}, g + 1, S1, S0, cn, 1);
-        else if (rem == 3) step(M2{}, g + 1, S1, S0, cn, 1);
-        else if (rem == 2) step(M3{}, g + 1, S1, S0, cn, 1);
-        cn = get_pi(g + 3).x;
-      }
-    } else {
     for (; g < g1; g += 2) {
       step(std::true_type{}, g, S0, S1, cn, 0);
       cn = get_pi(g + 2).x;
       if (g + 1 < g1) step(std::true_type{}, g + 1, S1, S0, cn, 1);
       cn = get_pi(g + 3).x;
     }
-    }
   }
-#undef CS_HAS1
-#undef CS_HAS2
   const bool combine = A.split > 1 && A.ticket != nullptr;
   if (combine) {
     // Publish the partial row sums with write-through (sc1) 16-byte stores — acknowledged stores are visible to every
@@ -892,57 +583,19 @@ __global__ __launch_bounds__(kCsThreads) void k_spmv_cs_il(CsView A, const doubl
   }
 }
 
-// 3 (default, round 4) = braided gathers / row sums with the stream loads of pass g + 2 issued BEFORE the barrier of step g
-// (k_spmv_cs_il<.., 6>: -6..7 us per launch on the metric shapes, same bits; tools/cs_lab.hip, profiles/r04_cs_lab.txt);
-// 2 = the braid of rounds 2-3 (stream loads behind the gathers); 1 = gather-ahead (k_spmv_cs_ga); 0 = k_spmv_cs
-// The product launches schedule 3 only; the older schedules (and the in-kernel combine of split layouts, which lives in the stage-default
-// instantiation of k_spmv_cs_il) are instantiated in the labs build (SCS_HIP_CS_SCHED, SCS_HIP_CS_COMBINE: options.hpp).
-inline int cs_schedule() { return kLabsBuild ? opts().cs_sched : 3; }
-
+// (The in-kernel combine of split layouts is reached in the labs build only: SCS_HIP_CS_COMBINE, options.hpp.)
 template <class Epi>
 inline void launch_spmv_cs(const CsView &A, const double *x, const Epi &epi, const int *done_flag, hipStream_t s,
                            int *step_counter) {
   if (A.nchunks <= 0) return;
   const dim3 g(A.nchunks * A.split), b(kCsThreads);
-  if (cs_schedule() >= 3) {
-    switch (A.rpt) {
-      case 1: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 1, 6>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-      case 2: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 2, 6>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-      case 4: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 4, 6>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-      case 8: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 8, 6>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-      default: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 16, 6>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-    }
-    return;
-  }
-#ifdef SCS_HIP_LABS
-  if (cs_schedule() == 2 || (A.split > 1 && A.ticket != nullptr)) {  // (the in-kernel combine lives in k_spmv_cs_il only)
-    switch (A.rpt) {
-      case 1: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 1>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-      case 2: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 2>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-      case 4: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 4>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-      case 8: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 8>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-      default: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 16>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-    }
-    return;
-  }
-  if (cs_schedule() == 1) {
-    switch (A.rpt) {
-      case 1: hipLaunchKernelGGL((k_spmv_cs_ga<Epi, 1>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-      case 2: hipLaunchKernelGGL((k_spmv_cs_ga<Epi, 2>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-      case 4: hipLaunchKernelGGL((k_spmv_cs_ga<Epi, 4>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-      case 8: hipLaunchKernelGGL((k_spmv_cs_ga<Epi, 8>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-      default: hipLaunchKernelGGL((k_spmv_cs_ga<Epi, 16>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-    }
-    return;
-  }
   switch (A.rpt) {
-    case 1: hipLaunchKernelGGL((k_spmv_cs<Epi, 1>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-    case 2: hipLaunchKernelGGL((k_spmv_cs<Epi, 2>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-    case 4: hipLaunchKernelGGL((k_spmv_cs<Epi, 4>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-    case 8: hipLaunchKernelGGL((k_spmv_cs<Epi, 8>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
-    default: hipLaunchKernelGGL((k_spmv_cs<Epi, 16>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
+    case 1: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 1>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
+    case 2: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 2>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
+    case 4: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 4>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
+    case 8: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 8>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
+    default: hipLaunchKernelGGL((k_spmv_cs_il<Epi, 16>), g, b, 0, s, A, x, epi, done_flag, step_counter); break;
   }
-#endif
 }
 
 }  // namespace scship

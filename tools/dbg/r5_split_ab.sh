@@ -21,4 +21,3 @@ run "same again (box noise)" X=1
 run "A split in two + in-kernel combine, A' split in two + in-kernel combine" SCS_HIP_CS_COMBINE=1 SCS_HIP_CS_SPLIT_A=2 SCS_HIP_CS_SPLIT_AT=2
 run "A split in two + combine, A' split in four + combine" SCS_HIP_CS_COMBINE=1 SCS_HIP_CS_SPLIT_A=2 SCS_HIP_CS_SPLIT_AT=4
 run "A unsplit, A' split in two + in-kernel combine (no partial vectors)" SCS_HIP_CS_COMBINE=1 SCS_HIP_CS_SPLIT_A=1 SCS_HIP_CS_SPLIT_AT=2
-run "round-2/3 schedule, shipped layout (SCS_HIP_CS_SCHED=2)" SCS_HIP_CS_SCHED=2
