@@ -142,6 +142,30 @@ SCS_HIP_API void scs_hip_kernel_times(const ScsWork *w, double *out);
  * host copies scs_solve returned (NaN where the status leaves a vector undefined).  scs/batch.py gathers from these. */
 SCS_HIP_API int scs_hip_solution_to_device(ScsWork *w, scs_float *x_dev, scs_float *y_dev, scs_float *s_dev);
 
+/* Device-resident endpoints: scs_update / scs_solve / scs_hip_solve_batch for callers whose b, c, warm start and solution live in
+ * HBM (a sweep over one matrix inside a device program).  Every *_dev pointer is a DEVICE address on the workspace's device
+ * (scs_hip_work_device); anything else is refused with -1 before device work starts.  No vector of n or m doubles crosses the host:
+ * an update reads back three doubles (max |b|, max |c|, sigma), a solve the flags and residual partials scs_solve reads.
+ *
+ * STREAM CONTRACT.  The library works on its own non-blocking stream.  The CALLER guarantees that the inputs (b_dev, c_dev and, with
+ * warm_start, x_dev / y_dev / s_dev) are complete before the call — synchronise the stream that produced them.  The LIBRARY drains
+ * its stream before it returns, as scs_solve does, so the outputs may be read from any stream afterwards.
+ *
+ *   update_device: b_dev (m) / c_dev (n), NULL = keep the current vector.  Same arithmetic as scs_update: a following solve gives the
+ *                  same bits.  Host and device updates may be mixed; scs_hip_clone still starts from what scs_init was given.
+ *   solve_device:  x_dev (n), y_dev (m), s_dev (m) hold the warm start on entry when warm_start != 0 (all three are required
+ *                  then) and the solution on return; a NULL pointer skips that output.  info, the status, NaN for a vector the status
+ *                  leaves undefined, Ctrl-C, log_csv and verbose are scs_solve's; the return value is the status, -1 for refused
+ *                  arguments (scs_hip_last_error).
+ *   solve_batch_device: the grouped solve over arrays of such pointers (any of the three arrays may be NULL without warm_start).  Its
+ *                  groups are those of scs_hip_solve_batch: scs_hip_batch_plan is the plan. */
+SCS_HIP_API scs_int scs_hip_update_device(ScsWork *w, const scs_float *b_dev, const scs_float *c_dev);
+SCS_HIP_API scs_int scs_hip_solve_device(ScsWork *w, scs_float *x_dev, scs_float *y_dev, scs_float *s_dev, ScsInfo *info, scs_int warm_start);
+SCS_HIP_API scs_int scs_hip_solve_batch_device(ScsWork **w, scs_float **x_dev, scs_float **y_dev, scs_float **s_dev, ScsInfo **info,
+                                               scs_int count, scs_int warm_start);
+/* the HIP device a workspace lives on (-1: NULL) */
+SCS_HIP_API int scs_hip_work_device(const ScsWork *w);
+
 /* Grouped solve of `count` independent, already initialised workspaces (BASELINE.json configs[4]: a batch of small cone
  * programs; the reference's notion is "independent instances run concurrently", R:test/test_thread_safety.py:78-93 —
  * one scs_solve per thread).  Members of equal shape (n, m, cone structure, Anderson schedule) whose matrices use the

@@ -280,6 +280,7 @@ static std::atomic<long> g_tiled_launches{0};  // scs_hip_tiled_launches(): test
 struct GroupSolve {
   std::vector<ScsHipWork *> W;
   std::vector<ScsSolution *> sols;
+  bool dev_io = false;  // sols hold DEVICE addresses (scs_hip_solve_batch_device; work_solve_ends.inl)
   std::vector<ScsInfo *> infos;
   int G = 0, n = 0, m = 0;
   long l = 0;
@@ -976,7 +977,7 @@ struct GroupSolve {
       }
     }
     t_start = now_ms();  // behind the deferred setup: solve_time is the solve (ScsInfo as the reference fills it)
-    for (int g = 0; g < G; ++g) W[(size_t)g]->begin_solve(sols[(size_t)g], infos[(size_t)g], warm_start);
+    for (int g = 0; g < G; ++g) W[(size_t)g]->begin_solve(sols[(size_t)g], infos[(size_t)g], warm_start, dev_io);
     for (int g = 0; g < G; ++g) {
       if (dense)
         std::snprintf(infos[(size_t)g]->lin_sys_solver, sizeof(infos[(size_t)g]->lin_sys_solver),
@@ -998,7 +999,7 @@ struct GroupSolve {
         sync();
         for (int g : active) {
           infos[(size_t)g]->status_val = SCS_SIGINT;
-          W[(size_t)g]->finish_solve(sols[(size_t)g], infos[(size_t)g], i, t_start, t_lin, t_cone, t_acc, /*grouped=*/true);
+          W[(size_t)g]->finish_solve(sols[(size_t)g], infos[(size_t)g], i, t_start, t_lin, t_cone, t_acc, /*grouped=*/true, dev_io);
         }
         active.clear();
         break;
@@ -1203,7 +1204,7 @@ struct GroupSolve {
         if (!ends) continue;
         const int iters = stop[(size_t)g] ? i : i + 1;
         const double tf0 = now_ms();
-        W[(size_t)g]->finish_solve(sols[(size_t)g], infos[(size_t)g], iters, t_start, t_lin, t_cone, t_acc, /*grouped=*/true);
+        W[(size_t)g]->finish_solve(sols[(size_t)g], infos[(size_t)g], iters, t_start, t_lin, t_cone, t_acc, /*grouped=*/true, dev_io);
         t_finish += now_ms() - tf0;
         finished.push_back(g);
       }

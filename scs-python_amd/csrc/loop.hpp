@@ -45,7 +45,8 @@ struct InterruptListener {
   static bool interrupted() { return enabled() && flag().load(std::memory_order_relaxed) != 0; }
 };
 
-static scs_int solve_impl(ScsHipWork *w, ScsSolution *sol, ScsInfo *info, scs_int warm_start) {
+// dev_io: sol holds DEVICE addresses (scs_hip_solve_device; work_solve_ends.inl)
+static scs_int solve_impl(ScsHipWork *w, ScsSolution *sol, ScsInfo *info, scs_int warm_start, bool dev_io = false) {
   std::lock_guard<std::mutex> lock(w->mtx);
   InterruptListener ctrlc;
   HIP_CHECK(hipSetDevice(w->device));
@@ -55,7 +56,7 @@ static scs_int solve_impl(ScsHipWork *w, ScsSolution *sol, ScsInfo *info, scs_in
   hipStream_t s = w->stream;
   w->finish_pending_setup();  // the deferred end of scs_init: counted in setup_time, so the clock of the solve starts behind it
   const double t_start = now_ms();
-  w->begin_solve(sol, info, warm_start);
+  w->begin_solve(sol, info, warm_start, dev_io);
   double t_lin = 0, t_cone = 0, t_acc = 0;
   FILE *csv = nullptr;
   if (!w->log_csv_filename.empty()) {
@@ -179,7 +180,18 @@ static scs_int solve_impl(ScsHipWork *w, ScsSolution *sol, ScsInfo *info, scs_in
     for (int v : w->cg_hist) std::fprintf(stderr, " %d", v);
     std::fprintf(stderr, "\n");
   }
-  w->finish_solve(sol, info, i, t_start, t_lin, t_cone, t_acc);
+  w->finish_solve(sol, info, i, t_start, t_lin, t_cone, t_acc, /*grouped=*/false, dev_io);
+  std::vector<double> foot;  // device endpoints: the footer's diagnostics read host copies of y and s (verbose runs only)
+  ScsSolution foot_sol{nullptr, nullptr, nullptr};
+  if (verbose && dev_io) {
+    foot.resize(2 * (size_t)m);
+    foot_sol.y = foot.data();
+    foot_sol.s = foot.data() + m;
+    w->soly.download(foot_sol.y, m, s);
+    w->sols.download(foot_sol.s, m, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    sol = &foot_sol;
+  }
   if (verbose) {
     std::printf("------------------------------------------------------------------\n");
     std::printf("status:  %s\ntimings: total: %.2es = setup: %.2es + solve: %.2es\n\t lin-sys: %.2es, cones: %.2es, accel: %.2es\n",

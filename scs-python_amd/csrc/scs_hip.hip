@@ -36,6 +36,7 @@
 #include "setup_cs_dev.hpp"
 #include "spmv.hpp"
 #include "vec.hpp"
+#include "device_io.hpp"
 
 #include "runtime.hpp"
 #include "device_csr.hpp"
@@ -115,14 +116,31 @@ ScsWork *scs_hip_clone(ScsWork *w) {
 int scs_hip_shares_matrix(const ScsWork *a, const ScsWork *b) { return a && b && a->mats == b->mats ? 1 : 0; }
 int scs_hip_linsys_kind(const ScsWork *w) { return w ? (w->dense() ? 2 : 1) : 0; }
 
-scs_int scs_solve(ScsWork *w, ScsSolution *sol, ScsInfo *info, scs_int warm_start) {
-  if (!w || !sol || !info) return SCS_FAILED;
+// A vector of a failed solve is NaN: on the host, or — device endpoints — on the device (best effort: the failure may be the device's)
+static void fill_failed(ScsHipWork *w, ScsSolution *sol, bool dev_io) {
+  if (!dev_io) {
+    fill_nan(sol->x, w->n);
+    fill_nan(sol->y, w->m);
+    fill_nan(sol->s, w->m);
+    return;
+  }
+  if (hipSetDevice(w->device) != hipSuccess) return;
+  const double *ptr[3] = {sol->x, sol->y, sol->s};
+  const long len[3] = {w->n, w->m, w->m};
+  for (int k = 0; k < 3; ++k)
+    if (ptr[k]) hipLaunchKernelGGL(k_fill, dim3(vec_blocks(len[k])), dim3(kVecThreads), 0, w->stream, (double *)ptr[k], (double)NAN, len[k]);
+  (void)hipStreamSynchronize(w->stream);
+  (void)hipGetLastError();
+}
+
+// scs_solve and scs_hip_solve_device: one loop, the endpoints on the host or (dev_io) on the device
+static scs_int solve_entry(ScsWork *w, ScsSolution *sol, ScsInfo *info, scs_int warm_start, bool dev_io) {
   try {
     set_last_error("");
     refresh_options();
     const double scale_entry = w->scale;
     try {
-      return solve_impl(w, sol, info, warm_start);
+      return solve_impl(w, sol, info, warm_start, dev_io);
     } catch (const SpinTimeout &) {
       // not a failure of the problem: restart without the spinning kernels (the caller's sol is untouched until a solve finishes)
       ++g_spin_fallbacks;
@@ -131,18 +149,72 @@ scs_int scs_solve(ScsWork *w, ScsSolution *sol, ScsInfo *info, scs_int warm_star
         HIP_CHECK(hipSetDevice(w->device));
         w->spin_fallback(scale_entry);
       }
-      return solve_impl(w, sol, info, warm_start);
+      return solve_impl(w, sol, info, warm_start, dev_io);
     }
   } catch (const std::exception &e) {
     set_last_error(e.what());
     info->status_val = SCS_FAILED;
     std::snprintf(info->status, sizeof(info->status), "failure");
-    fill_nan(sol->x, w->n);
-    fill_nan(sol->y, w->m);
-    fill_nan(sol->s, w->m);
+    fill_failed(w, sol, dev_io);
     return SCS_FAILED;
   }
 }
+
+scs_int scs_solve(ScsWork *w, ScsSolution *sol, ScsInfo *info, scs_int warm_start) {
+  if (!w || !sol || !info) return SCS_FAILED;
+  return solve_entry(w, sol, info, warm_start, /*dev_io=*/false);
+}
+
+// ---- device-resident endpoints (include/scs_hip.h; csrc/device_io.hpp) ----
+// a caller's vector must be device memory of the workspace's device: a host address handed to a kernel is a GPU fault, not an error code
+static void check_device_vector(const void *p, int device, const char *who, const char *name) {
+  hipPointerAttribute_t a;
+  std::memset(&a, 0, sizeof(a));
+  const hipError_t e = hipPointerGetAttributes(&a, p);
+  if (e != hipSuccess) (void)hipGetLastError();
+  if (e != hipSuccess || a.type != hipMemoryTypeDevice)
+    throw std::runtime_error(std::string(who) + ": " + name + " is not a device address");
+  if (a.device != device)
+    throw std::runtime_error(std::string(who) + ": " + name + " lives on device " + std::to_string(a.device) + ", the workspace on device " +
+                             std::to_string(device));
+}
+static void check_device_solution(const ScsHipWork *w, const double *x, const double *y, const double *s, scs_int warm_start, const char *who) {
+  if (warm_start && (!x || !y || !s)) throw std::runtime_error(std::string(who) + ": a warm start needs x_dev, y_dev and s_dev");
+  if (x) check_device_vector(x, w->device, who, "x_dev");
+  if (y) check_device_vector(y, w->device, who, "y_dev");
+  if (s) check_device_vector(s, w->device, who, "s_dev");
+}
+
+scs_int scs_hip_update_device(ScsWork *w, const scs_float *b_dev, const scs_float *c_dev) {
+  if (!w) return -1;
+  try {
+    set_last_error("");
+    if (b_dev) check_device_vector(b_dev, w->device, "scs_hip_update_device", "b_dev");
+    if (c_dev) check_device_vector(c_dev, w->device, "scs_hip_update_device", "c_dev");
+    std::lock_guard<std::mutex> lock(w->mtx);
+    HIP_CHECK(hipSetDevice(w->device));
+    ScsHipWork::ScratchTurn turn(w);
+    w->update_device(b_dev, c_dev);
+    return 0;
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return -1;
+  }
+}
+
+scs_int scs_hip_solve_device(ScsWork *w, scs_float *x_dev, scs_float *y_dev, scs_float *s_dev, ScsInfo *info, scs_int warm_start) {
+  if (!w || !info) return -1;
+  try {
+    set_last_error("");
+    check_device_solution(w, x_dev, y_dev, s_dev, warm_start, "scs_hip_solve_device");
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return -1;
+  }
+  ScsSolution sol{x_dev, y_dev, s_dev};
+  return solve_entry(w, &sol, info, warm_start, /*dev_io=*/true);
+}
+int scs_hip_work_device(const ScsWork *w) { return w ? w->device : -1; }
 
 // Grouped solve of `count` workspaces (include/scs_hip.h): members that can share launches — same shape, CSR-stream
 // layouts, one-launch cone kernels (GroupSolve::member_ok / same_shape) — advance in lock step through the grouped
@@ -154,10 +226,10 @@ scs_int scs_solve(ScsWork *w, ScsSolution *sol, ScsInfo *info, scs_int warm_star
 // synchronisations issued from several host threads contend inside the HIP runtime, as the one-stream-per-problem
 // mode showed before (profiles/r02_batch_queues.txt) => off by default.
 static scs_int solve_one_group(ScsWork **works, ScsSolution **sols, ScsInfo **infos, const std::vector<int> &idx, scs_int warm_start,
-                               std::string &err) {
+                               std::string &err, bool dev_io) {
   if (idx.size() == 1) {
     const int i = idx[0];
-    const scs_int st = scs_solve(works[i], sols[i], infos[i], warm_start);
+    const scs_int st = solve_entry(works[i], sols[i], infos[i], warm_start, dev_io);
     if (st == SCS_FAILED) { err = scs_hip_last_error(); return -1; }
     return 0;
   }
@@ -180,6 +252,7 @@ static scs_int solve_one_group(ScsWork **works, ScsSolution **sols, ScsInfo **in
     }
     HIP_CHECK(hipSetDevice(works[idx[0]]->device));
     gs.s = works[idx[0]]->stream;
+    gs.dev_io = dev_io;
     for (int j : idx) {
       gs.W.push_back(works[j]); gs.sols.push_back(sols[j]); gs.infos.push_back(infos[j]);
       saved.push_back(works[j]->stream);
@@ -196,9 +269,7 @@ static scs_int solve_one_group(ScsWork **works, ScsSolution **sols, ScsInfo **in
       if (infos[j]->status[0] == 0) {  // (finish_solve writes the status string: empty = this member never got there)
         infos[j]->status_val = SCS_FAILED;
         std::snprintf(infos[j]->status, sizeof(infos[j]->status), "failure");
-        fill_nan(sols[j]->x, works[j]->n);
-        fill_nan(sols[j]->y, works[j]->m);
-        fill_nan(sols[j]->s, works[j]->m);
+        fill_failed(works[j], sols[j], dev_io);
       }
   }
   for (size_t k = 0; k < saved.size(); ++k) {
@@ -255,15 +326,9 @@ int scs_hip_batch_plan(ScsWork **works, scs_int count, scs_int *group_of) {
   return groups;
 }
 
-scs_int scs_hip_solve_batch(ScsWork **works, ScsSolution **sols, ScsInfo **infos, scs_int count, scs_int warm_start) {
-  if (!works || !sols || !infos || count < 0) return -1;
-  set_last_error("");
+// scs_hip_solve_batch and scs_hip_solve_batch_device: the same jobs, the endpoints on the host or (dev_io) on the device
+static scs_int solve_batch_entry(ScsWork **works, ScsSolution **sols, ScsInfo **infos, scs_int count, scs_int warm_start, bool dev_io) {
   InterruptListener ctrlc;  // for the whole call: members solved one after the other all see the same Ctrl-C
-  for (int i = 0; i < count; ++i) {
-    if (!works[i] || !sols[i] || !infos[i]) { set_last_error("scs_hip_solve_batch: null entry"); return -1; }
-    for (int j = 0; j < i; ++j)
-      if (works[j] == works[i]) { set_last_error("scs_hip_solve_batch: a workspace appears twice"); return -1; }
-  }
   refresh_options();
   const int lanes = opts().group_lanes;
   std::vector<std::vector<int>> jobs = plan_batch(works, (int)count);
@@ -280,7 +345,7 @@ scs_int scs_hip_solve_batch(ScsWork **works, ScsSolution **sols, ScsInfo **infos
       const size_t j = next.fetch_add(1);
       if (j >= jobs.size()) break;
       std::string err;
-      if (solve_one_group(works, sols, infos, jobs[j], warm_start, err) != 0) {
+      if (solve_one_group(works, sols, infos, jobs[j], warm_start, err, dev_io) != 0) {
         rc_all.store(-1);
         std::lock_guard<std::mutex> g(err_mtx);
         if (first_err.empty()) first_err = err;
@@ -298,6 +363,40 @@ scs_int scs_hip_solve_batch(ScsWork **works, ScsSolution **sols, ScsInfo **infos
   return rc_all.load();
 }
 
+scs_int scs_hip_solve_batch(ScsWork **works, ScsSolution **sols, ScsInfo **infos, scs_int count, scs_int warm_start) {
+  if (!works || !sols || !infos || count < 0) return -1;
+  set_last_error("");
+  for (int i = 0; i < count; ++i) {
+    if (!works[i] || !sols[i] || !infos[i]) { set_last_error("scs_hip_solve_batch: null entry"); return -1; }
+    for (int j = 0; j < i; ++j)
+      if (works[j] == works[i]) { set_last_error("scs_hip_solve_batch: a workspace appears twice"); return -1; }
+  }
+  return solve_batch_entry(works, sols, infos, count, warm_start, /*dev_io=*/false);
+}
+
+scs_int scs_hip_solve_batch_device(ScsWork **works, scs_float **x_dev, scs_float **y_dev, scs_float **s_dev, ScsInfo **infos, scs_int count,
+                                   scs_int warm_start) {
+  if (!works || !infos || count < 0) return -1;
+  set_last_error("");
+  std::vector<ScsSolution> sols((size_t)count);
+  std::vector<ScsSolution *> solp((size_t)count);
+  try {
+    if (warm_start && (!x_dev || !y_dev || !s_dev)) throw std::runtime_error("scs_hip_solve_batch_device: a warm start needs x_dev, y_dev and s_dev");
+    for (int i = 0; i < count; ++i) {
+      if (!works[i] || !infos[i]) throw std::runtime_error("scs_hip_solve_batch_device: null entry");
+      for (int j = 0; j < i; ++j)
+        if (works[j] == works[i]) throw std::runtime_error("scs_hip_solve_batch_device: a workspace appears twice");
+      sols[(size_t)i] = ScsSolution{x_dev ? x_dev[i] : nullptr, y_dev ? y_dev[i] : nullptr, s_dev ? s_dev[i] : nullptr};
+      solp[(size_t)i] = &sols[(size_t)i];
+      check_device_solution(works[i], sols[(size_t)i].x, sols[(size_t)i].y, sols[(size_t)i].s, warm_start, "scs_hip_solve_batch_device");
+    }
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return -1;
+  }
+  return solve_batch_entry(works, solp.data(), infos, count, warm_start, /*dev_io=*/true);
+}
+
 scs_int scs_update(ScsWork *w, scs_float *b, scs_float *c) {
   if (!w) return -1;
   try {
@@ -305,8 +404,9 @@ scs_int scs_update(ScsWork *w, scs_float *b, scs_float *c) {
     HIP_CHECK(hipSetDevice(w->device));
     ScsHipWork::ScratchTurn turn(w);
     const int n = w->n, m = w->m;
-    if (b) w->b_orig.assign(b, b + m);
-    if (c) w->c_orig.assign(c, c + n);
+    if ((!b && w->b_host_stale) || (!c && w->c_host_stale)) w->refresh_host_bc(!b, !c);  // (a kept vector that a device update replaced)
+    if (b) { w->b_orig.assign(b, b + m); w->b_host_stale = false; w->b_raw_fresh = false; }
+    if (c) { w->c_orig.assign(c, c + n); w->c_host_stale = false; w->c_raw_fresh = false; }
     w->nm_b_orig = w->nm_c_orig = 0;
     for (double x : w->b_orig) w->nm_b_orig = std::max(w->nm_b_orig, std::fabs(x));
     for (double x : w->c_orig) w->nm_c_orig = std::max(w->nm_c_orig, std::fabs(x));

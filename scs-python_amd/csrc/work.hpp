@@ -113,6 +113,12 @@ struct ScsHipWork {
   DevBuf<int> fl;
   DevBuf<double> solx, soly, sols;
   bool sol_on_device = false;  // solx/soly/sols hold the final (x, y, s) of the last solve
+  // device-resident endpoints (device_io.hpp, scs_hip_update_device): the caller's b / c as they arrived, allocated by the first device
+  // update.  A vector lives where it was last written: *_raw_fresh = the device copy is current, *_host_stale = b_orig / c_orig is not
+  // (scs_update with one NULL argument refreshes the mirror it keeps: refresh_host_bc)
+  DevBuf<double> b_raw, c_raw;
+  DevBuf<unsigned> io_ticket;  // k_bc_load's arrival counter (0 between launches)
+  bool b_raw_fresh = false, c_raw_fresh = false, b_host_stale = false, c_host_stale = false;
   // large solutions leave through a pinned mirror owned by the workspace (the caller's arrays are never handed to the runtime,
   // see scs_hip_runtime_env): three DMA copies in flight, each array moved on by a few host threads as soon as it has landed
   double *sol_pin = nullptr;

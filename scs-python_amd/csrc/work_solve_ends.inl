@@ -1,7 +1,8 @@
 // work_solve_ends.inl — members of ScsHipWork (work.hpp): the two ends of a solve (begin_solve / finish_solve), shared by scs_solve and the grouped solve (batch.hpp)
   // ---- the two ends of a solve, shared by scs_solve and the grouped solve (batch.hpp) ----
   // per-solve state, info header and the initial iterate (cold: v = [0; 0; 1]; warm: from sol)
-  void begin_solve(ScsSolution *sol, ScsInfo *info, int warm_start) {
+  // dev_io: sol holds DEVICE addresses (scs_hip_solve_device): the warm start is built by k_warm_v, the solution handed over on the device
+  void begin_solve(ScsSolution *sol, ScsInfo *info, int warm_start, bool dev_io = false) {
     std::memset(info, 0, sizeof(*info));
     info->setup_time = setup_time;
     if (dense())
@@ -30,7 +31,11 @@
     // ---- initial iterate ----
     {
       const double one = 1.0;
-      if (warm_start) {
+      if (warm_start && dev_io) {  // the same v from device x, y, s (device_io.hpp k_warm_v: the expressions of the host loop below)
+        hipLaunchKernelGGL(k_warm_v, dim3(vb(l)), dim3(kVecThreads), 0, stream, (const double *)sol->x, (const double *)sol->y,
+                           (const double *)sol->s, normalized ? D.p : (const double *)nullptr, normalized ? E.p : (const double *)nullptr,
+                           normalized ? scal.sigma : 1.0, 1.0 / (1000. * scale), 1.0 / scale, cone.z, n, m, v.p);
+      } else if (warm_start) {
         // v = [x_hat; y_hat + s_hat / r_y; 1] with the normalised warm start (boundary work, O(l) on the host)
         std::vector<double> v0(l, 0.0);
         const double sg = normalized ? scal.sigma : 1.0;
@@ -60,7 +65,7 @@
   // status, un-normalised (x, y, s) on the device and on the host, info; i = iterations done.  info->status_val holds
   // the verdict of the last convergence check (SCS_UNFINISHED: none fired).
   void finish_solve(ScsSolution *sol, ScsInfo *info, int i, double t_start, double t_lin, double t_cone, double t_acc,
-                    bool grouped = false) {
+                    bool grouped = false, bool dev_io = false) {
     // ---- finalize ----
     const int max_iters = stgs.max_iters;
     if (!grouped) {  // (the grouped solve has read this problem's flags and residuals already)
@@ -130,7 +135,8 @@
     hipLaunchKernelGGL(k_scale3, dim3(vb((long)n + m)), dim3(kVecThreads), 0, stream, solx.p, soly.p, sols.p, n, m, fx, fy, fs);
     // (nothing is left running when scs_solve returns: a device-wide synchronize issued by the caller right after an
     // un-synchronised kernel was measured to take 25 ms on this runtime)
-    download_solution(sol);
+    if (dev_io) hand_over_solution(sol);
+    else download_solution(sol);
     sol_on_device = true;
     {
       double cs = 0.;
@@ -143,4 +149,52 @@
     info->cg_iters = (scs_int)tot_cg_iters;
     info->aa_stats = aa.st;
     info->solve_time = now_ms() - t_start;
+  }
+
+  // ---- device-resident endpoints (device_io.hpp) ----
+  // the finished (x, y, s) to the caller's DEVICE vectors (a NULL pointer skips one); the stream is drained on return, as after download_solution
+  void hand_over_solution(ScsSolution *sol) {
+    if (sol->x) HIP_CHECK(hipMemcpyAsync(sol->x, solx.p, sizeof(double) * n, hipMemcpyDeviceToDevice, stream));
+    if (sol->y) HIP_CHECK(hipMemcpyAsync(sol->y, soly.p, sizeof(double) * m, hipMemcpyDeviceToDevice, stream));
+    if (sol->s) HIP_CHECK(hipMemcpyAsync(sol->s, sols.p, sizeof(double) * m, hipMemcpyDeviceToDevice, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+  }
+  // scs_update with one NULL argument keeps a vector a device update may have replaced since: bring that host mirror up to date
+  void refresh_host_bc(bool need_b, bool need_c) {
+    if (need_b && b_host_stale) b_raw.download(b_orig.data(), m, stream);
+    if (need_c && c_host_stale) c_raw.download(c_orig.data(), n, stream);
+    HIP_CHECK(hipStreamSynchronize(stream));
+    if (need_b) b_host_stale = false;
+    if (need_c) c_host_stale = false;
+  }
+  // The device twin of scs_update (csrc/scs_hip.hip): b_dev (m) / c_dev (n) are device vectors, NULL = keep.  h, Dinv / Einv and sigma are
+  // formed on the device; what comes back to the host is three doubles (max |b|, max |c|, sigma: the residual tests and the
+  // un-normalisation of the host side read them).  The caller holds mtx and the scratch turn, as in scs_update.
+  void update_device(const double *b_dev, const double *c_dev) {
+    if (!b_raw.p) {  // first device update of this workspace (outside the arena: exact-size blocks, returned through the pool)
+      b_raw.alloc(m);
+      c_raw.alloc(n);
+      io_ticket.alloc_zero(1, stream);
+    }
+    // a kept vector that only the host has seen so far (scs_init, scs_update) goes up once
+    if (!b_dev && !b_raw_fresh) b_raw.upload(b_orig.data(), m, stream);
+    if (!c_dev && !c_raw_fresh) c_raw.upload(c_orig.data(), n, stream);
+    const int nb = vb((long)n + m);
+    hipLaunchKernelGGL(k_bc_load, dim3(nb), dim3(kVecThreads), 0, stream, b_dev ? b_dev : (const double *)b_raw.p,
+                       c_dev ? c_dev : (const double *)c_raw.p, b_raw.p, c_raw.p, normalized ? D.p : (const double *)nullptr,
+                       normalized ? E.p : (const double *)nullptr, n, m, h.p, part.p, sc.p, io_ticket.p);
+    if (normalized)
+      hipLaunchKernelGGL(k_bc_finish, dim3(nb), dim3(kVecThreads), 0, stream, h.p, (const double *)D.p, (const double *)E.p, Dinv.p, Einv.p,
+                         n, m, (const double *)sc.p);
+    HIP_CHECK(hipMemcpyAsync(h_pin, sc.p + S_NM_B, sizeof(double) * 3, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    b_raw_fresh = c_raw_fresh = true;
+    if (b_dev) b_host_stale = true;
+    if (c_dev) c_host_stale = true;
+    nm_b_orig = h_pin[0];
+    nm_c_orig = h_pin[1];
+    if (normalized) scal.sigma = h_pin[2];
+    if (setup_pending) finish_pending_setup();  // (a workspace that has not solved yet: R, the preconditioner or G^{-1}, and g in one go)
+    else update_work_cache();
+    HIP_CHECK(hipStreamSynchronize(stream));
   }

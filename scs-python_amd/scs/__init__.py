@@ -227,6 +227,21 @@ class SCS(object):
     (or from the rows of x, y, s)."""
     return self._solver.solve_many(b, c, warm_start, x, y, s)
 
+  def update_device(self, b=None, c=None):
+    """`update` for b / c that already live on the solver's GPU: float64, 1-D, contiguous torch tensors (None = keep).  No vector
+    crosses the host.  The tensors must be complete on torch's current stream (the call synchronises it)."""
+    self._solver.update_device(b, c)
+
+  def solve_device(self, warm_start=False, x=None, y=None, s=None):
+    """`solve` whose warm start and solution stay on the GPU: x, y, s are torch tensors (an omitted one = the previous solution),
+    the result's "x", "y", "s" are fresh float64 device tensors; "info" as `solve()`."""
+    return self._solver.solve_device(warm_start, x, y, s)
+
+  def solve_many_device(self, b=None, c=None, warm_start=False, x=None, y=None, s=None):
+    """`solve_many` over device tensors b (K, m), c (K, n) and warm starts (K, .): one grouped solve that writes into the rows of
+    {"x": (K, n), "y": (K, m), "s": (K, m)} on the GPU; "info" is the list of K info dicts."""
+    return self._solver.solve_many_device(b, c, warm_start, x, y, s)
+
 
 def solve(data, cone, **settings):
   """Legacy one-shot API; warm-start vectors may ride along in `data`."""

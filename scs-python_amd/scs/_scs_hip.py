@@ -205,6 +205,15 @@ def _load():
     lib.scs_hip_kernel_times.argtypes = [C.c_void_p, _PD]
     lib.scs_hip_solution_to_device.restype = c_int
     lib.scs_hip_solution_to_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.scs_hip_update_device.restype = c_int
+    lib.scs_hip_update_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.scs_hip_solve_device.restype = c_int
+    lib.scs_hip_solve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_ScsInfo), c_int]
+    lib.scs_hip_solve_batch_device.restype = c_int
+    lib.scs_hip_solve_batch_device.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                               C.POINTER(C.POINTER(_ScsInfo)), c_int, c_int]
+    lib.scs_hip_work_device.restype = c_int
+    lib.scs_hip_work_device.argtypes = [C.c_void_p]
     lib.scs_hip_set_mark.restype = None
     lib.scs_hip_set_mark.argtypes = [C.c_void_p, c_int]
     lib.scs_hip_get_mark.restype = None
@@ -714,6 +723,122 @@ class SCS(object):
                             sv._warm(name, dst, rows[name][i])
         return solve_batch(members, bool(warm_start))
 
+    # ------------------------------------------ device-resident endpoints (torch tensors; include/scs_hip.h)
+    def _device_index(self):
+        if not self._work:
+            raise ValueError("Workspace not initialized!")
+        return int(_lib.scs_hip_work_device(self._work))
+
+    def update_device(self, b=None, c=None):
+        """`update` for b (m) / c (n) that live on the workspace's GPU: float64, 1-D, contiguous torch tensors, None = keep.  Nothing of
+        length n or m crosses the host; a following solve gives the bits `update` with the same values would give."""
+        dev = self._device_index()
+        bp = _device_vec("b_new", b, self.m, dev) if b is not None else None
+        cp = _device_vec("c_new", c, self.n, dev) if c is not None else None
+        _sync_torch_stream(dev)  # the stream contract: inputs complete before the library's own stream reads them
+        with self._lock:
+            if not self._work:
+                raise ValueError("Workspace not initialized!")
+            rc = _lib.scs_hip_update_device(self._work, bp, cp)
+        if rc != 0:
+            raise RuntimeError("libscs_hip: " + last_error())
+        return None
+
+    def _previous_to_device(self, ptrs):
+        """the workspace's last solution into the device vectors {name: address} (zeros before the first solve); lock held"""
+        got = _lib.scs_hip_solution_to_device(self._work, ptrs.get("x"), ptrs.get("y"), ptrs.get("s")) == 0
+        return got
+
+    def solve_device(self, warm_start=False, x=None, y=None, s=None):
+        """`solve` with the endpoints on the device: returns {"x", "y", "s", "info"} with three fresh float64 torch tensors on the
+        workspace's GPU.  warm_start=True starts from the device tensors x / y / s; an omitted one starts from this solver's previous
+        solution as it lies on the device (zeros before the first solve)."""
+        if not isinstance(warm_start, (bool, np.bool_)):
+            raise TypeError("argument 1 must be bool, not %s" % type(warm_start).__name__)
+        dev = self._device_index()
+        given = {}
+        if warm_start:
+            for name, t, length in (("x", x, self.n), ("y", y, self.m), ("s", s, self.m)):
+                if t is not None:
+                    _device_vec(name, t, length, dev)
+                    given[name] = t
+        import torch
+        tdev = torch.device("cuda", dev)
+        out = {"x": torch.empty(self.n, dtype=torch.float64, device=tdev), "y": torch.empty(self.m, dtype=torch.float64, device=tdev),
+               "s": torch.empty(self.m, dtype=torch.float64, device=tdev)}
+        with self._lock:
+            if not self._work:
+                raise ValueError("Workspace not initialized!")
+            if warm_start:
+                for name, t in given.items():
+                    out[name].copy_(t)
+                missing = {name: out[name].data_ptr() for name in out if name not in given}
+                if missing:
+                    for name in missing:
+                        out[name].zero_()
+                    _sync_torch_stream(dev)
+                    self._previous_to_device(missing)
+            _sync_torch_stream(dev)
+            info = _ScsInfo()
+            rc = _lib.scs_hip_solve_device(self._work, out["x"].data_ptr(), out["y"].data_ptr(), out["s"].data_ptr(), C.byref(info),
+                                           1 if warm_start else 0)
+            err = last_error() if rc == -1 else ""
+        if rc == -1 and info.status_val == 0:  # refused arguments (an unbounded problem also returns -1, with its info filled)
+            raise RuntimeError("libscs_hip: " + err)
+        out["info"] = _info_dict(info)
+        return out
+
+    def solve_many_device(self, b=None, c=None, warm_start=False, x=None, y=None, s=None):
+        """`solve_many` with the endpoints on the device: b (K, m), c (K, n) and the warm starts (K, .) are float64 torch tensors on the
+        workspace's GPU.  Members are this solver and its cached clones; each is `update_device`d from its row, then ONE grouped solve
+        writes straight into the rows of the result: {"x": (K, n), "y": (K, m), "s": (K, m), "info": [K dicts]}."""
+        dev = self._device_index()
+        K, rows = _many_device_args(self.m, self.n, dev, b, c, warm_start, x, y, s)
+        pool = self._many
+        while len(pool) < K - 1:
+            pool.append(self.clone())
+        members = [self] + pool[:K - 1]
+        for i, sv in enumerate(members):
+            bi, ci = rows["b"][i] if b is not None else None, rows["c"][i] if c is not None else None
+            if bi is not None or ci is not None:
+                sv.update_device(bi, ci)
+        import torch
+        tdev = torch.device("cuda", dev)
+        out = {"x": torch.empty((K, self.n), dtype=torch.float64, device=tdev), "y": torch.empty((K, self.m), dtype=torch.float64, device=tdev),
+               "s": torch.empty((K, self.m), dtype=torch.float64, device=tdev)}
+        ordered = sorted(members, key=id)  # the lock order of solve_batch
+        for sv in ordered:
+            sv._lock.acquire()
+        try:
+            for sv in members:
+                if not sv._work:
+                    raise ValueError("Workspace not initialized!")
+            if warm_start:
+                missing = [name for name in ("x", "y", "s") if rows[name] is None]
+                for name in ("x", "y", "s"):
+                    if rows[name] is not None:
+                        out[name].copy_(rows[name])
+                    else:
+                        out[name].zero_()
+                _sync_torch_stream(dev)
+                if missing:
+                    for i, sv in enumerate(members):
+                        sv._previous_to_device({name: out[name][i].data_ptr() for name in missing})
+            _sync_torch_stream(dev)
+            infos = [_ScsInfo() for _ in members]
+            works = (C.c_void_p * K)(*[sv._work for sv in members])
+            ptrs = {name: (C.c_void_p * K)(*[out[name][i].data_ptr() for i in range(K)]) for name in ("x", "y", "s")}
+            infp = (C.POINTER(_ScsInfo) * K)(*[C.pointer(io) for io in infos])
+            rc = _lib.scs_hip_solve_batch_device(works, ptrs["x"], ptrs["y"], ptrs["s"], infp, K, 1 if warm_start else 0)
+            err = last_error() if rc != 0 else ""
+        finally:
+            for sv in ordered:
+                sv._lock.release()
+        out["info"] = [_info_dict(io) for io in infos]
+        if rc != 0 and any(o["status_val"] == 0 for o in out["info"]):  # (as solve_batch: only a call that failed as a whole raises)
+            raise RuntimeError("libscs_hip: " + err)
+        return out
+
     # -------------------------------------------------- bench hooks (not part of the reference surface)
     def _set_profiling(self, on):
         with self._lock:
@@ -780,6 +905,60 @@ class SCS(object):
             with lock:
                 _lib.scs_finish(self._work)
                 self._work = None
+
+
+def _device_vec(name, t, length, device):
+    """The one argument check of the device-resident endpoints, before anything touches the device: `t` must be a float64, 1-D,
+    contiguous torch tensor of `length` elements on GPU `device` (an index); returns its device address.  torch is imported here,
+    not by `import scs`.  (Other device-array objects — DLPack, __cuda_array_interface__ — would be added here.)"""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor on the workspace's GPU, not %s" % (name, type(t).__name__))
+    if t.dtype != torch.float64:
+        raise TypeError("%s must be a float64 tensor, not %s" % (name, t.dtype))
+    if t.dim() != 1 or t.shape[0] != length:
+        raise ValueError("%s must be a 1-D tensor of length %d, not of shape %s" % (name, length, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    if t.device.type != "cuda" or t.device.index != device:
+        raise ValueError("%s must live on the workspace's GPU (cuda:%d), not on %s" % (name, device, t.device))
+    return t.data_ptr()
+
+
+def _sync_torch_stream(device):
+    """Stream contract of the device-resident endpoints (include/scs_hip.h): what torch has queued on its current stream of `device`
+    is complete before the library's own stream reads it."""
+    import torch
+    torch.cuda.current_stream(device).synchronize()
+
+
+def _many_device_args(m, n, device, b, c, warm_start, x, y, s):
+    """Argument checks of SCS.solve_many_device, before anything touches the device: (K, {name: (K, .) tensor or None}); every row goes
+    through `_device_vec`."""
+    if not isinstance(warm_start, (bool, np.bool_)):
+        raise TypeError("argument 1 must be bool, not %s" % type(warm_start).__name__)
+    rows = {"b": None, "c": None, "x": None, "y": None, "s": None}
+    K = None
+    for name, t, width, used in (("c", c, n, True), ("b", b, m, True), ("x", x, n, warm_start), ("y", y, m, warm_start),
+                                 ("s", s, m, warm_start)):
+        if t is None or not used:
+            continue
+        label = name + "_new" if name in ("b", "c") else name
+        if not hasattr(t, "dim"):
+            _device_vec(label, t, width, device)  # (not a tensor: its TypeError)
+        if t.dim() != 2:
+            raise ValueError("%s must be a 2-D tensor, one row per problem" % label)
+        if K is not None and t.shape[0] != K:
+            raise ValueError("%s must have one row per problem (%d), not %d" % (label, K, t.shape[0]))
+        K = t.shape[0]
+        if K < 1:
+            raise ValueError("solve_many_device needs at least one problem")
+        for i in range(K):
+            _device_vec(label, t[i], width, device)
+        rows[name] = t
+    if K is None:
+        K = 1
+    return K, rows
 
 
 def _many_args(m, n, b, c, warm_start, x, y, s):
