@@ -163,6 +163,33 @@ SCS_HIP_API scs_int scs_hip_update_device(ScsWork *w, const scs_float *b_dev, co
 SCS_HIP_API scs_int scs_hip_solve_device(ScsWork *w, scs_float *x_dev, scs_float *y_dev, scs_float *s_dev, ScsInfo *info, scs_int warm_start);
 SCS_HIP_API scs_int scs_hip_solve_batch_device(ScsWork **w, scs_float **x_dev, scs_float **y_dev, scs_float **s_dev, ScsInfo **info,
                                                scs_int count, scs_int warm_start);
+/* Matrix values: new VALUES of A and / or P on the sparsity pattern scs_init was given (a re-linearised model, a time-varying cost),
+ * written into every resident layout instead of a new scs_init.  Ax holds nnz(A) and Px nnz(P) doubles in the order of the CSC arrays
+ * scs_init got (P: the upper triangle as passed; explicit zeros are values); NULL keeps that matrix, both NULL is a no-op returning 0.
+ * scs_hip_update_matrix takes HOST pointers, scs_hip_update_matrix_device DEVICE pointers of the workspace's device (the stream contract
+ * of the device endpoints above: inputs complete on entry, the library drains its stream before it returns); the host entry stages its
+ * values into a device buffer and runs the same path.
+ *
+ * CONTRACT.  Afterwards the workspace is in the state scs_init would leave a NEW workspace in, given the new values on the old pattern,
+ * the workspace's CURRENT b and c (after any scs_update / scs_hip_update_device), and the same cone, settings, linear solver and
+ * environment: cold iterate, empty Anderson history, scale = settings.scale, fresh D, E, sigma, box bounds rescaled from the caller's,
+ * diag(P), R and the preconditioner or G^-1, g (deferred where scs_init defers them).  A following solve returns the x, y, s, iteration
+ * and CG-step counts of that new workspace bit for bit.  A warm start is what the caller passes to the solve.  What a LATER
+ * scs_hip_clone starts from (the b, c scs_init was given) is unchanged; the clone shares the updated matrices.
+ *
+ * Returns 0, or -1 with the reason in scs_hip_last_error.  Refused before any device work, the workspace unchanged and usable: a NULL
+ * workspace; Px for a workspace created without P; (device entry) a pointer that is not device memory of the workspace's device;
+ * a matrix set other workspaces share (live clones — it is read-only for them; the message names the count); a workspace whose P
+ * scs_init got with entries below the diagonal or with row indices that do not ascend inside a column (scs_init accepts both; the
+ * value order of the triangle cannot be mapped onto the full matrix then).
+ * One refusal comes AFTER device work, at the first call only: a value map that does not reproduce, bit for bit, the values a resident
+ * layout holds (the map kernels, scans and a check pass have run by then; no matrix value has been written, the maps are released,
+ * the workspace is unchanged and usable).  It guards layouts whose placement the map builder cannot re-derive.
+ *
+ * The first call builds one int32 source index per stored value slot of every resident form except CSR(A') (csrc/matrix_update.hpp;
+ * 4 bytes per slot, INTEGRATION.md has the total); later calls allocate nothing new (temporaries come back from the block pool). */
+SCS_HIP_API scs_int scs_hip_update_matrix(ScsWork *w, const scs_float *Ax, const scs_float *Px);
+SCS_HIP_API scs_int scs_hip_update_matrix_device(ScsWork *w, const scs_float *Ax_dev, const scs_float *Px_dev);
 /* the HIP device a workspace lives on (-1: NULL) */
 SCS_HIP_API int scs_hip_work_device(const ScsWork *w);
 

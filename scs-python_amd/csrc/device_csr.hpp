@@ -18,6 +18,7 @@ struct DeviceCsr {
   DevBuf<unsigned short> s_roff;
   DevBuf<double> s_val;
   int s_nchunks = 0, s_S = 0, s_R = 0, s_max_seg = 0;
+  int s_shift = 0;  // log2 of the slab width the copy was built with (matrix_update.hpp re-derives the value map from it)
   // optional column-sorted pass copy (spmv_cs.hpp); preferred over the slab copy when both could be built
   DeviceCs cs;
   static bool cs_enabled() { return opts().cs; }  // SCS_HIP_CS=0: keep the slab kernel (A/B measurements)
@@ -26,6 +27,7 @@ struct DeviceCsr {
   DevBuf<int4> peel_blk;
   int npeel = 0, npeel_long = 0;
   long peel_nnz = 0;  // nonzeros in the peeled rows
+  int cs_virt_lp = 0;  // piece length the virtual-row layout was accepted with (0: no virtual rows); matrix_update.hpp re-plans with it
   // host: mark rows longer than `thresh`; one row block {row, row + 1, first nonzero, end} each.  false: nothing to peel
   bool make_peel(const int *rp_host, int thresh, hipStream_t s) {
     peel_mask.release(); peel_blk.release(); npeel = 0; npeel_long = 0; peel_nnz = 0;
@@ -88,6 +90,7 @@ struct DeviceCsr {
                    rows, cols, std::max(lp, peel_threshold(1)), lp, npeel, peel_nnz, (long)nnz, P.V, P.Rr, P.Rp, P.rpt, built ? "built" : "a count field overflowed");
     if (!built) { clear_peel(); return false; }
     adopt_virtual(P, s);
+    cs_virt_lp = lp;
     return true;
   }
   bool build_virtual_host(const int *rp, const int *ci, const double *v, int lp, hipStream_t s, HostCs &h) {
@@ -95,6 +98,7 @@ struct DeviceCsr {
     if (!plan_virtual(rp, lp, P, s)) return false;
     if (!build_cs_virtual(rp, ci, v, rows, cols, P, h)) { clear_peel(); return false; }
     virt_host_plan = P;
+    cs_virt_lp = lp;
     return true;
   }
   VirtPlan virt_host_plan;
@@ -189,7 +193,7 @@ struct DeviceCsr {
     cs_after_build(s);
     return ok;
   }
-  void clear_peel() { peel_mask.release(); peel_blk.release(); npeel = 0; npeel_long = 0; peel_nnz = 0; }
+  void clear_peel() { peel_mask.release(); peel_blk.release(); npeel = 0; npeel_long = 0; peel_nnz = 0; cs_virt_lp = 0; }
   bool build_cs_host(const int *rp, const int *ci, const double *v, hipStream_t s, int kind) {
     cs.release();
     peel_mask.release(); peel_blk.release(); npeel = 0; npeel_long = 0;
@@ -249,7 +253,7 @@ struct DeviceCsr {
           s_roff.upload(hs.roff.data(), hs.roff.size(), s);
           s_col.upload(hs.col.data(), hs.col.size(), s);
           s_val.upload(hs.val.data(), hs.val.size(), s);
-          s_nchunks = hs.nchunks; s_S = hs.S; s_R = hs.R; s_max_seg = hs.max_seg;
+          s_nchunks = hs.nchunks; s_S = hs.S; s_R = hs.R; s_max_seg = hs.max_seg; s_shift = slab_shift();
           has_slab = true;
           HIP_CHECK(hipStreamSynchronize(s));  // hs is a local
         }
@@ -332,8 +336,38 @@ struct DeviceCsr {
                        s_col.p, s_val.p);
     hipLaunchKernelGGL(k_slab_pad, dim3(vec_blocks(nseg)), dim3(kVecThreads), 0, s, g, s_roff.p, s_segptr.p, s_col.p, s_val.p);
     HIP_CHECK(hipStreamSynchronize(s));
-    s_nchunks = g.nchunks; s_S = g.S; s_R = g.R; s_max_seg = max_seg;
+    s_nchunks = g.nchunks; s_S = g.S; s_R = g.R; s_max_seg = max_seg; s_shift = g.shift;
     has_slab = true;
+  }
+  // ---- value maps of the EXISTING layout copies (matrix_update.hpp): where every stored value slot takes its value from ----
+  // pass layout: positions in T.val (T = the CSR the layout was built from), through the builder re-run in map-only mode with the
+  // layout's own geometry — the resident peel mask, or the row slots of the virtual rows re-planned with the accepted piece length
+  bool build_cs_value_map(const DeviceCsr &T, hipStream_t s, DevBuf<int> &map) const {
+    if (!cs.ok) return false;
+    if (cs_virt_lp <= 0) return cs.build_value_map(T.rowptr.p, T.col.p, nnz, s, npeel > 0 ? peel_mask.p : nullptr, map);
+    std::vector<int> rp((size_t)rows + 1);
+    rowptr.download(rp.data(), rp.size(), s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    VirtPlan P;
+    if (!cs_plan_virtual(rp.data(), rows, cs_virt_lp, std::max(cs_virt_lp, peel_threshold(1)), P)) return false;
+    if (P.R != cs.R || P.rpt != cs.rpt || P.nchunks != cs.nchunks || P.Rr != cs.Rr || P.Rp != cs.Rp || P.V != cs.npieces) return false;
+    DevBuf<int2> d_info;
+    DevBuf<int> vslot;
+    d_info.upload(P.rowinfo.data(), P.rowinfo.size(), s);
+    vslot.alloc((size_t)nnz);
+    hipLaunchKernelGGL(k_cs_vslot, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, T.rowptr.p, T.col.p, cols, (long)nnz, rowptr.p, col.p,
+                       d_info.p, P.Rr, P.Rp, P.R, vslot.p);
+    HIP_CHECK(hipStreamSynchronize(s));  // (P.rowinfo is read by the upload)
+    return cs.build_value_map(T.rowptr.p, vslot.p, nnz, s, nullptr, map);  // (synchronises: vslot is a local)
+  }
+  // slab copy: positions in this matrix's own CSR values, through the resident row offsets and segment pointers
+  void build_slab_value_map(hipStream_t s, DevBuf<int> &map) const {
+    map.alloc(s_val.n);
+    HIP_CHECK(hipMemsetAsync(map.p, 0xFF, sizeof(int) * std::max<size_t>(s_val.n, 1), s));  // -1: padding
+    SlabGeom g;
+    g.rows = rows; g.cols = cols; g.R = s_R; g.shift = s_shift; g.S = s_S; g.nchunks = s_nchunks;
+    hipLaunchKernelGGL(k_slab_fill_map, dim3(vec_blocks(rows)), dim3(kVecThreads), 0, s, rowptr.p, col.p, g, s_roff.p, s_segptr.p, map.p);
+    HIP_CHECK(hipStreamSynchronize(s));
   }
   SpmvMat view() const {
     SpmvMat M;

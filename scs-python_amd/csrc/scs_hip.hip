@@ -45,6 +45,7 @@
 #include "setup.hpp"
 #include "loop.hpp"
 #include "batch.hpp"
+#include "matrix_update.hpp"
 
 // ================================================================ C ABI
 // A consumer compiled without USE_SPECTRAL_CONES hands over a ScsCone that ends at psize: the plain entry points copy that
@@ -432,6 +433,44 @@ scs_int scs_update(ScsWork *w, scs_float *b, scs_float *c) {
     set_last_error(e.what());
     return -1;
   }
+}
+
+// ---- matrix values on the resident layouts (include/scs_hip.h; csrc/matrix_update.hpp) ----
+// every refusal of an ARGUMENT comes before device work; all leave the workspace as it was (a value map that does not reproduce a
+// resident layout is found by device work, at the first call: matrix_update.hpp build_value_maps)
+static scs_int update_matrix_entry(ScsWork *w, const scs_float *Ax, const scs_float *Px, bool dev, const char *who) {
+  if (!w) {
+    set_last_error(std::string(who) + ": null workspace");
+    return -1;
+  }
+  try {
+    set_last_error("");
+    if (!Ax && !Px) return 0;
+    if (Px && !w->has_P) throw std::runtime_error(std::string(who) + ": values of P for a workspace created without P");
+    // (Ax alone too: the first call maps every resident form, and with `normalize` new values of A re-equilibrate P from its raw values)
+    if (w->has_P && !w->mats->p_update_refusal.empty()) throw std::runtime_error(std::string(who) + ": " + w->mats->p_update_refusal);
+    if (dev) {
+      if (Ax) check_device_vector(Ax, w->device, who, "Ax_dev");
+      if (Px) check_device_vector(Px, w->device, who, "Px_dev");
+    }
+    std::lock_guard<std::mutex> lock(w->mtx);
+    if (w->mats.use_count() > 1)
+      throw std::runtime_error(std::string(who) + ": the matrix set is shared by " + std::to_string(w->mats.use_count()) +
+                               " workspaces (live clones read it): finish the clones first");
+    HIP_CHECK(hipSetDevice(w->device));
+    ScsHipWork::ScratchTurn turn(w);
+    update_matrix_impl(w, Ax, Px, dev);
+    return 0;
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return -1;
+  }
+}
+scs_int scs_hip_update_matrix(ScsWork *w, const scs_float *Ax, const scs_float *Px) {
+  return update_matrix_entry(w, Ax, Px, /*dev=*/false, "scs_hip_update_matrix");
+}
+scs_int scs_hip_update_matrix_device(ScsWork *w, const scs_float *Ax_dev, const scs_float *Px_dev) {
+  return update_matrix_entry(w, Ax_dev, Px_dev, /*dev=*/true, "scs_hip_update_matrix_device");
 }
 
 void scs_finish(ScsWork *w) {

@@ -178,8 +178,80 @@ static void init_streams_and_pinned(ScsHipWork *w) {
   for (int i = 0; i < 2; ++i) HIP_CHECK(hipEventCreateWithFlags(&w->ev_iter[i], hipEventDisableTiming));
 }
 
-// Everything of scs_init behind the matrix set: vectors, the scaled b / c, cone metadata, the Anderson workspace and (unless deferred)
-// R, the preconditioner or G^{-1}, and g.  scs_hip_clone runs exactly this on the shared set, from the b, c and settings scs_init got.
+// The host mirrors of D and E and the box bounds that follow the row scaling (bl_j <- bl_j D_{j+1} / D_0, from the CALLER's bounds in the
+// matrix set): behind every device_normalize — scs_init's and scs_hip_update_matrix's
+static void adopt_equilibration(ScsHipWork *w) {
+  hipStream_t s = w->stream;
+  const int n = w->n, m = w->m;
+  w->scal.D.resize(m);
+  w->scal.E.resize(n);
+  w->D.download(w->scal.D.data(), m, s);
+  w->E.download(w->scal.E.data(), n, s);
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (w->cone.bsize > 1) {
+    const double *Db = &w->scal.D[w->cone.off_box];
+    const std::vector<double> &bl0 = w->mats->bl0, &bu0 = w->mats->bu0;
+    for (int j = 0; j < w->cone.bsize - 1; ++j) {
+      w->cone.bu[j] = (bu0[j] >= 1e15) ? INFINITY : Db[j + 1] * bu0[j] / Db[0];
+      w->cone.bl[j] = (bl0[j] <= -1e15) ? -INFINITY : Db[j + 1] * bl0[j] / Db[0];
+    }
+  }
+}
+
+// The part of scs_init's state that is a function of the resident matrices, D / E and the CURRENT b and c: h, sigma, Dinv / Einv, the
+// working box bounds, the box cone's t, an empty Anderson history and (unless deferred) R, the preconditioner or G^{-1}, and g.
+// scs_init, scs_hip_clone (through init_state) and scs_hip_update_matrix all end in this one function.
+template <class Mark>
+static void start_state(ScsHipWork *w, Mark &&mark) {
+  hipStream_t s = w->stream;
+  const int n = w->n, m = w->m;
+  const long l = w->l;
+  {
+    std::vector<double> hh(l, 0.0);
+    std::copy(w->c_orig.begin(), w->c_orig.end(), hh.begin());
+    std::copy(w->b_orig.begin(), w->b_orig.end(), hh.begin() + n);
+    w->h.upload(hh.data(), l, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  if (w->normalized) {
+    w->scal.sigma = device_normalize_b_c(w->h, n, m, w->D, w->E, w->part, w->h_pin, s);
+    std::vector<double> di(m), ei(n);
+    for (int i = 0; i < m; ++i) di[i] = 1.0 / (w->scal.D[i] * w->scal.sigma);
+    for (int i = 0; i < n; ++i) ei[i] = 1.0 / (w->scal.E[i] * w->scal.sigma);
+    w->Dinv.upload(di.data(), m, s);
+    w->Einv.upload(ei.data(), n, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  if (w->cone.bsize > 1) {  // the working bounds (they follow the row scaling: adopt_equilibration)
+    w->box_bl.upload(w->cone.bl.data(), w->cone.bl.size(), s);
+    w->box_bu.upload(w->cone.bu.data(), w->cone.bu.size(), s);
+  }
+  {
+    const double one = 1.0;
+    HIP_CHECK(hipMemcpyAsync(w->sc.p + S_BOX_T, &one, sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  w->aa.reset(); w->aa.success = 0; w->aa.pending_safeguard = false; w->aa.st = ScsAaStats{};
+  mark("b/c scaling, box bounds, AA reset");
+  // ---- R, preconditioner (or G^{-1}), pre-solved g ----
+  {
+    // Round 5, late: the indirect path defers it too (SCS_HIP_LAZY_SETUP=0: inside scs_init) — its cold PCG for g is ~50 steps = 150 dependent
+    // launches, three quarters of the dispatch chain of a small problem's scs_init; a batch runs it as ONE grouped cold solve (batch.hpp
+    // apply_scale_updates, the path of an adaptive-scale update: bit-identical to the solo one), a lone workspace at its first solve.
+    // (small problems only, n + m <= 32768: there the chain is what scs_init costs; a large problem keeps its cold solve out of scs_solve)
+    const bool small_indirect = !w->dense() && (long)n + m <= 32768;
+    w->setup_pending = (w->dense() || small_indirect) && w->mats->lazy_setup;
+  }
+  if (!w->setup_pending) {
+    w->set_diag_r();
+    w->update_work_cache();
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  mark("R, preconditioner, g = KKT^-1 h");
+}
+
+// Everything of scs_init behind the matrix set: vectors, cone metadata, the Anderson workspace (the allocations), then start_state.
+// scs_hip_clone runs exactly this on the shared set, from the b, c and settings scs_init got.
 template <class Mark>
 static void init_state(ScsHipWork *w, Mark &&mark) {
   hipStream_t s = w->stream;
@@ -206,48 +278,13 @@ static void init_state(ScsHipWork *w, Mark &&mark) {
   w->sc.alloc_zero(S_COUNT, s);
   w->out.alloc_zero(256, s);
   w->fl.alloc_zero(F_COUNT, s);
-  {
-    std::vector<double> hh(l, 0.0);
-    std::copy(w->c_orig.begin(), w->c_orig.end(), hh.begin());
-    std::copy(w->b_orig.begin(), w->b_orig.end(), hh.begin() + n);
-    w->h.upload(hh.data(), l, s);
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
-  if (w->normalized) {
-    w->scal.sigma = device_normalize_b_c(w->h, n, m, w->D, w->E, w->part, w->h_pin, s);
-    std::vector<double> di(m), ei(n);
-    for (int i = 0; i < m; ++i) di[i] = 1.0 / (w->scal.D[i] * w->scal.sigma);
-    for (int i = 0; i < n; ++i) ei[i] = 1.0 / (w->scal.E[i] * w->scal.sigma);
-    w->Dinv.upload(di.data(), m, s);
-    w->Einv.upload(ei.data(), n, s);
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
   upload_cone_meta(w);
-  {
-    const double one = 1.0;
-    HIP_CHECK(hipMemcpyAsync(w->sc.p + S_BOX_T, &one, sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
   // ---- AA workspace ----
   w->aa.init(l, w->stgs.acceleration_lookback, w->stgs.acceleration_type_1, w->stgs.acceleration_regularization,
              w->stgs.acceleration_relaxation, /*safeguard_factor=*/1.0, /*max_weight_norm=*/1e10, s);
-  mark("vectors, b/c scaling, cones, AA workspace");
-  // ---- R, preconditioner (or G^{-1}), pre-solved g ----
   if (w->dense()) w->dense_alloc();
-  {
-    // Round 5, late: the indirect path defers it too (SCS_HIP_LAZY_SETUP=0: inside scs_init) — its cold PCG for g is ~50 steps = 150 dependent
-    // launches, three quarters of the dispatch chain of a small problem's scs_init; a batch runs it as ONE grouped cold solve (batch.hpp
-    // apply_scale_updates, the path of an adaptive-scale update: bit-identical to the solo one), a lone workspace at its first solve.
-    // (small problems only, n + m <= 32768: there the chain is what scs_init costs; a large problem keeps its cold solve out of scs_solve)
-    const bool small_indirect = !w->dense() && (long)n + m <= 32768;
-    w->setup_pending = (w->dense() || small_indirect) && w->mats->lazy_setup;
-  }
-  if (!w->setup_pending) {
-    w->set_diag_r();
-    w->update_work_cache();
-  }
-  HIP_CHECK(hipStreamSynchronize(s));
-  mark("R, preconditioner, g = KKT^-1 h");
+  mark("vectors, cones, AA workspace");
+  start_state(w, mark);
 }
 
 static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys = 0) {
@@ -301,6 +338,22 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
   w->mats->bu0 = w->cone.bu;
   w->mats->stgs0 = w->stgs;
   w->mats->lazy_setup = opts().lazy_setup;
+  w->mats->a_nnz_in = d->A->p[n];
+  w->mats->p_nnz_in = d->P ? d->P->p[n] : 0;
+  if (d->P) {  // (O(nnz(P)) over arrays validate_matrix has just walked)
+    bool below = false, unsorted = false;
+    for (int j = 0; j < n; ++j)
+      for (scs_int p = d->P->p[j]; p < d->P->p[j + 1]; ++p) {
+        below |= d->P->i[p] > j;
+        unsorted |= p > d->P->p[j] && d->P->i[p] < d->P->i[p - 1];
+      }
+    if (below) w->mats->p_update_refusal = "P was given to scs_init with entries below the diagonal (they were ignored): its values cannot be updated in place";
+    else if (unsorted) w->mats->p_update_refusal = "P was given to scs_init with row indices that do not ascend inside a column: its values cannot be updated in place";
+  }
+  if (d->P && stgs->normalize) {  // (scs_hip_update_matrix with one matrix kept re-equilibrates both: work.hpp MatrixSet::ax0)
+    w->mats->ax0.assign(d->A->x, d->A->x + w->mats->a_nnz_in);
+    w->mats->px0.assign(d->P->x, d->P->x + w->mats->p_nnz_in);
+  }
 
   init_streams_and_pinned(w.get());
   hipStream_t s = w->stream;
@@ -360,18 +413,7 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
   // ---- K12: equilibrate on the device, in place in all resident layouts ----
   if (w->normalized) {
     device_normalize(w->At, w->Ar, w->has_P ? &w->Pf : nullptr, w->cone, w->D, w->E, s);
-    w->scal.D.resize(m);
-    w->scal.E.resize(n);
-    w->D.download(w->scal.D.data(), m, s);
-    w->E.download(w->scal.E.data(), n, s);
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (w->cone.bsize > 1) {  // box bounds follow the row scaling: bl_j <- bl_j D_{j+1} / D_0
-      const double *Db = &w->scal.D[w->cone.off_box];
-      for (int j = 0; j < w->cone.bsize - 1; ++j) {
-        w->cone.bu[j] = (w->cone.bu[j] >= 1e15) ? INFINITY : Db[j + 1] * w->cone.bu[j] / Db[0];
-        w->cone.bl[j] = (w->cone.bl[j] <= -1e15) ? -INFINITY : Db[j + 1] * w->cone.bl[j] / Db[0];
-      }
-    }
+    adopt_equilibration(w.get());
   }
   mark("equilibration (device)");
   for (DeviceCsr *M : {&w->At, &w->Ar, &w->Pf}) M->refresh_slab(s, true);

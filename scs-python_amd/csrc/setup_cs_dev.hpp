@@ -225,6 +225,27 @@ __global__ __launch_bounds__(1024) void k_cs_fill(const int4 *__restrict__ pass_
   if (tid == 0) pinfo[g] = int2{base, len};
 }
 
+// k_cs_fill in map-only mode (matrix_update.hpp): the position in T of the value every slot of a pass holds, -1 for the padding slots.
+// The same keys and the same sort as k_cs_fill (ties by stream position), so slot for slot the placement of the builder.
+__global__ __launch_bounds__(1024) void k_cs_fill_map(const int4 *__restrict__ pass_info, const int *__restrict__ s_row,
+                                                      const int *__restrict__ s_src, int R, int rpt, int *map) {
+  __shared__ unsigned key[kCsPass];
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const int4 pi = pass_info[g];
+  const int begin = pi.x, len = pi.y, r0 = pi.w * R;
+  const unsigned RR = (unsigned)(kCsThreads * rpt);
+  for (int q = tid; q < kCsPass; q += kCsThreads) {
+    const unsigned k = q < len ? (unsigned)cs_row_key(s_row[begin + q] - r0, rpt) : RR;
+    key[q] = (k << kCsSlotBits) | (unsigned)q;
+  }
+  bitonic_sort_lds<kCsPass>(key);
+  const size_t o = (size_t)g * kCsPass;
+  for (int i = tid; i < kCsPass; i += kCsThreads) {
+    const int q = (int)(key[i] & (kCsPass - 1));
+    map[o + cs_store_pos(q)] = q < len ? s_src[begin + q] : -1;
+  }
+}
+
 // Owning device copy of one matrix in the column-sorted pass layout
 struct DeviceCs {
   DevBuf<int> passptr;
@@ -268,6 +289,40 @@ struct DeviceCs {
     meta.upload(h.meta.data(), h.meta.size(), s);
     HIP_CHECK(hipStreamSynchronize(s));
     ok = true;
+  }
+  // The value map of the EXISTING layout (matrix_update.hpp): map[k] = position in T's nonzero array of the value slot k holds, -1 for
+  // padding.  Partition, cut and slot sort of build_from_transpose are re-run on the same pattern with the layout's own geometry
+  // (R, rpt, split, the peel mask or the row slots of the virtual rows); nothing of the layout is written.  false: the re-run did not
+  // arrive at the layout's pass count (the map is released).
+  bool build_value_map(const int *tptr, const int *trow, long nnz, hipStream_t s, const unsigned *peel, DevBuf<int> &map) const {
+    map.release();
+    const int nblocks = (int)((nnz + kCsBlock - 1) / kCsBlock);
+    if (!ok || nnz <= 0 || npass <= 0) return false;
+    const long nh = (long)nchunks * nblocks;
+    DevBuf<int> hist, hoff, tmp, s_row, s_col, s_src, flag, pp;
+    DevBuf<int4> pass_info;
+    hist.alloc((size_t)nh);
+    hoff.alloc((size_t)nh + 1);
+    tmp.alloc_zero((size_t)(nh / kScanTile + 4), s);
+    flag.alloc_zero(1, s);
+    s_row.alloc((size_t)nnz); s_col.alloc((size_t)nnz); s_src.alloc((size_t)nnz);
+    hipLaunchKernelGGL(k_cs_hist, dim3(nblocks), dim3(1024), 0, s, trow, nnz, R, nchunks, nblocks, hist.p, peel);
+    device_exclusive_scan(hist.p, hoff.p, nh, tmp.p, s);
+    hipLaunchKernelGGL(k_cs_scatter, dim3(nblocks), dim3(1024), 0, s, tptr, trow, cols, nnz, R, nchunks, nblocks, hoff.p, s_row.p,
+                       s_col.p, s_src.p, peel);
+    pass_info.alloc((size_t)npass);
+    pp.alloc((size_t)nchunks * split + 1);
+    hipLaunchKernelGGL(k_cs_cut, dim3(1), dim3(kScanThreads), 0, s, hoff.p, nblocks, nchunks, split, nnz, s_col.p, npass, pp.p,
+                       pass_info.p, flag.p);
+    int got = 0, failed = 0;
+    HIP_CHECK(hipMemcpyAsync(&got, pp.p + (size_t)nchunks * split, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&failed, flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (failed || got != npass) return false;
+    map.alloc((size_t)npass * kCsPass);
+    hipLaunchKernelGGL(k_cs_fill_map, dim3(npass), dim3(kCsThreads), 0, s, pass_info.p, s_row.p, s_src.p, R, rpt, map.p);
+    HIP_CHECK(hipStreamSynchronize(s));  // (the stream positions are locals)
+    return true;
   }
   // layout for the matrix M (rows_ x cols_) whose TRANSPOSE is the CSR (tptr, trow, tval) with cols_ rows.
   // false (and nothing kept) when the pattern does not fit the format: the caller keeps its other layouts.

@@ -239,6 +239,23 @@ __global__ __launch_bounds__(kVecThreads) void k_slab_fill(const int *__restrict
     }
   }
 }
+// k_slab_fill in map-only mode (matrix_update.hpp): the CSR position every slab slot was filled from, through the resident row offsets
+// and segment pointers of the copy; the padding slots keep the -1 the caller filled the map with
+__global__ __launch_bounds__(kVecThreads) void k_slab_fill_map(const int *__restrict__ rowptr, const int *__restrict__ col, SlabGeom g,
+                                                               const unsigned short *__restrict__ roff, const int *__restrict__ segptr,
+                                                               int *s_map) {
+  for (long r = (long)blockIdx.x * kVecThreads + threadIdx.x; r < g.rows; r += (long)gridDim.x * kVecThreads) {
+    const int c = (int)(r / g.R), rl = (int)(r - (long)c * g.R);
+    int p = rowptr[r];
+    const int e = rowptr[r + 1];
+    while (p < e) {
+      const int s = col[p] >> g.shift;
+      const size_t seg = (size_t)c * g.S + s;
+      int dst = segptr[seg] + roff[seg * (g.R + kSlabRoffPad) + rl];
+      while (p < e && (col[p] >> g.shift) == s) s_map[dst++] = p++;
+    }
+  }
+}
 // the up-to-3 padding entries at the end of every segment: zero values on a column inside the slab
 __global__ __launch_bounds__(kVecThreads) void k_slab_pad(SlabGeom g, const unsigned short *__restrict__ roff, const int *__restrict__ segptr,
                                                           int *s_col, double *s_val) {

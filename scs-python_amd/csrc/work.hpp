@@ -42,6 +42,28 @@ struct MatrixSet {
   std::vector<double> b0, c0, bl0, bu0;
   ScsSettings stgs0{};
   bool lazy_setup = true;  // SCS_HIP_LAZY_SETUP as scs_init read it: a clone defers what its parent deferred
+  // scs_hip_update_matrix (matrix_update.hpp): nothing of this exists until the first call.  One int32 source index per stored value
+  // slot of every resident form but A' (whose values ARE the caller's CSC order): -1 marks a padding slot.  ar / pf index the caller's
+  // arrays, the layout maps the equilibrated CSR they were built from (cs of A': CSR(A); cs of A: CSR(A'); cs of P and every slab: own CSR).
+  struct ValueMaps {
+    bool built = false;
+    DevBuf<int> ar, pf, at_cs, ar_cs, pf_cs, at_slab, ar_slab, pf_slab;
+    // the caller's values as they arrived (staging of the host entry; with `normalize` and a P also the copy a later call that keeps
+    // one matrix re-equilibrates from)
+    DevBuf<double> raw_a, raw_p;
+    bool raw_a_set = false, raw_p_set = false;
+    size_t bytes() const {
+      return sizeof(int) * (ar.n + pf.n + at_cs.n + ar_cs.n + pf_cs.n + at_slab.n + ar_slab.n + pf_slab.n) + sizeof(double) * (raw_a.n + raw_p.n);
+    }
+  } vmaps;
+  long a_nnz_in = 0, p_nnz_in = 0;  // lengths of the value arrays scs_init was given (P: the triangle as passed)
+  // why Px cannot be taken ("" = it can): the map of the full CSR(P) (matrix_update.hpp k_map_pf) pairs the k-th entry of a column of the
+  // caller's triangle with the k-th lower entry of that row of the full matrix, which holds for an upper triangle with ascending
+  // row indices in every column only.  scs_init accepts other P (entries below the diagonal are ignored, columns may be unsorted).
+  std::string p_update_refusal;
+  // host copies of those values, kept only where a matrix update may need them: `normalize` with a P (updating one matrix re-equilibrates
+  // both from their raw values); moved to raw_a / raw_p by the first update
+  std::vector<double> ax0, px0;
   // The column-sorted layouts keep scratch of a product inside the layout (partial row sums of split chunks, piece sums of virtual rows,
   // combine tickets).  Workspaces that share such a set take turns: one solve / update at a time (small problems — CSR-stream — have none).
   std::mutex scratch_mu;

@@ -153,6 +153,17 @@ def _dense_1d(v):
   return v
 
 
+def _update_arg(M, what, upper):
+  """A matrix argument of `SCS.update_matrix` as the backend takes it: a sparse matrix becomes the (data, indices, indptr) of the form
+  the constructor hands over (`_csc_sorted`, upper triangle for P), anything else passes through."""
+  if M is None or not sparse.issparse(M):
+    return M
+  M = _csc_sorted(M, what)
+  if upper and _has_lower_tri(M):
+    M = sparse.triu(M, format="csc")
+  return (M.data, M.indices, M.indptr)
+
+
 class SCS(object):
 
   def __init__(self, data, cone, **settings):
@@ -208,6 +219,19 @@ class SCS(object):
     """Replace `b` and/or `c`, re-using the workspace for the next solve."""
     self._solver.update(b, c)
 
+
+  def update_matrix(self, A=None, P=None):
+    """Replace the VALUES of `A` and / or `P`, keeping the sparsity pattern the solver was created with (None = keep).  Each argument
+    is a scipy sparse matrix — brought to the form the constructor uses (sorted CSC, upper triangle of P; explicit zeros stay), its
+    pattern must equal the constructor's, else ValueError — or a 1-D float array of the stored values in that order.  The solver is
+    then in the state a new `SCS` on the new matrices and the current b, c would be in (cold start: pass x, y, s to `solve` for a warm
+    one); clones held by the caller must be gone (ValueError otherwise)."""
+    self._solver.update_matrix(_update_arg(A, "A", False), _update_arg(P, "P", True))
+
+  def update_matrix_device(self, A=None, P=None):
+    """`update_matrix` for values on the solver's GPU: float64, 1-D, contiguous torch tensors of the stored values in the constructor's
+    CSC order (P: its upper triangle).  The tensors must be complete on torch's current stream (the call synchronises it)."""
+    self._solver.update_matrix_device(A, P)
 
   def clone(self):
     """A second solver over the SAME device matrix: the state this one had when it was constructed (its original b, c and

@@ -207,6 +207,10 @@ def _load():
     lib.scs_hip_solution_to_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.scs_hip_update_device.restype = c_int
     lib.scs_hip_update_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.scs_hip_update_matrix.restype = c_int
+    lib.scs_hip_update_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.scs_hip_update_matrix_device.restype = c_int
+    lib.scs_hip_update_matrix_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.scs_hip_solve_device.restype = c_int
     lib.scs_hip_solve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_ScsInfo), c_int]
     lib.scs_hip_solve_batch_device.restype = c_int
@@ -615,6 +619,8 @@ class SCS(object):
             self._init_error = last_error()
             raise ValueError("ScsWork allocation error!" + (" (%s)" % self._init_error if self._init_error else ""))
         self._work = work
+        # the sparsity pattern as given (update_matrix checks new matrices against it; the arrays are the ones built above: no copy)
+        self._pattern = {"A": (Apc, Aic), "P": (Ppc, Pic) if have_P else None}
 
     # every attribute of an instance is set by these two: the constructor and clone() build their objects through them
     def _blank(self):
@@ -622,6 +628,7 @@ class SCS(object):
         self._lock = threading.Lock()
         self._fn_keep = []
         self._many = []  # solve_many's clones (members 1 .. K-1), kept for the next call
+        self._pattern = None  # {"A": (indptr, indices), "P": ... or None}: what update_matrix checks against
 
     def _shape(self, m, n):
         self.m, self.n = m, n
@@ -678,6 +685,52 @@ class SCS(object):
             _lib.scs_update(self._work, _pd(bc) if bc is not None else None, _pd(cc) if cc is not None else None)
         return None
 
+    # ---------------------------------------------------------- matrix values
+    def _finish_many(self):
+        """solve_many's cached clones share the matrix set, which a matrix update may not write under a reader: they are finished
+        here (internal objects; the next solve_many makes new ones)"""
+        pool, self._many = self._many, []
+        for sv in pool:
+            sv.__del__()
+
+    def _update_matrix_call(self, fn, ap, pp):
+        self._finish_many()
+        with self._lock:
+            if not self._work:
+                raise ValueError("Workspace not initialized!")
+            rc = fn(self._work, ap, pp)
+            err = last_error() if rc != 0 else ""
+        if rc != 0:
+            raise ValueError("libscs_hip: " + err)
+        return None
+
+    def update_matrix(self, A=None, P=None):
+        """New VALUES of A and / or P on the sparsity pattern of the constructor (include/scs_hip.h: scs_hip_update_matrix); None =
+        keep.  Each argument is a 1-D float array of nnz values in the constructor's CSC order (P: its upper triangle), or a
+        (data, indices, indptr) triple of a canonical CSC matrix whose pattern must equal the constructor's (`scs.SCS.update_matrix`
+        builds it from a scipy matrix).  Afterwards the solver is in the state a new one built from the new matrices and the current
+        b, c would be in: a following solve returns that solver's bits."""
+        if not self._work:
+            raise ValueError("Workspace not initialized!")
+        av = _matrix_values("A", A, self._pattern["A"]) if A is not None else None
+        pv = _matrix_values("P", P, self._pattern["P"]) if P is not None else None
+        if av is None and pv is None:
+            return None
+        return self._update_matrix_call(_lib.scs_hip_update_matrix, _pd(av) if av is not None else None, _pd(pv) if pv is not None else None)
+
+    def update_matrix_device(self, A=None, P=None):
+        """`update_matrix` for values that live on the workspace's GPU: float64, 1-D, contiguous torch tensors of nnz(A) / nnz(P)
+        elements in the constructor's CSC order, None = keep.  Same bits as `update_matrix` with the same values."""
+        dev = self._device_index()
+        if P is not None and self._pattern["P"] is None:
+            raise ValueError("P given, but the solver was created without P")
+        ap = _device_vec("A", A, int(self._pattern["A"][1].shape[0]), dev) if A is not None else None
+        pp = _device_vec("P", P, int(self._pattern["P"][1].shape[0]), dev) if P is not None else None
+        if ap is None and pp is None:
+            return None
+        _sync_torch_stream(dev)  # the stream contract: inputs complete before the library's own stream reads them
+        return self._update_matrix_call(_lib.scs_hip_update_matrix_device, ap, pp)
+
     # ------------------------------------------------- one matrix, many (b, c)
     def clone(self):
         """A new solver in the state the constructor left this one in (its original b, c and settings, cold start) that SHARES this
@@ -692,6 +745,7 @@ class SCS(object):
         new._blank()
         new._shape(self.m, self.n)
         new._work = work
+        new._pattern = self._pattern
         return new
 
     def shares_matrix(self, other):
@@ -905,6 +959,32 @@ class SCS(object):
             with lock:
                 _lib.scs_finish(self._work)
                 self._work = None
+
+
+def _matrix_values(name, M, pattern):
+    """The one argument check of SCS.update_matrix, before the library is called (no GPU needed): `M` is a 1-D float array of nnz values,
+    or a (data, indices, indptr) triple of a canonical CSC matrix; `pattern` = the (indptr, indices) the constructor was given, None for
+    a solver without that matrix.  Returns the float64 values (a fresh contiguous array).  Explicit zeros are values: nothing is
+    eliminated, so a matrix that lost or gained a stored entry differs in its pattern."""
+    if pattern is None:
+        raise ValueError("%s given, but the solver was created without %s" % (name, name))
+    indptr, indices = pattern
+    nnz = int(indices.shape[0])
+    if isinstance(M, tuple):
+        if len(M) != 3:
+            raise TypeError("%s must be a 1-D float array of values or a (data, indices, indptr) triple" % name)
+        data, ind, ptr = M
+        ind, ptr = np.asarray(ind), np.asarray(ptr)
+        if ptr.shape != indptr.shape or ind.shape != indices.shape or not np.array_equal(ptr, indptr) or not np.array_equal(ind, indices):
+            raise ValueError("%s: sparsity pattern differs from the one the solver was created with" % name)
+        M = data
+    if not isinstance(M, np.ndarray):
+        raise TypeError("%s must be a 1-D float array of values or a sparse matrix, not %s" % (name, type(M).__name__))
+    if M.ndim != 1 or not (np.issubdtype(M.dtype, np.floating) or np.issubdtype(M.dtype, np.integer)):
+        raise TypeError("%s values must be a 1-D numpy array of floats" % name)
+    if M.shape[0] != nnz:
+        raise ValueError("%s has %d values, the solver's pattern has %d" % (name, M.shape[0], nnz))
+    return np.array(M, dtype=np.float64, order="C", copy=True)
 
 
 def _device_vec(name, t, length, device):
