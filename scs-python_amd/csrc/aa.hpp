@@ -634,15 +634,15 @@ struct DeviceAa {
   DeviceAa &operator=(const DeviceAa &) = delete;
   ~DeviceAa() { if (h_pin && owns_pin) (void)hipHostFree(h_pin); }
 
-  static bool tsqr_default() { return !opts().aa_gram; }  // SCS_HIP_AA=gram: incremental Gram update + host solve (A/B, tests)
   int nbl() const { return vec_blocks(dim); }
 
+  // gram = Options::aa_gram (SCS_HIP_AA=gram: incremental Gram update + host solve; A/B, tests)
   void init(long dim_, int mem_, int type1_, double regularization_, double relaxation_, double safeguard_factor_,
-            double max_weight_norm_, hipStream_t s) {
+            double max_weight_norm_, hipStream_t s, bool gram) {
     dim = dim_; mem = mem_; type1 = type1_ ? 1 : 0; regularization = regularization_; relaxation = relaxation_;
     safeguard_factor = safeguard_factor_; max_weight_norm = max_weight_norm_; stream = s;
     iter = 0; success = 0; st = ScsAaStats{}; pending_safeguard = false;
-    tsqr = tsqr_default() && mem <= kAaMaxMem;  // (longer histories: the Gram path, a block of kAaMaxMem columns per launch)
+    tsqr = !gram && mem <= kAaMaxMem;  // (longer histories: the Gram path, a block of kAaMaxMem columns per launch)
     if (mem <= 0) return;
     for (DevBuf<double> *b : {&x, &f, &gprev}) b->alloc_zero((size_t)dim, s);
     for (DevBuf<double> *b : {&S, &Y, &D}) b->alloc_zero((size_t)dim * mem, s);
@@ -672,12 +672,8 @@ struct DeviceAa {
   int ncols() const { return type1 ? 2 * mem + 1 : mem + 1; }
 
   static constexpr int kTsqrWaves1 = 1024, kTsqrWaves2 = 16;
-  // chains of the register-tile level-1 kernel: enough wavefronts to put 2-3 on every SIMD of the chip (SCS_HIP_AA_WAVES1: lab)
-  static constexpr int kTsqrWavesFast = 4096;
-  static int fast_waves() {
-    const int t = opts().aa_waves1;  // (labs knob)
-    return t > 0 && t <= kTsqrWavesFast ? t : 2048;
-  }
+  // chains of the register-tile level-1 kernel: enough wavefronts to put 2-3 on every SIMD of the chip (rbuf holds up to kTsqrWavesFast)
+  static constexpr int kTsqrWavesFast = 4096, kTsqrWavesFast1 = 2048;
 
   // One launch of the TSQR reduction: the tall matrix it reads, its geometry and where its stacked triangles go
   struct TsqrLevel {
@@ -697,13 +693,12 @@ struct DeviceAa {
     W.ld = dim; W.rows = dim; W.nL = len; W.nY = type1 ? len : 0; W.c = W.nL + W.nY + 1; W.npiv = len;
     const int c = W.c, rho = aa_pick_rho(c);
     const size_t lds = aa_tsqr_lds(c, len, rho);
-    const bool fast_on = opts().aa_fast;  // (labs switch: the LDS kernel of round 2)
     int level = 0, dst = 0;
     while (true) {
-      const int fast = fast_on ? aa_tsqr_fast_kind(c, len) : 0;  // (every level: the stacked triangles have the same c columns and pivots)
+      const int fast = aa_tsqr_fast_kind(c, len);  // 0: the LDS-tile kernel of round 2 (every level: the stacked triangles have the same c columns and pivots)
       const int TR = 64 * (fast ? kAaFastRho : rho);
       const long ntiles = std::max(1L, (W.rows + TR - 1) / TR);
-      const long cap = fast ? (level == 0 ? fast_waves() : 64) : (level == 0 ? kTsqrWaves1 : kTsqrWaves2);
+      const long cap = fast ? (level == 0 ? kTsqrWavesFast1 : 64) : (level == 0 ? kTsqrWaves1 : kTsqrWaves2);
       long nw = ntiles <= 8 ? 1 : std::min(ntiles, cap);
       const long tpw = (ntiles + nw - 1) / nw;
       nw = (ntiles + tpw - 1) / tpw;

@@ -278,6 +278,10 @@ static std::atomic<long> g_tiled_launches{0};  // scs_hip_tiled_launches(): test
 
 // ---- the group ---------------------------------------------------------------------------------------------
 struct GroupSolve {
+  // what spans the members is call-level: the options scs_hip_solve_batch read when it was called (SCS_HIP_DEBUG=group, (labs)
+  // SCS_HIP_SHARED_TILE).  Everything per member — cone pipelines, the PSD stopping level, Anderson — follows the member's own snapshot.
+  const Options &opt;
+  explicit GroupSolve(const Options &o) : opt(o) {}
   std::vector<ScsHipWork *> W;
   std::vector<ScsSolution *> sols;
   bool dev_io = false;  // sols hold DEVICE addresses (scs_hip_solve_batch_device; work_solve_ends.inl)
@@ -323,13 +327,9 @@ struct GroupSolve {
   SCS_GTABLE(kVecThreads, d_copy_i32) t_gather_fl;
   // dense direct linsys (dense.hpp): rhs = R_x v_x - A' v_y; u~_x = G^{-1} rhs; u~_y = v_y + R_y^{-1} A u~_x — and the cold KKT solve of a scale update
   SCS_GTABLE(kSpmvThreads, d_spmv_stream<EpiDenseRhs>) t_dense_rhs;
-  SCS_GTABLE(kDenseThreads, d_dense_gemv) t_dense_gemv, t_dense_gemv_kkt;   // SCS_HIP_DENSE_GEMV=full
-  SCS_GTABLE(kDenseThreads, d_dense_symv_tiles) t_symv_tiles;
-  SCS_GTABLE(kDenseThreads, d_dense_symv_sum) t_symv_sum, t_symv_sum_kkt;
+  SCS_GTABLE(kDenseThreads, d_dense_gemv) t_dense_gemv, t_dense_gemv_kkt;
   void go_dense_gemv(const int *list, int count, bool kkt) {  // x = G^{-1} cg_b into ut (iteration) or ws (cold KKT solve)
-    if (ScsHipWork::dense_full_gemv()) { go(kkt ? t_dense_gemv_kkt : t_dense_gemv, list, count); return; }
-    go(t_symv_tiles, list, count);
-    go(kkt ? t_symv_sum_kkt : t_symv_sum, list, count);
+    go(kkt ? t_dense_gemv_kkt : t_dense_gemv, list, count);
   }
   SCS_GTABLE(kSpmvThreads, d_spmv_stream<EpiY>) t_dense_y;
   bool dense = false;
@@ -570,7 +570,7 @@ struct GroupSolve {
         set_of[(size_t)g] = (int)k;
       }
       shared_sets = (int)sets.size() < G;
-      has_runs = shared_sets && opts().shared_tile;
+      has_runs = shared_sets && opt.shared_tile;
       if (has_runs) {
         by_set.assign(sets.size(), {});
         HIP_CHECK(hipHostMalloc((void **)&tiles_h, sizeof(int) * (size_t)(kListSlots + 1) * 3 * G));
@@ -590,10 +590,9 @@ struct GroupSolve {
              t_gather_res, t_gather_fl, t_set_diag_r, t_precond, t_g_rhs, t_kkt_prep, t_spmv_rhs, t_zero_part, t_fin_tol,
              t_cg_init, t_fin_cg_init, t_zero_iters, t_kkt_y, t_copy_g, t_gg, t_fin_gg, t_v_rescale, t_spmv_ax);
     if (has_P) size_all(t_spmv_pws, t_spmv_p, t_res_px);
-    if (dense) size_all(t_dense_rhs, t_dense_gemv, t_dense_gemv_kkt, t_dense_y, t_symv_tiles, t_symv_sum, t_symv_sum_kkt);
+    if (dense) size_all(t_dense_rhs, t_dense_gemv, t_dense_gemv_kkt, t_dense_y);
     if (c0.bsize > 0) t_box.resize((size_t)G);
-    soc_psd_fused = w0->soc_psd_one_launch && w0->n_soc > 0 && w0->n_soc_big == 0 && w0->n_psd > 0 &&
-                    !w0->psd_small_one_wave;  // (as project_nonlinear_cones decides; member_ok: no big PSD matrix)
+    soc_psd_fused = w0->opt.soc_psd_fuse && w0->n_soc > 0 && w0->n_soc_big == 0 && w0->n_psd > 0;  // (as project_nonlinear_cones decides; member_ok: no big PSD matrix)
     if (soc_psd_fused) t_soc_psd.resize((size_t)G);
     else {
       if (w0->n_soc > 0) t_soc.resize((size_t)G);
@@ -645,9 +644,6 @@ struct GroupSolve {
         t_dense_rhs.set(g, At, w->v.p + n, EpiDenseRhs{w->cg_b.p, w->rdx(), w->v.p}, nullptr, nullptr);
         t_dense_gemv.set(g, w->dn_G.p, dn_NP, n, w->cg_b.p, w->ut.p, nostall);
         t_dense_gemv_kkt.set(g, w->dn_G.p, dn_NP, n, w->cg_b.p, w->ws.p, nostall);
-        t_symv_tiles.set(g, w->dn_G.p, dn_NP, n, w->cg_b.p, w->dn_part.p, nostall);
-        t_symv_sum.set(g, w->dn_part.p, dn_NP, n, w->ut.p, nostall);
-        t_symv_sum_kkt.set(g, w->dn_part.p, dn_NP, n, w->ws.p, nostall);
       }
       if (has_P) t_spmv_pws.set(g, Pf, w->ws.p, EpiStore{w->cg_Gp.p, 0}, nullptr, nullptr);
       t_spmv_r0.set(g, At, w->ut.p + n,
@@ -746,8 +742,6 @@ struct GroupSolve {
     t_spmv_y.gx = t_spmv_a.gx = t_res_pri.gx = t_spmv_ax.gx = t_dense_y.gx = gx_ar;
     t_spmv_r0.gx = t_spmv_at.gx = t_res_dual.gx = t_spmv_rhs.gx = t_dense_rhs.gx = gx_at;
     t_dense_gemv.gx = t_dense_gemv_kkt.gx = dense_gemv_blocks(n);
-    t_symv_tiles.gx = dense ? dense_symv_tiles(dn_NP) : 1;
-    t_symv_sum.gx = t_symv_sum_kkt.gx = ceil_div(n, kDenseThreads);
     if (dense) {  // the members' matrices as the batched factorisation kernels take them
       std::vector<DenseMat> hm((size_t)G);
       std::vector<DenseSrc> hs((size_t)G);
@@ -798,7 +792,7 @@ struct GroupSolve {
     f(t_kkt_y); f(t_copy_g); f(t_gather_aa); f(t_gg); f(t_fin_gg); f(t_v_rescale); f(t_aa_seed); f(t_aa_update);
     for (int k = 0; k < n_tsqr; ++k) { f(t_aa_tsqr_f21[k]); f(t_aa_tsqr_f11[k]); f(t_aa_tsqr[k]); }
     f(t_aa_solve); f(t_aa_apply); f(t_aa_diffsq); f(t_fin_safe); f(t_aa_restore);
-    f(t_dense_rhs); f(t_dense_gemv); f(t_dense_gemv_kkt); f(t_dense_y); f(t_symv_tiles); f(t_symv_sum); f(t_symv_sum_kkt);
+    f(t_dense_rhs); f(t_dense_gemv); f(t_dense_gemv_kkt); f(t_dense_y);
   }
   void upload_all() {
     for_tables([&](auto &t) { t.upload(s); });
@@ -992,7 +986,7 @@ struct GroupSolve {
     std::iota(active.begin(), active.end(), 0);
     upload_active();
     std::vector<int> tmp_list;
-    const bool stats = (opts().debug & DBG_GROUP) != 0;  // SCS_HIP_DEBUG=group
+    const bool stats = (opt.debug & DBG_GROUP) != 0;  // SCS_HIP_DEBUG=group
     InterruptListener ctrlc;  // (loop.hpp: Ctrl-C ends every member that is still running with SCS_SIGINT)
     for (int i = 0; !active.empty(); ++i) {
       if (InterruptListener::interrupted()) {
@@ -1108,8 +1102,7 @@ struct GroupSolve {
       if (has_P) go_mv(t_spmv_pws, active_d, na);
       go_mv(t_spmv_r0, active_d, na);
       go(t_fin_head, active_d, na);
-      const int pred_mode = opts().group_predict;  // (labs) 0: max + 1
-      finish_cg(active, active_d, 0, [&](int g) { return pred_mode ? W[(size_t)g]->recent_cg_q3() : W[(size_t)g]->recent_cg_max() + 1; }, deferred_host_work);
+      finish_cg(active, active_d, 0, [&](int g) { return W[(size_t)g]->recent_cg_q3(); }, deferred_host_work);
       iters_since_sync = 0;
       for (int g : active) {
         ScsHipWork *w = W[(size_t)g];
@@ -1218,7 +1211,7 @@ struct GroupSolve {
       }
     }
     HIP_CHECK(hipStreamSynchronize(s));
-    if (opts().debug & DBG_GROUP)
+    if (opt.debug & DBG_GROUP)
       std::fprintf(stderr, "[scs-hip group] members %d, lock-step iterations %d, grouped launches %ld (%.1f per iteration), host syncs %d, %.1f ms (%.1f ms of it finishing members: un-scaling, s'y, downloads)\n",
                    G, lockstep_iters, launches, (double)launches / std::max(lockstep_iters, 1), syncs, now_ms() - t_start, t_finish);
   }

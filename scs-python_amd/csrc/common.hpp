@@ -73,7 +73,7 @@ struct DevPool {
         blocks.erase(blocks.begin() + (long)i);
         cached -= bytes;
         ++hits;
-        if (opts().pool_poison) {  // (labs: recycled blocks arrive poisoned)
+        if (opts().pool_poison) {  // (labs: recycled blocks arrive poisoned; the pool is the process's, so this is the global's, by design)
           (void)hipMemset(p, 0xFF, bytes);
           (void)hipDeviceSynchronize();
         }

@@ -250,6 +250,9 @@ __device__ __forceinline__ void d_gj_update(DenseMat D, int k) {
 // its rows 2 l, 2 l + 1, 2 l + 128, ... in ascending order, then the fixed shuffle tree.  (Round 4: 16-byte loads of the four
 // columns against one pair of b entries — 6 memory instructions per 4 x 128 entries where one column per wavefront needed 16; a
 // batch of 512 members streams 8 GB of inverses per lock-step iteration through this kernel.)
+// The WHOLE computed inverse X is read although it is symmetric: a Gauss-Jordan inverse is accurate on ONE side (|| X G - I || ~ eps kappa,
+// so X' b solves G x = b to ~ kappa eps), while its asymmetry — what a product that mirrors one triangle sees — is kappa times larger.
+// The half-storage product was built and measured (1e-11 against 3.5e-8 relative error at kappa = 2e4) and is gone: DESIGN.md §4 "Retired lab switches".
 constexpr int kDenseGemvCols = 4;
 inline int dense_gemv_blocks(int n) { return ceil_div(n, kDenseGemvCols * (kDenseThreads / 64)); }
 __device__ __forceinline__ void d_dense_gemv(const double *__restrict__ Ginv, int NP, int n, const double *__restrict__ b, double *x,
@@ -281,78 +284,6 @@ __device__ __forceinline__ void d_dense_gemv(const double *__restrict__ Ginv, in
     if (j0 + 2 < n) x[j0 + 2] = s2;
     if (j0 + 3 < n) x[j0 + 3] = s3;
   }
-}
-
-// ---- x = G^{-1} b reading only the tiles on and below the diagonal (the inverse is symmetric; a batch of 512 config-5 members streams
-// 8 GB of inverses per lock-step iteration through the full product — the HBM-bound part of that batch).  LAB SWITCH
-// (SCS_HIP_DENSE_GEMV=half), not the default: a Gauss-Jordan inverse X is accurate on one side only — d_dense_gemv's X' b has the
-// residual of || X G - I || ~ kappa eps, a product that mirrors one triangle of X sees its asymmetry, ~ kappa^2 eps (measured 1e-11
-// vs 3.5e-8 at kappa = 2e4; ScsHipWork::dense_full_gemv).  Two launches:
-//   d_dense_symv_tiles: workgroup t = tile (I, J), I >= J, of 64 x 64:  part[I][J] = T x_J,  part[J][I] = T' x_I  (I != J)
-//   d_dense_symv_sum:   x_K = sum over o = 0 .. nb-1, ascending, of part[K][o]
-// Every slot part[K][o] is written by exactly one tile; fixed summation orders everywhere => deterministic, and the same bits for a
-// member of a group and a solve of its own.  (What is used of G^{-1} is its lower triangle: the operator is exactly symmetric.)
-__device__ __forceinline__ void d_dense_symv_tiles(const double *__restrict__ Ginv, int NP, int n, const double *__restrict__ b, double *part,
-                                                   const int *stall) {
-  SCS_STALL_GUARD(stall);
-  __shared__ double xs[2][kDenseB], red[4][kDenseB];
-  const int nb = NP / kDenseB, tid = threadIdx.x;
-  const int t = blockIdx.x;
-  if (t >= nb * (nb + 1) / 2) return;
-  int I = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-  while (I * (I + 1) / 2 > t) --I;
-  while ((I + 1) * (I + 2) / 2 <= t) ++I;
-  const int J = t - I * (I + 1) / 2;
-  const int I0 = I * kDenseB, J0 = J * kDenseB;
-  if (I0 >= n) return;  // (I >= J: padding rows and, with them or alone, padding columns: zero off the diagonal; their slots are never read — d_dense_symv_sum stops at o with o 64 < n)
-  if (tid < 64) xs[0][tid] = J0 + tid < n ? b[J0 + tid] : 0.;
-  else if (tid < 128) xs[1][tid - 64] = I0 + (tid - 64) < n ? b[I0 + (tid - 64)] : 0.;
-  __syncthreads();
-  const int r = tid & 63, q = tid >> 6;
-  const double *src = Ginv + (size_t)(I0 + r) + (size_t)NP * (J0 + q * 16);
-  double v[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) v[k] = src[(size_t)NP * k];
-  double d = 0.;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) d += v[k] * xs[0][q * 16 + k];
-  red[q][r] = d;
-  if (I != J) {
-    const double xi = xs[1][r];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const double s = wave_sum(v[k] * xi);  // (wavefront q holds all 64 rows of its 16 columns)
-      if (r == 0) part[((size_t)J * nb + I) * kDenseB + q * 16 + k] = s;
-    }
-  }
-  __syncthreads();
-  if (tid < 64) part[((size_t)I * nb + J) * kDenseB + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-}
-__device__ __forceinline__ void d_dense_symv_sum(const double *__restrict__ part, int NP, int n, double *x, const int *stall) {
-  SCS_STALL_GUARD(stall);
-  const int nb = NP / kDenseB, no = (n + kDenseB - 1) / kDenseB;  // blocks o >= no hold only padding
-  const int i = blockIdx.x * kDenseThreads + threadIdx.x;
-  if (i >= n) return;
-  const int K = i / kDenseB, r = i % kDenseB;
-  const double *p = part + (size_t)K * nb * kDenseB + r;
-  double s = 0.;
-  for (int o = 0; o < no; ++o) s += p[(size_t)o * kDenseB];
-  x[i] = s;
-}
-inline int dense_symv_tiles(int NP) { const int nb = NP / kDenseB; return nb * (nb + 1) / 2; }
-inline size_t dense_symv_part_len(int NP) { const size_t nb = (size_t)(NP / kDenseB); return nb * nb * kDenseB; }
-
-__global__ __launch_bounds__(kDenseThreads) void k_dense_symv_tiles(const double *__restrict__ Ginv, int NP, int n, const double *__restrict__ b,
-                                                                    double *part, const int *stall) {
-  d_dense_symv_tiles(Ginv, NP, n, b, part, stall);
-}
-__global__ __launch_bounds__(kDenseThreads) void k_dense_symv_sum(const double *__restrict__ part, int NP, int n, double *x, const int *stall) {
-  d_dense_symv_sum(part, NP, n, x, stall);
-}
-// x = G^{-1} b on stream s (two launches)
-inline void dense_apply(const double *Ginv, int NP, int n, const double *b, double *part, double *x, const int *stall, hipStream_t s) {
-  hipLaunchKernelGGL(k_dense_symv_tiles, dim3(dense_symv_tiles(NP)), dim3(kDenseThreads), 0, s, Ginv, NP, n, b, part, stall);
-  hipLaunchKernelGGL(k_dense_symv_sum, dim3(ceil_div(n, kDenseThreads)), dim3(kDenseThreads), 0, s, (const double *)part, NP, n, x, stall);
 }
 
 __global__ __launch_bounds__(kDenseBuildThreads) void k_dense_build(DenseSrc S, DenseMat D) { d_dense_build(S, D); }

@@ -21,17 +21,18 @@ struct DeviceCsr {
   int s_shift = 0;  // log2 of the slab width the copy was built with (matrix_update.hpp re-derives the value map from it)
   // optional column-sorted pass copy (spmv_cs.hpp); preferred over the slab copy when both could be built
   DeviceCs cs;
-  static bool cs_enabled() { return opts().cs; }  // SCS_HIP_CS=0: keep the slab kernel (A/B measurements)
   // rows too long for the layout's count fields are peeled off it (spmv_cs.hpp CsView::peel) and done over the plain CSR
   DevBuf<unsigned> peel_mask;
   DevBuf<int4> peel_blk;
   int npeel = 0, npeel_long = 0;
   long peel_nnz = 0;  // nonzeros in the peeled rows
   int cs_virt_lp = 0;  // piece length the virtual-row layout was accepted with (0: no virtual rows); matrix_update.hpp re-plans with it
+  // Every builder below takes the options the layouts are built under (`o`: the matrix set's snapshot, work.hpp MatrixSet::opt — or a
+  // kernel-level entry point's own): what a value map is later re-derived from must be what the layout was built with.
   // host: mark rows longer than `thresh`; one row block {row, row + 1, first nonzero, end} each.  false: nothing to peel
-  bool make_peel(const int *rp_host, int thresh, hipStream_t s) {
+  bool make_peel(const int *rp_host, int thresh, hipStream_t s, const Options &o) {
     peel_mask.release(); peel_blk.release(); npeel = 0; npeel_long = 0; peel_nnz = 0;
-    if (!opts().cs_peel) return false;  // (labs) A/B: reject such patterns as round 1 did
+    if (!o.cs_peel) return false;  // (labs) A/B: reject such patterns as round 1 did
     std::vector<int4> blk;
     std::vector<unsigned> mask;
     for (int r = 0; r < rows; ++r)
@@ -54,13 +55,12 @@ struct DeviceCsr {
   }
   // ---- virtual rows (spmv_cs.hpp CsView::Rr): long rows cut into pieces that ride in the passes ----
   using VirtPlan = CsVirtPlan;
-  static bool virt_enabled() { return opts().cs_virt; }  // (labs) SCS_HIP_CS_VIRT=0: long rows go to the CSR-stream side launch whole (round 2)
   // rows longer than max(lp, what a count field holds) nonzeros -> ceil(len / lp) pieces (rows a field holds stay whole and keep
   // the oracle's summation order; a piece's run is added by ONE lane, so pieces are short whatever the field would hold);
   // fills the peel mask / row blocks {row, row + 1, first piece, end}
-  bool plan_virtual(const int *rp, int lp, VirtPlan &P, hipStream_t s) {
+  bool plan_virtual(const int *rp, int lp, VirtPlan &P, hipStream_t s, const Options &o) {
     clear_peel();
-    if (!cs_plan_virtual(rp, rows, lp, std::max(lp, peel_threshold(1)), P)) return false;
+    if (!cs_plan_virtual(rp, rows, lp, std::max(lp, peel_threshold(1, o)), P, o.cs_rpt)) return false;
     npeel = (int)P.blk.size();
     npeel_long = 0;  // (a row's pieces are few: one wavefront adds them)
     peel_nnz = P.long_nnz;
@@ -74,9 +74,9 @@ struct DeviceCsr {
     cs.Rr = P.Rr; cs.Rp = P.Rp; cs.npieces = P.V;
     cs.tpart.alloc_zero((size_t)P.V, s);
   }
-  bool build_virtual_dev(const DeviceCsr &T, const int *rp, int lp, hipStream_t s) {
+  bool build_virtual_dev(const DeviceCsr &T, const int *rp, int lp, hipStream_t s, const Options &o) {
     VirtPlan P;
-    if (!plan_virtual(rp, lp, P, s)) return false;
+    if (!plan_virtual(rp, lp, P, s, o)) return false;
     DevBuf<int2> d_info;
     DevBuf<int> vslot;
     d_info.upload(P.rowinfo.data(), P.rowinfo.size(), s);
@@ -85,17 +85,17 @@ struct DeviceCsr {
                        d_info.p, P.Rr, P.Rp, P.R, vslot.p);
     HIP_CHECK(hipStreamSynchronize(s));  // (P.rowinfo is read by the upload)
     const bool built = cs.build_from_transpose(P.nchunks * P.R, cols, T.rowptr.p, vslot.p, T.val.p, nnz, s, 1, nullptr, P.R, P.rpt);
-    if (opts().debug & DBG_SETUP)
+    if (o.debug & DBG_SETUP)
       std::fprintf(stderr, "[scs-hip] column-sorted layout %d x %d: rows longer than %d in pieces of <= %d (%d rows, %ld of %ld nonzeros, %d pieces; chunks of %d + %d slots, %d rows per lane): %s\n",
-                   rows, cols, std::max(lp, peel_threshold(1)), lp, npeel, peel_nnz, (long)nnz, P.V, P.Rr, P.Rp, P.rpt, built ? "built" : "a count field overflowed");
+                   rows, cols, std::max(lp, peel_threshold(1, o)), lp, npeel, peel_nnz, (long)nnz, P.V, P.Rr, P.Rp, P.rpt, built ? "built" : "a count field overflowed");
     if (!built) { clear_peel(); return false; }
     adopt_virtual(P, s);
     cs_virt_lp = lp;
     return true;
   }
-  bool build_virtual_host(const int *rp, const int *ci, const double *v, int lp, hipStream_t s, HostCs &h) {
+  bool build_virtual_host(const int *rp, const int *ci, const double *v, int lp, hipStream_t s, HostCs &h, const Options &o) {
     VirtPlan P;
-    if (!plan_virtual(rp, lp, P, s)) return false;
+    if (!plan_virtual(rp, lp, P, s, o)) return false;
     if (!build_cs_virtual(rp, ci, v, rows, cols, P, h)) { clear_peel(); return false; }
     virt_host_plan = P;
     cs_virt_lp = lp;
@@ -109,36 +109,32 @@ struct DeviceCsr {
     for (int per_pass : {24, 12, 6}) out.push_back((int)std::min<long>(per_pass * npass_est, 1L << 20));
     return out;
   }
-  static std::vector<int> peel_ladder() {  // (labs) SCS_HIP_CS_PEEL_LADDER=0: rows longer than a count field at once (round 2)
-    if (!opts().cs_peel_ladder) return {1};
-    return {32, 16, 8, 4, 2, 1};
-  }
-  int peel_threshold(int split) const {
+  static constexpr int kPeelLadder[] = {32, 16, 8, 4, 2, 1};  // multiples of the count field's capacity tried as the peel threshold
+  int peel_threshold(int split, const Options &o) const {
     int R, rpt;
-    cs_pick_geometry(rows, R, rpt, split);
+    cs_pick_geometry(rows, R, rpt, split, o.cs_rpt);
     return cs_peel_threshold(rpt);
   }
   DevBuf<double> cs_part0, cs_part1;  // cs.split == 2 without the in-kernel combine: partial row sums (spmv.hpp EpiPartial / EpiGp::split)
-  static bool cs_split_enabled() { return opts().cs_split; }  // SCS_HIP_CS_SPLIT=0: one workgroup per row chunk everywhere (bit-exact sequential row sums; A/B)
   // Workgroups per row chunk.  kind: 0 = A (y-space products), 1 = A' (x-space products), 2 = P.  Taller chunks mean more
   // nonzeros per 128-byte line of the gather vector, i.e. fewer lines per gather instruction — the quantity that bounds
   // these kernels — at the price of partial row sums.  Default: only A' is split, in two, and hands its two partial
   // vectors to the CG update (EpiGp::split: Gp is linear in them) or to k_epi_finish — no combine pass.
   // SCS_HIP_CS_COMBINE=1: the partial sums of up to 4 parts are added INSIDE the kernel by the
-  // last workgroup of a chunk to arrive, so every product — A too — may be split (SCS_HIP_CS_SPLIT_A / _AT / _P).
+  // last workgroup of a chunk to arrive, so every product — A too — may be split (SCS_HIP_CS_SPLIT_A / _AT).
   // Measured at the bench size (tools/cs_lab.hip): the 48 MB of partial-sum traffic and the 16-rows-per-lane row sums
   // eat the gather gain (A: 91.5 us unsplit, 95 us split in two + combine; A': 93 us two partial vectors, 100 us four
   // parts + combine) => off by default.
-  static bool cs_combine_enabled() { return opts().cs_combine; }  // (labs)
-  int cs_pick_split(int kind) const {
-    if (!cs_split_enabled() || opts().cs_rpt > 0) return 1;
-    if (!cs_combine_enabled()) {
+  // SCS_HIP_CS_SPLIT=0: one workgroup per row chunk everywhere (bit-exact sequential row sums; A/B)
+  int cs_pick_split(int kind, const Options &o) const {
+    if (!o.cs_split || o.cs_rpt > 0) return 1;
+    if (!o.cs_combine) {  // (labs: the in-kernel combine)
       if (kind != 1) return 1;
       int R, rpt;
       cs_pick_geometry(rows, R, rpt, 2);
       return rpt <= 8 ? 2 : 1;
     }
-    { const int v = kind == 0 ? opts().cs_split_a : kind == 1 ? opts().cs_split_at : opts().cs_split_p; if (v == 1 || v == 2 || v == 4) return v; }
+    { const int v = kind == 0 ? o.cs_split_a : kind == 1 ? o.cs_split_at : 0; if (v == 1 || v == 2 || v == 4) return v; }
     for (int sp : {4, 2}) {
       int R, rpt;
       cs_pick_geometry(rows, R, rpt, sp);
@@ -146,19 +142,21 @@ struct DeviceCsr {
     }
     return 1;
   }
-  void cs_after_build(hipStream_t s) {
+  void cs_after_build(hipStream_t s, const Options &o) {
     cs_part0.release(); cs_part1.release();
     if (!cs.ok || cs.split <= 1) return;
-    if (cs_combine_enabled()) cs.enable_combine(s);
+    if (o.cs_combine) cs.enable_combine(s);
     else { cs_part0.alloc_zero((size_t)rows, s); cs_part1.alloc_zero((size_t)rows, s); }
   }
   // T = this matrix transposed (device CSR with the CURRENT values); host: build from this matrix's own host arrays.
-  bool build_cs_dev(const DeviceCsr &T, hipStream_t s, int kind) {
+  // the pass layout is used at all: SCS_HIP_CS=0 keeps the slab kernel, SCS_HIP_SLAB=0 the CSR-stream kernel (A/B measurements)
+  bool cs_wanted_here(const Options &o) const { return o.cs && o.slab && cs_wanted(rows, nnz, o.cs_min_nnz); }
+  bool build_cs_dev(const DeviceCsr &T, hipStream_t s, int kind, const Options &o) {
     cs.release();
     peel_mask.release(); peel_blk.release(); npeel = 0; npeel_long = 0;
-    if (!cs_enabled() || !cs_wanted(rows, cols, nnz) || !opts().slab) return false;
+    if (!cs_wanted_here(o)) return false;
     bool ok = false;
-    const int sp = cs_pick_split(kind);
+    const int sp = cs_pick_split(kind, o);
     std::vector<int> rp((size_t)rows + 1);  // row lengths decide what is peeled (O(rows) at init)
     rowptr.download(rp.data(), rp.size(), s);
     HIP_CHECK(hipStreamSynchronize(s));
@@ -168,20 +166,20 @@ struct DeviceCsr {
     // a layout whose peeled rows hold most of the nonzeros is not kept (the side launch would be the product).
     auto attempt = [&](int split) {
       clear_peel();
-      if (cs.build_from_transpose(rows, cols, T.rowptr.p, T.col.p, T.val.p, nnz, s, split, nullptr)) return true;
+      if (cs.build_from_transpose(rows, cols, T.rowptr.p, T.col.p, T.val.p, nnz, s, split, nullptr, 0, o.cs_rpt)) return true;
       // the long rows cut into pieces that ride in the passes (one workgroup per chunk: split 1) ...
-      if (virt_enabled())
+      if (o.cs_virt)  // (labs) SCS_HIP_CS_VIRT=0: long rows go to the CSR-stream side launch whole (round 2)
         for (int lp : virt_piece_lengths())
-          if (build_virtual_dev(T, rp.data(), lp, s)) return true;
+          if (build_virtual_dev(T, rp.data(), lp, s, o)) return true;
       // ... or, failing that, peeled as FEW rows as the count fields allow: a row of 500 nonzeros has ~50 in each of its chunk's ten passes and
       // rides in them (its gathers share lines with the other rows' there); thresholds from 32 x the field down to the field
-      for (int mult : peel_ladder()) {
-        if (!make_peel(rp.data(), peel_threshold(split) * mult, s)) continue;  // (no row that long: next rung)
+      for (int mult : kPeelLadder) {
+        if (!make_peel(rp.data(), peel_threshold(split, o) * mult, s, o)) continue;  // (no row that long: next rung)
         if (peel_nnz > (nnz / 5) * 3) { clear_peel(); return false; }
-        const bool built = cs.build_from_transpose(rows, cols, T.rowptr.p, T.col.p, T.val.p, nnz, s, split, peel_mask.p);
-        if (opts().debug & DBG_SETUP)
+        const bool built = cs.build_from_transpose(rows, cols, T.rowptr.p, T.col.p, T.val.p, nnz, s, split, peel_mask.p, 0, o.cs_rpt);
+        if (o.debug & DBG_SETUP)
           std::fprintf(stderr, "[scs-hip] column-sorted layout %d x %d, split %d: rows longer than %d peeled (%d rows, %ld of %ld nonzeros): %s\n",
-                       rows, cols, split, peel_threshold(split) * mult, npeel, peel_nnz, (long)nnz, built ? "built" : "a count field overflowed");
+                       rows, cols, split, peel_threshold(split, o) * mult, npeel, peel_nnz, (long)nnz, built ? "built" : "a count field overflowed");
         if (built) return true;
       }
       clear_peel();
@@ -190,31 +188,31 @@ struct DeviceCsr {
     if (sp > 1) ok = attempt(sp);
     if (!ok) ok = attempt(1);
     if (!ok) clear_peel();
-    cs_after_build(s);
+    cs_after_build(s, o);
     return ok;
   }
   void clear_peel() { peel_mask.release(); peel_blk.release(); npeel = 0; npeel_long = 0; peel_nnz = 0; cs_virt_lp = 0; }
-  bool build_cs_host(const int *rp, const int *ci, const double *v, hipStream_t s, int kind) {
+  bool build_cs_host(const int *rp, const int *ci, const double *v, hipStream_t s, int kind, const Options &o) {
     cs.release();
     peel_mask.release(); peel_blk.release(); npeel = 0; npeel_long = 0;
-    if (!cs_enabled() || !cs_wanted(rows, cols, nnz) || !opts().slab) return false;
+    if (!cs_wanted_here(o)) return false;
     HostCs h;
     bool ok = false, virt_host = false;
-    const int sp = cs_pick_split(kind);
+    const int sp = cs_pick_split(kind, o);
     auto attempt = [&](int split) {  // same policy as build_cs_dev: unpeeled first, then the long rows peeled, capped
       clear_peel();
-      if (build_cs(rp, ci, v, rows, cols, h, 0, split, nullptr)) return true;
-      if (virt_enabled())
+      if (build_cs(rp, ci, v, rows, cols, h, o.cs_rpt, split, nullptr)) return true;
+      if (o.cs_virt)
         for (int lp : virt_piece_lengths())
-          if (build_virtual_host(rp, ci, v, lp, s, h)) { virt_host = true; return true; }
-      for (int mult : peel_ladder()) {
-        const int thresh = peel_threshold(split) * mult;
-        if (!make_peel(rp, thresh, s)) continue;
+          if (build_virtual_host(rp, ci, v, lp, s, h, o)) { virt_host = true; return true; }
+      for (int mult : kPeelLadder) {
+        const int thresh = peel_threshold(split, o) * mult;
+        if (!make_peel(rp, thresh, s, o)) continue;
         if (peel_nnz > (nnz / 5) * 3) { clear_peel(); return false; }
         std::vector<unsigned> mk(((size_t)rows + 31) / 32, 0u);
         for (int r = 0; r < rows; ++r)
           if (rp[r + 1] - rp[r] > thresh) mk[r >> 5] |= 1u << (r & 31);
-        if (build_cs(rp, ci, v, rows, cols, h, 0, split, mk.data())) return true;
+        if (build_cs(rp, ci, v, rows, cols, h, o.cs_rpt, split, mk.data())) return true;
       }
       clear_peel();
       return false;
@@ -224,26 +222,26 @@ struct DeviceCsr {
     if (!ok) { clear_peel(); return false; }
     cs.from_host(h, s);
     if (virt_host) adopt_virtual(virt_host_plan, s);
-    cs_after_build(s);
+    cs_after_build(s, o);
     return true;
   }
-  static bool host_setup() { return opts().host_setup; }  // SCS_HIP_SETUP=host: transposition and slab construction on the host (fallback / A-B / tests)
   void set_rowblocks(const int *rp_host, hipStream_t s) {
     std::vector<int4> rb = build_rowblocks(rp_host, rows);
     nblk = (int)rb.size();
     rowblk.upload(rb.data(), rb.size(), s);
     HIP_CHECK(hipStreamSynchronize(s));  // rb is a local
   }
-  void upload(int rows_, int cols_, const int *rp, const int *ci, const double *v, hipStream_t s, bool allow_slab = true) {
+  // (o.host_setup — SCS_HIP_SETUP=host — builds the slab copy on the host: fallback / A-B / tests)
+  void upload(int rows_, int cols_, const int *rp, const int *ci, const double *v, hipStream_t s, const Options &o, bool allow_slab = true) {
     rows = rows_; cols = cols_; nnz = rp[rows_];
     rowptr.upload(rp, rows + 1, s);
     col.upload(ci, nnz, s);
     val.upload(v, nnz, s);
     set_rowblocks(rp, s);
     has_slab = false;
-    if (allow_slab && slab_wanted(rows, cols) && opts().slab) {  // SCS_HIP_SLAB=0 forces the plain CSR-stream kernel (A/B measurements)
-      if (!host_setup()) {
-        build_slab_dev(s);
+    if (allow_slab && slab_wanted(rows, cols) && o.slab) {  // SCS_HIP_SLAB=0 forces the plain CSR-stream kernel (A/B measurements)
+      if (!o.host_setup) {
+        build_slab_dev(s, o);
       } else {
         HostSlab hs;
         std::vector<int> src;
@@ -253,7 +251,7 @@ struct DeviceCsr {
           s_roff.upload(hs.roff.data(), hs.roff.size(), s);
           s_col.upload(hs.col.data(), hs.col.size(), s);
           s_val.upload(hs.val.data(), hs.val.size(), s);
-          s_nchunks = hs.nchunks; s_S = hs.S; s_R = hs.R; s_max_seg = hs.max_seg; s_shift = slab_shift();
+          s_nchunks = hs.nchunks; s_S = hs.S; s_R = hs.R; s_max_seg = hs.max_seg; s_shift = kSlabShift;
           has_slab = true;
           HIP_CHECK(hipStreamSynchronize(s));  // hs is a local
         }
@@ -300,11 +298,11 @@ struct DeviceCsr {
     return true;
   }
   // L2-blocked copy of the CURRENT csr arrays, built on the device (same layout as spmv.hpp build_slab)
-  void build_slab_dev(hipStream_t s) {
+  void build_slab_dev(hipStream_t s, const Options &o) {
     has_slab = false;
-    if (!slab_wanted(rows, cols) || !opts().slab) return;
+    if (!slab_wanted(rows, cols) || !o.slab) return;
     SlabGeom g;
-    g.rows = rows; g.cols = cols; g.R = slab_pick_rows(rows); g.shift = slab_shift();
+    g.rows = rows; g.cols = cols; g.R = slab_pick_rows(rows); g.shift = kSlabShift;
     g.S = (int)(((long)cols + (1L << g.shift) - 1) >> g.shift);
     g.nchunks = (rows + g.R - 1) / g.R;
     const long nseg = (long)g.nchunks * g.S;
@@ -342,14 +340,14 @@ struct DeviceCsr {
   // ---- value maps of the EXISTING layout copies (matrix_update.hpp): where every stored value slot takes its value from ----
   // pass layout: positions in T.val (T = the CSR the layout was built from), through the builder re-run in map-only mode with the
   // layout's own geometry — the resident peel mask, or the row slots of the virtual rows re-planned with the accepted piece length
-  bool build_cs_value_map(const DeviceCsr &T, hipStream_t s, DevBuf<int> &map) const {
+  bool build_cs_value_map(const DeviceCsr &T, hipStream_t s, DevBuf<int> &map, const Options &o) const {
     if (!cs.ok) return false;
     if (cs_virt_lp <= 0) return cs.build_value_map(T.rowptr.p, T.col.p, nnz, s, npeel > 0 ? peel_mask.p : nullptr, map);
     std::vector<int> rp((size_t)rows + 1);
     rowptr.download(rp.data(), rp.size(), s);
     HIP_CHECK(hipStreamSynchronize(s));
     VirtPlan P;
-    if (!cs_plan_virtual(rp.data(), rows, cs_virt_lp, std::max(cs_virt_lp, peel_threshold(1)), P)) return false;
+    if (!cs_plan_virtual(rp.data(), rows, cs_virt_lp, std::max(cs_virt_lp, peel_threshold(1, o)), P, o.cs_rpt)) return false;
     if (P.R != cs.R || P.rpt != cs.rpt || P.nchunks != cs.nchunks || P.Rr != cs.Rr || P.Rp != cs.Rp || P.V != cs.npieces) return false;
     DevBuf<int2> d_info;
     DevBuf<int> vslot;
@@ -398,8 +396,9 @@ struct DeviceCsr {
 };
 
 // K12 on the device: equilibrate the three resident layouts in place; D (m) and E (n) accumulate the scalings.
+// fused_finish = Options::norm_fuse ((labs) SCS_HIP_NORM_FUSE=0: the four launches of rounds 1-4; A/B, same bits)
 static void device_normalize(DeviceCsr &At, DeviceCsr &Ar, DeviceCsr *Pf, const HostCone &cone, DevBuf<double> &D,
-                             DevBuf<double> &E, hipStream_t s) {
+                             DevBuf<double> &E, hipStream_t s, bool fused_finish) {
   const int m = Ar.rows, n = At.rows;
   DevBuf<double> Dt, Et, Ep;
   Dt.alloc(m);
@@ -418,7 +417,6 @@ static void device_normalize(DeviceCsr &At, DeviceCsr &Ar, DeviceCsr *Pf, const 
     if (cone.boundaries[i] >= 1) { boff.push_back((int)count); blen.push_back(cone.boundaries[i]); }
     count += cone.boundaries[i];
   }
-  const bool fused_finish = opts().norm_fuse;  // (labs) SCS_HIP_NORM_FUSE=0: the four launches of rounds 1-4 (A/B; same bits)
   DevBuf<int> dboff, dblen;
   const int nblocks = (int)boff.size();
   if (nblocks) { dboff.upload(boff.data(), boff.size(), s); dblen.upload(blen.data(), blen.size(), s); }

@@ -15,23 +15,24 @@ struct TmpStream {
   ~TmpStream() { if (s) (void)hipStreamDestroy(s); }
 };
 
-static void upload_for_spmv(const ScsMatrix *A, int transpose, DeviceCsr &M, hipStream_t s) {
+// Each entry point below refreshes the options, takes the current struct ONCE and hands that reference to the temporary objects it builds.
+static void upload_for_spmv(const ScsMatrix *A, int transpose, DeviceCsr &M, hipStream_t s, const Options &o) {
   HostCsr ar;
   csc_to_csr(A->m, A->n, A->p, A->i, A->x, ar);
-  const bool host = DeviceCsr::host_setup();
+  const bool host = o.host_setup;
   DeviceCsr T;  // the other orientation: what the device builder of the column-sorted copy reads
   if (transpose) {
-    M.upload(A->n, A->m, A->p, A->i, A->x, s);
-    if (host) { M.build_cs_host(A->p, A->i, A->x, s, /*kind=*/1); return; }
-    if (!cs_wanted(M.rows, M.cols, M.nnz)) return;
-    T.upload(A->m, A->n, ar.rowptr.data(), ar.col.data(), ar.val.data(), s, /*allow_slab=*/false);
+    M.upload(A->n, A->m, A->p, A->i, A->x, s, o);
+    if (host) { M.build_cs_host(A->p, A->i, A->x, s, /*kind=*/1, o); return; }
+    if (!M.cs_wanted_here(o)) return;
+    T.upload(A->m, A->n, ar.rowptr.data(), ar.col.data(), ar.val.data(), s, o, /*allow_slab=*/false);
   } else {
-    M.upload(A->m, A->n, ar.rowptr.data(), ar.col.data(), ar.val.data(), s);
-    if (host) { M.build_cs_host(ar.rowptr.data(), ar.col.data(), ar.val.data(), s, /*kind=*/0); return; }
-    if (!cs_wanted(M.rows, M.cols, M.nnz)) return;
-    T.upload(A->n, A->m, A->p, A->i, A->x, s, /*allow_slab=*/false);
+    M.upload(A->m, A->n, ar.rowptr.data(), ar.col.data(), ar.val.data(), s, o);
+    if (host) { M.build_cs_host(ar.rowptr.data(), ar.col.data(), ar.val.data(), s, /*kind=*/0, o); return; }
+    if (!M.cs_wanted_here(o)) return;
+    T.upload(A->n, A->m, A->p, A->i, A->x, s, o, /*allow_slab=*/false);
   }
-  M.build_cs_dev(T, s, /*kind=*/transpose != 0 ? 1 : 0);
+  M.build_cs_dev(T, s, /*kind=*/transpose != 0 ? 1 : 0, o);
 }
 
 int scs_hip_spmv(const ScsMatrix *A, const scs_float *x, scs_float *y, int transpose) {
@@ -41,7 +42,7 @@ int scs_hip_spmv(const ScsMatrix *A, const scs_float *x, scs_float *y, int trans
     if (!validate_matrix(A, A->m, A->n)) throw std::runtime_error("invalid matrix");
     TmpStream ts;
     DeviceCsr M;
-    upload_for_spmv(A, transpose, M, ts.s);
+    upload_for_spmv(A, transpose, M, ts.s, opts());
     DevBuf<double> dx, dy;
     dx.upload(x, M.cols, ts.s);
     dy.upload(y, M.rows, ts.s);
@@ -68,6 +69,7 @@ static int cs_layout_host_spmv_impl(const ScsMatrix *A, const scs_float *x, scs_
   try {
     set_last_error("");
     refresh_options();
+    const Options &o = opts();
     if (!validate_matrix(A, A->m, A->n)) throw std::runtime_error("invalid matrix");
     HostCsr ar;
     const int *rp = A->p, *ci = A->i;
@@ -84,10 +86,10 @@ static int cs_layout_host_spmv_impl(const ScsMatrix *A, const scs_float *x, scs_
     std::vector<unsigned> mk;
     {
       int R0, rpt0;
-      cs_pick_geometry(rows, R0, rpt0, split);
+      cs_pick_geometry(rows, R0, rpt0, split, o.cs_rpt);
       if (rpt > 0) rpt0 = rpt;
       const int thresh = cs_peel_threshold(rpt0);
-      if (opts().cs_peel)
+      if (o.cs_peel)
         for (int r = 0; r < rows; ++r)
           if (rp[r + 1] - rp[r] > thresh) {
             if (mk.empty()) mk.assign(((size_t)rows + 31) / 32, 0u);
@@ -98,11 +100,11 @@ static int cs_layout_host_spmv_impl(const ScsMatrix *A, const scs_float *x, scs_
     const bool pieces = piece_len > 0;
     if (pieces) {
       int R0, rpt0;
-      cs_pick_geometry(rows, R0, rpt0, 1);
+      cs_pick_geometry(rows, R0, rpt0, 1, o.cs_rpt);
       mk.clear();
-      if (!cs_plan_virtual(rp, rows, piece_len, std::max(piece_len, cs_peel_threshold(rpt0)), P)) return 1;
+      if (!cs_plan_virtual(rp, rows, piece_len, std::max(piece_len, cs_peel_threshold(rpt0)), P, o.cs_rpt)) return 1;
       if (!build_cs_virtual(rp, ci, v, rows, cols, P, h)) return 1;
-    } else if (!build_cs(rp, ci, v, rows, cols, h, rpt, split, mk.empty() ? nullptr : mk.data())) return 1;
+    } else if (!build_cs(rp, ci, v, rows, cols, h, rpt > 0 ? rpt : o.cs_rpt, split, mk.empty() ? nullptr : mk.data())) return 1;
     std::vector<double> tpart((size_t)P.V, 0.0);
     if (!mk.empty())
       for (int r = 0; r < rows; ++r)
@@ -180,7 +182,7 @@ double scs_hip_spmv_bench(const ScsMatrix *A, int transpose, int reps) {
     refresh_options();
     TmpStream ts;
     DeviceCsr M;
-    upload_for_spmv(A, transpose, M, ts.s);
+    upload_for_spmv(A, transpose, M, ts.s, opts());
     std::vector<double> hx(M.cols);
     for (int i = 0; i < M.cols; ++i) hx[i] = 1.0 + 1e-3 * (i % 977);
     DevBuf<double> dx, dy;
@@ -238,7 +240,7 @@ static int proj_cone_impl(scs_float *x, const ScsCone *k, scs_int m, int dual) {
     set_last_error("");
     refresh_options();
     for (int attempt = 0; attempt < 2; ++attempt) {
-      ScsHipWork w;
+      ScsHipWork w(opts());
       TmpStream ts;
       oneshot_cone_work(w, k, m, /*warm=*/0, ts.s, attempt > 0);
       DevBuf<double> dx;
@@ -280,7 +282,7 @@ int scs_hip_proj_cone_seq(scs_float *xs, const ScsCone *k_in, scs_int m, int dua
     if (count < 0 || !xs) throw std::runtime_error("invalid sequence");
     std::vector<double> out((size_t)count * (size_t)std::max(m, 0));  // the inputs stay intact until the whole sequence went through
     for (int attempt = 0; attempt < 2; ++attempt) {
-      ScsHipWork w;
+      ScsHipWork w(opts());
       TmpStream ts;
       // warm = 1: as inside the ADMM loop, the eigenvectors (and every other cone's warm-start state) carry over from call to call
       oneshot_cone_work(w, k, m, /*warm=*/1, ts.s, attempt > 0);
@@ -339,7 +341,7 @@ static int kkt_solve_entry(const ScsMatrix *A, const ScsMatrix *P, const scs_flo
     set_last_error("");
     refresh_options();
     if (!validate_matrix(A, A->m, A->n)) throw std::runtime_error("invalid A");
-    ScsHipWork w;
+    ScsHipWork w(opts());
     TmpStream ts;
     hipStream_t s = ts.s;
     w.stream = s;
@@ -347,23 +349,24 @@ static int kkt_solve_entry(const ScsMatrix *A, const ScsMatrix *P, const scs_flo
     w.n = n; w.m = m; w.l = (long)n + m + 1;
     w.has_P = P != nullptr;
     HIP_CHECK(hipHostMalloc((void **)&w.h_flags, sizeof(int) * F_COUNT));
-    w.At.upload(n, m, A->p, A->i, A->x, s);
+    const Options &o = w.opt;
+    w.At.upload(n, m, A->p, A->i, A->x, s, o);
     {
       HostCsr ar;
       csc_to_csr(m, n, A->p, A->i, A->x, ar);
-      w.Ar.upload(m, n, ar.rowptr.data(), ar.col.data(), ar.val.data(), s);
+      w.Ar.upload(m, n, ar.rowptr.data(), ar.col.data(), ar.val.data(), s, o);
     }
     if (P) {
       HostCsr pf;
       std::vector<double> pdiag;
       sym_expand(n, P->p, P->i, P->x, pf, pdiag);
-      w.Pf.upload(n, n, pf.rowptr.data(), pf.col.data(), pf.val.data(), s);
+      w.Pf.upload(n, n, pf.rowptr.data(), pf.col.data(), pf.val.data(), s, o);
       w.Pdiag.upload(pdiag.data(), n, s);
     }
-    if (!DeviceCsr::host_setup()) {
-      w.At.build_cs_dev(w.Ar, s, /*kind=*/1);
-      w.Ar.build_cs_dev(w.At, s, /*kind=*/0);
-      if (P) w.Pf.build_cs_dev(w.Pf, s, /*kind=*/2);
+    if (!o.host_setup) {
+      w.At.build_cs_dev(w.Ar, s, /*kind=*/1, o);
+      w.Ar.build_cs_dev(w.At, s, /*kind=*/0, o);
+      if (P) w.Pf.build_cs_dev(w.Pf, s, /*kind=*/2, o);
     }
     std::vector<double> dr(w.l, 10.0);
     std::copy(diag_r, diag_r + n + m, dr.begin());
@@ -409,21 +412,22 @@ int scs_hip_normalize(ScsMatrix *A, ScsMatrix *P, scs_float *b, scs_float *c, co
     TmpStream ts;
     hipStream_t s = ts.s;
     const int m = A->m, n = A->n;
+    const Options &o = opts();
     DeviceCsr At, Ar, Pf;
-    At.upload(n, m, A->p, A->i, A->x, s, false);
+    At.upload(n, m, A->p, A->i, A->x, s, o, false);
     {
       HostCsr ar;
       csc_to_csr(m, n, A->p, A->i, A->x, ar);
-      Ar.upload(m, n, ar.rowptr.data(), ar.col.data(), ar.val.data(), s, false);
+      Ar.upload(m, n, ar.rowptr.data(), ar.col.data(), ar.val.data(), s, o, false);
     }
     if (P) {
       HostCsr pf;
       std::vector<double> pdiag;
       sym_expand(n, P->p, P->i, P->x, pf, pdiag);
-      Pf.upload(n, n, pf.rowptr.data(), pf.col.data(), pf.val.data(), s, false);
+      Pf.upload(n, n, pf.rowptr.data(), pf.col.data(), pf.val.data(), s, o, false);
     }
     DevBuf<double> dD, dE;
-    device_normalize(At, Ar, P ? &Pf : nullptr, cone, dD, dE, s);
+    device_normalize(At, Ar, P ? &Pf : nullptr, cone, dD, dE, s, o.norm_fuse);
     HostScaling sc;
     sc.D.resize(m);
     sc.E.resize(n);
@@ -469,7 +473,7 @@ ScsHipAa *scs_hip_aa_init(scs_int dim, scs_int mem, scs_int type1, scs_float reg
     a->device = current_device();
     HIP_CHECK(hipSetDevice(a->device));
     HIP_CHECK(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
-    a->aa.init(dim, mem, type1, regularization, relaxation, safeguard_factor, max_weight_norm, a->stream);
+    a->aa.init(dim, mem, type1, regularization, relaxation, safeguard_factor, max_weight_norm, a->stream, opts().aa_gram);
     a->f.alloc_zero((size_t)dim, a->stream);
     a->x.alloc_zero((size_t)dim, a->stream);
     a->bad.alloc_zero(1, a->stream);
@@ -485,7 +489,6 @@ scs_float scs_hip_aa_apply(ScsHipAa *a, scs_float *f, const scs_float *x) {
   if (!a || !f || !x) return NAN;
   try {
     set_last_error("");
-    refresh_options();
     HIP_CHECK(hipSetDevice(a->device));
     a->f.upload(f, (size_t)a->aa.dim, a->stream);
     a->x.upload(x, (size_t)a->aa.dim, a->stream);
@@ -503,7 +506,6 @@ scs_int scs_hip_aa_safeguard(ScsHipAa *a, scs_float *f_new, scs_float *x_new) {
   if (!a || !f_new || !x_new) return -2;
   try {
     set_last_error("");
-    refresh_options();
     HIP_CHECK(hipSetDevice(a->device));
     if (!a->aa.success) return 0;  // nothing to test (and no asynchronous upload of the caller's buffers left in flight)
     a->f.upload(f_new, (size_t)a->aa.dim, a->stream);
@@ -547,7 +549,6 @@ __global__ void k_copy4(const double4 *__restrict__ src, double4 *dst, size_t n4
 double scs_hip_copy_bandwidth(size_t bytes, int reps) {
   try {
     set_last_error("");
-    refresh_options();
     TmpStream ts;
     const size_t n4 = bytes / sizeof(double4);
     DevBuf<double4> a, b;

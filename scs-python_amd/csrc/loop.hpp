@@ -175,7 +175,7 @@ static scs_int solve_impl(ScsHipWork *w, ScsSolution *sol, ScsInfo *info, scs_in
     }
   }
   if (csv) std::fclose(csv);
-  if (ScsHipWork::debug_pipe()) {
+  if (w->debug_pipe()) {
     std::fprintf(stderr, "[scs-hip] iterations %d, run-ahead stalls %d, CG steps of the last 8 solves:", i, w->pipe_stalls);
     for (int v : w->cg_hist) std::fprintf(stderr, " %d", v);
     std::fprintf(stderr, "\n");

@@ -223,7 +223,7 @@ static void build_value_maps(ScsHipWork *w) {
       DeviceCsr &M = *lay[k].M;
       const DeviceCsr &T = *lay[k].T;
       if (M.cs.ok) {
-        if (!M.build_cs_value_map(T, s, *lay[k].cs_map))
+        if (!M.build_cs_value_map(T, s, *lay[k].cs_map, ms.opt))
           throw std::runtime_error("scs_hip_update_matrix: the pass layout could not be re-derived with the geometry scs_init chose");
         hipLaunchKernelGGL(k_map_check, dim3(vec_blocks((long)M.cs.val.n)), dim3(kVecThreads), 0, s, (const double *)M.cs.val.p,
                            (const int *)lay[k].cs_map->p, (const double *)T.val.p, (long)M.cs.val.n, (long)T.nnz, bad.p);
@@ -242,7 +242,7 @@ static void build_value_maps(ScsHipWork *w) {
     throw;
   }
   vm.built = true;
-  if (opts().debug & DBG_SETUP)  // SCS_HIP_DEBUG=setup: what was mapped (the tests read the layout kinds off this line)
+  if (ms.opt.debug & DBG_SETUP)  // SCS_HIP_DEBUG=setup: what was mapped (the tests read the layout kinds off this line)
     std::fprintf(stderr, "[scs-hip] value maps: CSR(A) %zu, CSR(P) %zu; pass layouts A' %zu, A %zu, P %zu slots (peeled rows %d, %d, %d; pieces %d, %d, %d); "
                  "slabs A' %zu, A %zu, P %zu slots\n", vm.ar.n, vm.pf.n, vm.at_cs.n, vm.ar_cs.n, vm.pf_cs.n,
                  ms.At.cs_virt_lp > 0 ? 0 : ms.At.npeel, ms.Ar.cs_virt_lp > 0 ? 0 : ms.Ar.npeel, ms.Pf.cs_virt_lp > 0 ? 0 : ms.Pf.npeel,
@@ -320,7 +320,7 @@ static void update_matrix_impl(ScsHipWork *w, const double *Ax, const double *Px
   if (px) vm_gather(ms.Pf.val.p, vm.pf, px, ms.Pf.nnz, nullptr, /*nontemporal=*/false, s);
   // ---- equilibrate in place, as scs_init ----
   if (w->normalized) {
-    device_normalize(ms.At, ms.Ar, w->has_P ? &ms.Pf : nullptr, w->cone, ms.D, ms.E, s);
+    device_normalize(ms.At, ms.Ar, w->has_P ? &ms.Pf : nullptr, w->cone, ms.D, ms.E, s, ms.opt.norm_fuse);
     adopt_equilibration(w);
   }
   pool.reset();

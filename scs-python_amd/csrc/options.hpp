@@ -1,13 +1,22 @@
 // options.hpp — every environment variable the library reads, in ONE place (round 6).
 //
 // The product has 17 runtime knobs (INTEGRATION.md "Runtime knobs"; the Python loader adds SCS_HIP_LIB, SCS_HIP_RUNTIME and shares
-// SCS_HIP_RUNTIME_ENV).  They are parsed HERE, once per scs_init / kernel-level entry point (refresh_options(): a test may change the
-// environment between two workspaces of one process; a workspace keeps what it was created with), never at the point of use.
+// SCS_HIP_RUNTIME_ENV).  They are parsed HERE (refresh_options(): a test may change the environment between two workspaces of one
+// process), never at the point of use, and every reader is handed the struct it reads:
+//   per workspace   scs_init takes opts() once, right after refresh_options(), and the matrix set keeps that snapshot (work.hpp
+//                   MatrixSet::opt, ScsHipWork::opt).  Layouts, cone pipelines, the Anderson factorisation, run-ahead and diagnostics of
+//                   the workspace read it for good; scs_hip_clone shares the set and with it the snapshot; scs_hip_update_matrix re-derives
+//                   layouts under it.  A solve re-reads nothing: no setenv and no other thread's scs_init changes a live workspace.
+//   per batch call  what spans workspaces — SCS_HIP_DEBUG=group, SCS_HIP_SHARED_TILE (labs) — is read once by scs_hip_solve_batch
+//                   (and its device twin) and handed down (batch.hpp GroupSolve::opt); the kernel-level entry points (lab_entries.hpp) hand
+//                   theirs to the temporary objects they build.
+//   process-wide    SCS_HIP_STREAMS, SCS_HIP_POOL_MB, SCS_HIP_CTRLC, SCS_HIP_RUNTIME_ENV (read once where they are used) and, labs,
+//                   SCS_HIP_POOL_POISON (the block pool is the process's: common.hpp DevPool::get reads the global).
 // Everything else that rounds 1-5 could switch at run time — the experiments that lost and still have code (cooperative launches, the
 // in-kernel combine of split layouts ...) and the lab switches of the kernels — is a compile-time default in
 // the product and only reads the environment in the `-DSCS_HIP_LABS` build (scs-python_amd/Makefile `make labs` -> libscs_hip_labs.so,
-// used by tools/ and by the tests marked `labs`).  Four closed experiments of the CG path and the older
-// schedules of the column-sorted SpMV have no code any more: DESIGN.md §4 and its column-sorted SpMV section.
+// used by tools/ and by the tests marked `labs`).  Four closed experiments of the CG path, the older schedules of the column-sorted
+// SpMV and the lab switches nothing set any more have no code: DESIGN.md §4, its column-sorted SpMV section and "Retired lab switches".
 #pragma once
 #include <atomic>
 #include <cstdlib>
@@ -22,7 +31,7 @@ namespace scship {
 enum : unsigned { DBG_PIPE = 1u, DBG_GROUP = 2u, DBG_SETUP = 4u, DBG_TOL = 8u };
 
 struct Options {
-  // ------------------------------------------------------------------ product knobs (per workspace)
+  // ------------------------------------------------------------------ product knobs (per workspace; `debug` group: per batch call)
   bool pipeline = true;        // SCS_HIP_PIPELINE=0: the host looks at the CG flags in every iteration (no run-ahead)
   int pipe_chunk = 0;          // SCS_HIP_PIPELINE=N (N >= 2): run-ahead with CG chunks of N steps (tests: forces stalls)
   bool host_setup = false;     // SCS_HIP_SETUP=host: transposition / layout builders on the host (fallback, entry-for-entry identical)
@@ -44,14 +53,12 @@ struct Options {
   // ------------------------------------------------------------------ labs (compile-time defaults in the product)
   bool psd_coop = false;       // hipLaunchCooperativeKernel for the multi-CU sweeps: ~2 ms per launch in a warm process
   bool cs_combine = false;     // in-kernel combine of split layouts: eats the gather gain
-  int cs_rpt = 0, cs_split_a = 0, cs_split_at = 0, cs_split_p = 0;
-  bool cs_peel = true, cs_peel_ladder = true, cs_virt = true;
-  int slab_rpt = 0, slab_shift = 17;
-  bool arena = true, cg_fuse = true, norm_fuse = true, soc_psd_fuse = true, dense_full_gemv = true, aa_fast = true, wait_spin = false;
-  int chunk_window = 3, group_predict = 1, group_max = 1024, group_lanes = 1, group_min = 16, aa_waves1 = 2048;
-  double psd_gate_k = 0., psd_gate_off = 0., psd_gate_omega = 0., psd_tol_k = 1e-2, psd_tol_max = 1e-3;
-  bool psd_la = true, psd_mc_nocheck = false, psd_small_one_wave = false;
-  bool pool_poison = false;
+  int cs_rpt = 0, cs_split_a = 0, cs_split_at = 0;
+  bool cs_peel = true, cs_virt = true;
+  bool cg_fuse = true, norm_fuse = true, soc_psd_fuse = true;
+  double psd_tol_k = 1e-2;
+  bool psd_la = true, psd_mc_nocheck = false;
+  bool pool_poison = false;     // (process-wide: the block pool is shared by every workspace)
   bool shared_tile = false;    // SCS_HIP_SHARED_TILE=1: members of a group on one matrix set read it once per tile of four (batch.hpp
                                // k_spmv_stream_tiled) instead of per-member launches over the shared storage; not measured to win yet
 
@@ -92,36 +99,17 @@ struct Options {
     auto pos_dbl = [](const char *name, double dflt) { const char *e = getenv(name); const double v = e ? atof(e) : 0.; return v > 0. ? v : dflt; };
     o.psd_coop = is1(getenv("SCS_HIP_PSD_COOP"));
     o.cs_combine = is1(getenv("SCS_HIP_CS_COMBINE"));
-    o.cs_rpt = pos_int("SCS_HIP_CS_RPT", 0);
+    { const int v = pos_int("SCS_HIP_CS_RPT", 0); o.cs_rpt = (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) ? v : 0; }  // full chunks of 1024 * rpt rows
     o.cs_split_a = pos_int("SCS_HIP_CS_SPLIT_A", 0);
     o.cs_split_at = pos_int("SCS_HIP_CS_SPLIT_AT", 0);
-    o.cs_split_p = pos_int("SCS_HIP_CS_SPLIT_P", 0);
     o.cs_peel = !is0(getenv("SCS_HIP_CS_PEEL"));
-    o.cs_peel_ladder = !is0(getenv("SCS_HIP_CS_PEEL_LADDER"));
     o.cs_virt = !is0(getenv("SCS_HIP_CS_VIRT"));
-    o.slab_rpt = pos_int("SCS_HIP_SLAB_RPT", 0);
-    { const int v = pos_int("SCS_HIP_SLAB_SHIFT", 17); o.slab_shift = (v >= 10 && v <= 24) ? v : 17; }
-    o.arena = !is0(getenv("SCS_HIP_ARENA"));
     o.cg_fuse = !is0(getenv("SCS_HIP_CG_FUSE"));
     o.norm_fuse = !is0(getenv("SCS_HIP_NORM_FUSE"));
     o.soc_psd_fuse = !is0(getenv("SCS_HIP_SOC_PSD_FUSE"));
-    if (const char *e = getenv("SCS_HIP_DENSE_GEMV")) o.dense_full_gemv = e[0] != 'h';
-    o.aa_fast = !is0(getenv("SCS_HIP_AA_FAST"));
-    if (const char *e = getenv("SCS_HIP_WAIT")) o.wait_spin = e[0] == 's';
-    { const int v = pos_int("SCS_HIP_CHUNK_WINDOW", 3); o.chunk_window = v < 1 ? 1 : (v > 8 ? 8 : v); }
-    if (const char *e = getenv("SCS_HIP_GROUP_PREDICT")) o.group_predict = atoi(e);
-    o.group_max = pos_int("SCS_HIP_GROUP_MAX", 1024);
-    o.group_lanes = pos_int("SCS_HIP_GROUP_LANES", 1);
-    o.group_min = pos_int("SCS_HIP_GROUP_MIN", 16);
-    o.aa_waves1 = pos_int("SCS_HIP_AA_WAVES1", 2048);
-    o.psd_gate_k = pos_dbl("SCS_HIP_PSD_GATE_K", 0.);
-    o.psd_gate_off = pos_dbl("SCS_HIP_PSD_GATE_OFF", 0.);
-    o.psd_gate_omega = pos_dbl("SCS_HIP_PSD_GATE_OMEGA", 0.);
     o.psd_tol_k = pos_dbl("SCS_HIP_PSD_TOL_K", 1e-2);
-    o.psd_tol_max = pos_dbl("SCS_HIP_PSD_TOL_MAX", 1e-3);
     o.psd_la = !is0(getenv("SCS_HIP_PSD_LA"));
     o.psd_mc_nocheck = getenv("SCS_HIP_PSD_MC_NOCHECK") != nullptr;
-    o.psd_small_one_wave = is1(getenv("SCS_HIP_PSD_SMALL_WAVES"));
     o.pool_poison = is1(getenv("SCS_HIP_POOL_POISON"));
     if (const char *e = getenv("SCS_HIP_SHARED_TILE")) o.shared_tile = e[0] != '0';
 #endif
@@ -136,17 +124,19 @@ inline std::atomic<const Options *> &options_ptr() {
   static std::atomic<const Options *> p{new Options(Options::parse())};
   return p;
 }
-// what the NEXT workspace / kernel-level call sees (the environment as it was at the last refresh_options())
+// what the NEXT workspace / batch call / kernel-level call takes its snapshot from (the environment as it was at the last
+// refresh_options()).  Called in the bodies of the entry points only: everything below them reads the reference it was handed.
 inline const Options &opts() { return *options_ptr().load(std::memory_order_acquire); }
-// re-read the environment: first thing in scs_init and in every kernel-level entry point.  A new struct is only published when an
-// SCS_HIP_* variable changed since the last call, so concurrent scs_init calls under one environment publish nothing.
+// re-read the environment: first thing in scs_init, the batch entries and the kernel-level entry points that read options.  A new
+// struct is only published when an SCS_HIP_* variable changed since the last call, so concurrent scs_init calls under one
+// environment publish nothing.
 inline void refresh_options() {
   static std::mutex m;
   static std::string last = "\x01";  // (never equal to a real signature: the first call publishes what it parsed)
+  std::lock_guard<std::mutex> lk(m);  // (before the walk: two threads must not publish in the opposite order of what they read)
   std::string sig;
   for (char **e = environ; e && *e; ++e)
     if (std::strncmp(*e, "SCS_HIP_", 8) == 0) { sig += *e; sig += '\n'; }
-  std::lock_guard<std::mutex> lk(m);
   if (sig != last) {
     options_ptr().store(new Options(Options::parse()), std::memory_order_release);
     last = sig;

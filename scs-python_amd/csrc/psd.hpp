@@ -2097,7 +2097,7 @@ __global__ __launch_bounds__(64) void k_proj_psd_small(double *x, PsdBatch B, do
 // in every round, so the copies ping-pong: one barrier per round.  After N - 1 rounds (one sweep) everything is back at its home
 // position, so the sweep test, the warm start and the reconstruction see the ordinary layout.  Same rotation formula, same
 // sweep test and reconstruction as the one-wavefront kernel; the pairs meet in a different order, so the results agree with it
-// to the sweep tolerance, not bit for bit (SCS_HIP_PSD_SMALL_WAVES=1 runs the one-wavefront kernel).
+// to the sweep tolerance, not bit for bit (the one-wavefront kernel, k_proj_psd_small, stays for tools/psd_lab.hip).
 constexpr int kPsdSmallThreads = 256;
 __device__ __forceinline__ int psd_small_next_pos(int a, int H) {
   if (H == 1 || a == 0) return a;

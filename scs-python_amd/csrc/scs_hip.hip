@@ -62,7 +62,6 @@ extern "C" {
 ScsWork *scs_init(const ScsData *d, const ScsCone *k, const ScsSettings *stgs) {
   try {
     set_last_error("");
-    refresh_options();
     const ScsCone kk = short_cone(k);
     return init_impl(d, k ? &kk : nullptr, stgs);
   } catch (const std::exception &e) {
@@ -74,7 +73,6 @@ ScsWork *scs_init(const ScsData *d, const ScsCone *k, const ScsSettings *stgs) {
 ScsWork *scs_hip_init_linsys(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys) {
   try {
     set_last_error("");
-    refresh_options();
     const ScsCone kk = short_cone(k);
     return init_impl(d, k ? &kk : nullptr, stgs, linsys);
   } catch (const std::exception &e) {
@@ -87,7 +85,6 @@ ScsWork *scs_hip_init_linsys(const ScsData *d, const ScsCone *k, const ScsSettin
 ScsWork *scs_init_spectral(const ScsData *d, const ScsCone *k, const ScsSettings *stgs) {
   try {
     set_last_error("");
-    refresh_options();
     return init_impl(d, k, stgs);
   } catch (const std::exception &e) {
     set_last_error(e.what());
@@ -98,7 +95,6 @@ ScsWork *scs_init_spectral(const ScsData *d, const ScsCone *k, const ScsSettings
 ScsWork *scs_hip_init_linsys_spectral(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys) {
   try {
     set_last_error("");
-    refresh_options();
     return init_impl(d, k, stgs, linsys);
   } catch (const std::exception &e) {
     set_last_error(e.what());
@@ -138,8 +134,7 @@ static void fill_failed(ScsHipWork *w, ScsSolution *sol, bool dev_io) {
 static scs_int solve_entry(ScsWork *w, ScsSolution *sol, ScsInfo *info, scs_int warm_start, bool dev_io) {
   try {
     set_last_error("");
-    refresh_options();
-    const double scale_entry = w->scale;
+    const double scale_entry = w->scale;  // (nothing of the environment is read here: the workspace has its snapshot, options.hpp)
     try {
       return solve_impl(w, sol, info, warm_start, dev_io);
     } catch (const SpinTimeout &) {
@@ -221,13 +216,11 @@ int scs_hip_work_device(const ScsWork *w) { return w ? w->device : -1; }
 // layouts, one-launch cone kernels (GroupSolve::member_ok / same_shape) — advance in lock step through the grouped
 // kernels of batch.hpp; the others are solved by scs_solve's own loop.  Every info[i] / sol[i] is filled exactly as
 // scs_solve(w[i], sol[i], info[i], warm_start) would (iterates are bit-identical).
-// A shape class is one group (up to SCS_HIP_GROUP_MAX members, default 1024).  Cutting it into several groups that run
-// concurrently — one host thread and one stream each, SCS_HIP_GROUP_LANES > 1 — was built and measured (512 config-5
-// problems, solve phase): 1 x 512: 4.0 s, 4 x 128: 4.2 s, 8 x 64: 6.4 s, 8 lanes of 32: 10.7 s — launches and
-// synchronisations issued from several host threads contend inside the HIP runtime, as the one-stream-per-problem
-// mode showed before (profiles/r02_batch_queues.txt) => off by default.
+// A shape class is one group (cut into near-equal parts above kGroupMax members), and the groups of a call run one after the other on
+// the calling thread: several concurrently driven groups were built, measured and lost.
+// o: the options of THIS call (solve_batch_entry) — the group-level ones, batch.hpp GroupSolve::opt.
 static scs_int solve_one_group(ScsWork **works, ScsSolution **sols, ScsInfo **infos, const std::vector<int> &idx, scs_int warm_start,
-                               std::string &err, bool dev_io) {
+                               std::string &err, bool dev_io, const Options &o) {
   if (idx.size() == 1) {
     const int i = idx[0];
     const scs_int st = solve_entry(works[i], sols[i], infos[i], warm_start, dev_io);
@@ -237,7 +230,7 @@ static scs_int solve_one_group(ScsWork **works, ScsSolution **sols, ScsInfo **in
   scs_int rc = 0;
   std::vector<std::unique_lock<std::mutex>> locks;
   std::vector<hipStream_t> saved;
-  GroupSolve gs;
+  GroupSolve gs(o);
   //  every member starts out "unfinished": the catch block below marks exactly those the solve did not finish, also when
   // the exception comes before the members' begin_solve cleared their infos (caller memory); member mutexes are taken in ADDRESS
   // order, so two concurrent batches that share workspaces in different orders cannot deadlock (the Python glue sorts too)
@@ -282,24 +275,23 @@ static scs_int solve_one_group(ScsWork **works, ScsSolution **sols, ScsInfo **in
 
 // The jobs of a batch: shape classes of members that can share launches (GroupSolve::member_ok / same_shape), in the order of
 // their first member, each cut into contiguous, near-equal parts; a job of one member is solved by scs_solve.  Both
-// scs_hip_solve_batch and scs_hip_batch_plan take their groups from here (options as refresh_options() last read them).
+// scs_hip_solve_batch and scs_hip_batch_plan take their groups from here (a function of the workspaces alone).
+constexpr int kGroupMax = 1024;  // members of one group
 static std::vector<std::vector<int>> plan_batch(ScsWork *const *works, int count) {
-  const int group_max = opts().group_max, lanes = opts().group_lanes, group_min = opts().group_min;  // (labs knobs: several concurrently driven groups lost)
   std::vector<std::vector<int>> jobs;
   std::vector<char> taken((size_t)count, 0);
   for (int i = 0; i < count; ++i) {
     if (taken[(size_t)i]) continue;
     taken[(size_t)i] = 1;
     std::vector<int> cls{i};
-    if (group_max > 1 && GroupSolve::member_ok(works[i]))
+    if (GroupSolve::member_ok(works[i]))
       for (int j = i + 1; j < count; ++j)
         if (!taken[(size_t)j] && GroupSolve::member_ok(works[j]) && GroupSolve::same_shape(works[i], works[j])) {
           taken[(size_t)j] = 1;
           cls.push_back(j);
         }
     const int S = (int)cls.size();
-    int k = std::max((S + group_max - 1) / group_max, lanes > 1 ? std::min(lanes, S / group_min) : 1);
-    k = std::max(1, std::min(k, S));
+    const int k = (S + kGroupMax - 1) / kGroupMax;
     for (int part = 0; part < k; ++part) {  // contiguous, near-equal parts
       const int lo = (int)((long)S * part / k), hi = (int)((long)S * (part + 1) / k);
       jobs.emplace_back(cls.begin() + lo, cls.begin() + hi);
@@ -318,7 +310,6 @@ int scs_hip_batch_plan(ScsWork **works, scs_int count, scs_int *group_of) {
     for (int j = 0; j < i; ++j)
       if (works[j] == works[i]) { set_last_error("scs_hip_batch_plan: a workspace appears twice"); return -1; }
   }
-  refresh_options();
   int groups = 0;
   for (const std::vector<int> &job : plan_batch(works, (int)count)) {
     const int id = job.size() > 1 ? groups++ : -1;
@@ -331,37 +322,21 @@ int scs_hip_batch_plan(ScsWork **works, scs_int count, scs_int *group_of) {
 static scs_int solve_batch_entry(ScsWork **works, ScsSolution **sols, ScsInfo **infos, scs_int count, scs_int warm_start, bool dev_io) {
   InterruptListener ctrlc;  // for the whole call: members solved one after the other all see the same Ctrl-C
   refresh_options();
-  const int lanes = opts().group_lanes;
+  const Options &o = opts();  // the group-level options of this call (per-workspace ones stay what each member was created with)
   std::vector<std::vector<int>> jobs = plan_batch(works, (int)count);
   std::stable_sort(jobs.begin(), jobs.end(), [](const std::vector<int> &a, const std::vector<int> &b) { return a.size() > b.size(); });
-  const int nthreads = std::max(1, std::min(lanes, (int)jobs.size()));
-  std::atomic<size_t> next{0};
-  std::atomic<int> rc_all{0};
-  std::mutex err_mtx;
+  scs_int rc = 0;
   std::string first_err;
-  const int dflt_dev = current_device();
-  auto worker = [&]() {
-    (void)hipSetDevice(dflt_dev);
-    while (true) {
-      const size_t j = next.fetch_add(1);
-      if (j >= jobs.size()) break;
-      std::string err;
-      if (solve_one_group(works, sols, infos, jobs[j], warm_start, err, dev_io) != 0) {
-        rc_all.store(-1);
-        std::lock_guard<std::mutex> g(err_mtx);
-        if (first_err.empty()) first_err = err;
-      }
+  (void)hipSetDevice(current_device());
+  for (const std::vector<int> &job : jobs) {
+    std::string err;
+    if (solve_one_group(works, sols, infos, job, warm_start, err, dev_io, o) != 0) {
+      rc = -1;
+      if (first_err.empty()) first_err = err;
     }
-  };
-  if (nthreads == 1) {
-    worker();
-  } else {
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nthreads; ++t) pool.emplace_back(worker);
-    for (auto &t : pool) t.join();
   }
-  if (rc_all.load() != 0) set_last_error(first_err);
-  return rc_all.load();
+  if (rc != 0) set_last_error(first_err);
+  return rc;
 }
 
 scs_int scs_hip_solve_batch(ScsWork **works, ScsSolution **sols, ScsInfo **infos, scs_int count, scs_int warm_start) {

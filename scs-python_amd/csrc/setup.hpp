@@ -137,7 +137,7 @@ static void upload_cone_meta(ScsHipWork *w) {
     // split mode: one CU per matrix would leave at least half of the GPU idle.  Its V update keeps a 16-row strip of V in LDS
     // (16 x NP doubles): orders above 1280 do not fit and take the one-workgroup-per-matrix kernel (any order up to 16 kPsdMaxH)
     w->psd_split = big_total > 0 && big_total <= 128 && (size_t)16 * w->psd_max_np * sizeof(double) <= 160 * 1024;
-    if (opts().psd_split >= 0) w->psd_split = big_total > 0 && opts().psd_split == 1;  // SCS_HIP_PSD_SPLIT: A/B and tests
+    if (w->opt.psd_split >= 0) w->psd_split = big_total > 0 && w->opt.psd_split == 1;  // SCS_HIP_PSD_SPLIT: A/B and tests
   }
   HIP_CHECK(hipStreamSynchronize(s));
 }
@@ -154,8 +154,8 @@ static size_t arena_first_chunk(long l, long lookback, long annz) {
 
 // the stream, events and pinned host block of a workspace (scs_init and scs_hip_clone)
 static void init_streams_and_pinned(ScsHipWork *w) {
-  w->pipelined = opts().pipeline;     // SCS_HIP_PIPELINE=0: the host looks at the CG flags in every iteration
-  w->pipe_chunk_override = opts().pipe_chunk;
+  w->pipelined = w->opt.pipeline;     // SCS_HIP_PIPELINE=0: the host looks at the CG flags in every iteration
+  w->pipe_chunk_override = w->opt.pipe_chunk;
   w->stream = g_streams.acquire(w->device, &w->stream_shared);
   w->pooled_stream = true;
   for (auto &e : w->ev) HIP_CHECK(hipEventCreate(&e));
@@ -240,7 +240,7 @@ static void start_state(ScsHipWork *w, Mark &&mark) {
     // apply_scale_updates, the path of an adaptive-scale update: bit-identical to the solo one), a lone workspace at its first solve.
     // (small problems only, n + m <= 32768: there the chain is what scs_init costs; a large problem keeps its cold solve out of scs_solve)
     const bool small_indirect = !w->dense() && (long)n + m <= 32768;
-    w->setup_pending = (w->dense() || small_indirect) && w->mats->lazy_setup;
+    w->setup_pending = (w->dense() || small_indirect) && w->opt.lazy_setup;  // (a clone defers what its parent deferred)
   }
   if (!w->setup_pending) {
     w->set_diag_r();
@@ -281,7 +281,7 @@ static void init_state(ScsHipWork *w, Mark &&mark) {
   upload_cone_meta(w);
   // ---- AA workspace ----
   w->aa.init(l, w->stgs.acceleration_lookback, w->stgs.acceleration_type_1, w->stgs.acceleration_regularization,
-             w->stgs.acceleration_relaxation, /*safeguard_factor=*/1.0, /*max_weight_norm=*/1e10, s);
+             w->stgs.acceleration_relaxation, /*safeguard_factor=*/1.0, /*max_weight_norm=*/1e10, s, w->opt.aa_gram);
   if (w->dense()) w->dense_alloc();
   mark("vectors, cones, AA workspace");
   start_state(w, mark);
@@ -289,8 +289,9 @@ static void init_state(ScsHipWork *w, Mark &&mark) {
 
 static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys = 0) {
   const double t0 = now_ms();
-  refresh_options();  // the environment as it is NOW: this workspace keeps what it is created with (options.hpp)
-  if (linsys == 0) linsys = opts().linsys_dense ? 2 : 1;
+  refresh_options();  // the environment as it is NOW ...
+  const Options &o = opts();  // ... and the snapshot this workspace, its matrix set and its clones keep for good (options.hpp)
+  if (linsys == 0) linsys = o.linsys_dense ? 2 : 1;
   if (linsys != 1 && linsys != 2) throw std::runtime_error("unknown linear-system solver kind");
   if (!d || !k || !stgs) throw std::runtime_error("null argument");
   if (d->m <= 0 || d->n <= 0 || !d->A || !d->b || !d->c) throw std::runtime_error("invalid data dimensions");
@@ -306,7 +307,7 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
     throw std::runtime_error("libscs_hip: no HIP device available (this backend has no CPU fallback)");
   HIP_CHECK(hipSetDevice(current_device()));
 
-  std::unique_ptr<ScsHipWork> w(new ScsHipWork());
+  std::unique_ptr<ScsHipWork> w(new ScsHipWork(o));
   w->device = current_device();
   {
     std::string why;
@@ -337,7 +338,6 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
   w->mats->bl0 = w->cone.bl;
   w->mats->bu0 = w->cone.bu;
   w->mats->stgs0 = w->stgs;
-  w->mats->lazy_setup = opts().lazy_setup;
   w->mats->a_nnz_in = d->A->p[n];
   w->mats->p_nnz_in = d->P ? d->P->p[n] : 0;
   if (d->P) {  // (O(nnz(P)) over arrays validate_matrix has just walked)
@@ -358,10 +358,10 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
   init_streams_and_pinned(w.get());
   hipStream_t s = w->stream;
   // small problems (config 5: a batch of them) take their device memory from one arena (common.hpp) instead of ~100
-  // separate allocations; SCS_HIP_ARENA=0 restores exact allocations (A/B)
+  // separate allocations
   {
     const long annz = d->A->p[n];
-    if (opts().arena && annz <= (1L << 18) && w->l <= (1L << 17)) {
+    if (annz <= (1L << 18) && w->l <= (1L << 17)) {
       w->arena.reset(new Arena());
       w->mats->home = w->arena;  // (the set's buffers live in it: it stays until the last user of the set is gone)
       w->arena->stream = s;
@@ -369,7 +369,7 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
     }
   }
   ArenaScope arena_scope(w->arena.get());
-  const bool setup_timing = (opts().debug & DBG_SETUP) != 0;  // SCS_HIP_DEBUG=setup: where does scs_init spend its time
+  const bool setup_timing = (o.debug & DBG_SETUP) != 0;  // SCS_HIP_DEBUG=setup: where does scs_init spend its time
   double t_mark = now_ms();
   auto mark = [&](const char *what) {
     if (!setup_timing) return;
@@ -384,15 +384,15 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
   w->normalized = stgs->normalize != 0;
   // Device path (default): upload the caller's CSC once, transpose and (after the equilibration) build the
   // L2-blocked copies on the device; the host builders remain for SCS_HIP_SETUP=host and for rows too long to sort.
-  const bool host_build = DeviceCsr::host_setup();
+  const bool host_build = o.host_setup;
   bool slabs_pending = false;
-  w->At.upload(n, m, d->A->p, d->A->i, d->A->x, s, /*allow_slab=*/host_build);
+  w->At.upload(n, m, d->A->p, d->A->i, d->A->x, s, o, /*allow_slab=*/host_build);
   mark("A' upload (+ slab build on the host)");
   HostCsr ar, pf;  // host copies of the index arrays: only filled on the host paths
   if (host_build || !w->Ar.transpose_from(w->At, s)) {
     csc_to_csr(m, n, d->A->p, d->A->i, d->A->x, ar);
     mark("CSC -> CSR on the host");
-    w->Ar.upload(m, n, ar.rowptr.data(), ar.col.data(), ar.val.data(), s, /*allow_slab=*/host_build);
+    w->Ar.upload(m, n, ar.rowptr.data(), ar.col.data(), ar.val.data(), s, o, /*allow_slab=*/host_build);
     mark("A upload (+ slab build on the host)");
     slabs_pending = !host_build;
   } else {
@@ -402,7 +402,7 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
   if (w->has_P) {
     std::vector<double> pdiag;
     sym_expand(n, d->P->p, d->P->i, d->P->x, pf, pdiag);
-    w->Pf.upload(n, n, pf.rowptr.data(), pf.col.data(), pf.val.data(), s, /*allow_slab=*/host_build);
+    w->Pf.upload(n, n, pf.rowptr.data(), pf.col.data(), pf.val.data(), s, o, /*allow_slab=*/host_build);
     w->px.alloc_zero(n, s);
   }
   if (w->cone.bsize > 1) {  // the caller's box bounds, before the row scaling touches the working copies
@@ -412,7 +412,7 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
   }
   // ---- K12: equilibrate on the device, in place in all resident layouts ----
   if (w->normalized) {
-    device_normalize(w->At, w->Ar, w->has_P ? &w->Pf : nullptr, w->cone, w->D, w->E, s);
+    device_normalize(w->At, w->Ar, w->has_P ? &w->Pf : nullptr, w->cone, w->D, w->E, s, o.norm_fuse);
     adopt_equilibration(w.get());
   }
   mark("equilibration (device)");
@@ -421,18 +421,18 @@ static ScsHipWork *init_impl(const ScsData *d, const ScsCone *k, const ScsSettin
     // large matrices: column-sorted pass copy (spmv_cs.hpp), each built from the other orientation's CSR;
     // the L2-blocked slab copy only where the pattern does not fit that format
     // A' products feed the CG update, which takes Gp as the sum of two partial vectors: two workgroups per chunk
-    if (!w->At.build_cs_dev(w->Ar, s, /*kind=*/1)) w->At.build_slab_dev(s);
-    if (!w->Ar.build_cs_dev(w->At, s, /*kind=*/0)) w->Ar.build_slab_dev(s);
-    if (w->has_P && !w->Pf.build_cs_dev(w->Pf, s, /*kind=*/2)) w->Pf.build_slab_dev(s);
+    if (!w->At.build_cs_dev(w->Ar, s, /*kind=*/1, o)) w->At.build_slab_dev(s, o);
+    if (!w->Ar.build_cs_dev(w->At, s, /*kind=*/0, o)) w->Ar.build_slab_dev(s, o);
+    if (w->has_P && !w->Pf.build_cs_dev(w->Pf, s, /*kind=*/2, o)) w->Pf.build_slab_dev(s, o);
   }
   if (host_build) {  // SCS_HIP_SETUP=host: the column-sorted copies from the host builder, on the equilibrated values
     std::vector<double> hv;
     auto host_cs = [&](DeviceCsr &M, const int *rp, const int *ci, int kind) {
-      if (!cs_wanted(M.rows, M.cols, M.nnz)) return;
+      if (!M.cs_wanted_here(o)) return;
       hv.resize((size_t)M.nnz);
       M.val.download(hv.data(), (size_t)M.nnz, s);
       HIP_CHECK(hipStreamSynchronize(s));
-      M.build_cs_host(rp, ci, hv.data(), s, kind);
+      M.build_cs_host(rp, ci, hv.data(), s, kind, o);
     };
     host_cs(w->At, d->A->p, d->A->i, 1);
     host_cs(w->Ar, ar.rowptr.data(), ar.col.data(), 0);
@@ -457,7 +457,7 @@ static ScsHipWork *clone_impl(ScsHipWork *src) {
   if (!src) throw std::runtime_error("null argument");
   std::lock_guard<std::mutex> lock(src->mtx);
   HIP_CHECK(hipSetDevice(src->device));
-  std::unique_ptr<ScsHipWork> w(new ScsHipWork(src->mats));
+  std::unique_ptr<ScsHipWork> w(new ScsHipWork(src->mats));  // (the set carries the parent's options snapshot: nothing of the environment is read)
   const MatrixSet &ms = *w->mats;
   w->device = src->device;
   w->cone = src->cone;  // (box bounds already follow the row scaling; nothing changes them after scs_init)
@@ -474,8 +474,6 @@ static ScsHipWork *clone_impl(ScsHipWork *src) {
   for (double x : w->b_orig) w->nm_b_orig = std::max(w->nm_b_orig, std::fabs(x));
   for (double x : w->c_orig) w->nm_c_orig = std::max(w->nm_c_orig, std::fabs(x));
   init_streams_and_pinned(w.get());
-  w->pipelined = src->pipelined;  // (what the parent was created with, not what the environment says now)
-  w->pipe_chunk_override = src->pipe_chunk_override;
   hipStream_t s = w->stream;
   const int n = w->n;
   if (src->arena) {  // as the parent: its own arena, sized without the matrix layouts

@@ -326,13 +326,14 @@ struct DeviceCs {
   }
   // layout for the matrix M (rows_ x cols_) whose TRANSPOSE is the CSR (tptr, trow, tval) with cols_ rows.
   // false (and nothing kept) when the pattern does not fit the format: the caller keeps its other layouts.
-  // force_R / force_rpt: the caller's geometry (virtual rows: `trow` holds row SLOTS, rows_ = nchunks * R of them)
+  // force_R / force_rpt: the caller's geometry (virtual rows: `trow` holds row SLOTS, rows_ = nchunks * R of them; force_rpt alone:
+  // full chunks of 1024 * force_rpt rows, cs_pick_geometry)
   bool build_from_transpose(int rows_, int cols_, const int *tptr, const int *trow, const double *tval, long nnz, hipStream_t s,
                             int split_ = 1, const unsigned *peel = nullptr, int force_R = 0, int force_rpt = 0) {
     release();
     rows = rows_; cols = cols_; split = split_;
-    cs_pick_geometry(rows, R, rpt, split);
-    if (force_R > 0) { R = force_R; rpt = force_rpt; }
+    cs_pick_geometry(rows, R, rpt, split, force_rpt);
+    if (force_R > 0) R = force_R;
     nchunks = (rows + R - 1) / R;
     const int nblocks = (int)((nnz + kCsBlock - 1) / kCsBlock);
     if (nnz <= 0 || nchunks > kCsMaxChunks || (long)nchunks * nblocks > (long)kScanTile * kScanTile || nnz > 2000000000L) return false;

@@ -366,14 +366,9 @@ __global__ __launch_bounds__(kSpmvThreads) void k_spmv_stream(CsrView A, const d
 // summed in ascending-column order: bit-identical to the CSR-stream kernel and to
 // the oracle.  Extra bytes vs CSR: 2 B * rows * S of uint16 row offsets.
 // ---------------------------------------------------------------------------
-constexpr int kSlabShiftDefault = 17;        // 2^17 columns = 1 MiB of fp64 per slab
+constexpr int kSlabShift = 17;               // 2^17 columns = 1 MiB of fp64 per slab (DeviceCsr::s_shift records it per copy)
 constexpr int kSlabStage = 3072;             // LDS products per pass (24 KiB)
 constexpr int kSlabTargetWgs = 512;          // 2 resident workgroups per CU on 256 CUs
-inline int slab_shift() {
-  const int v = opts().slab_shift;  // (labs knob)
-  return (v >= 10 && v <= 24) ? v : kSlabShiftDefault;
-}
-
 constexpr int kSlabRoffPad = 16;  // row offsets of a segment: R + 1 used, stride R + 16 ushorts (32-byte aligned rows of 16)
 struct SlabView {
   const int *segptr;            // nchunks*S + 1 offsets into val/col (multiples of 4)
@@ -391,7 +386,6 @@ struct HostSlab {
 };
 
 inline int slab_pick_rows(int rows) {
-  { const int v = opts().slab_rpt; if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) return 256 * v; }  // (labs knob)
   int rpt = 1;
   while (rpt < 16 && (long)kSlabTargetWgs * 256 * rpt < rows) rpt *= 2;
   return 256 * rpt;
@@ -400,9 +394,7 @@ inline bool slab_wanted(int rows, int cols) { return (long)cols * 8 > (2L << 20)
 // The column-sorted pass layout (spmv_cs.hpp) pays as soon as there is a pass of nonzeros for most CUs — whether or
 // not the gather vector fits L2 (what it saves is L2 -> L1 line traffic): measured crossover on LP+SOC problems with
 // 10 nonzeros per row at nnz ~ 1e6 (0.240 vs 0.245 ms/iter), -10 % per iteration at nnz = 2e6, -12 % at 4e6.
-inline bool cs_wanted(int rows, int cols, long nnz) {
-  const long min_nnz = opts().cs_min_nnz;  // SCS_HIP_CS=N: tests on small matrices
-  (void)cols;
+inline bool cs_wanted(int rows, long nnz, long min_nnz) {  // min_nnz: Options::cs_min_nnz (SCS_HIP_CS=N: tests on small matrices)
   return rows >= 16384 && nnz >= min_nnz;
 }
 
@@ -410,7 +402,7 @@ inline bool cs_wanted(int rows, int cols, long nnz) {
 inline bool build_slab(const int *rowptr, const int *col, const double *val, int rows, int cols, HostSlab &out,
                        std::vector<int> *src = nullptr, int force_R = 0) {
   const int R = force_R > 0 ? force_R : slab_pick_rows(rows);
-  const int shift = slab_shift();
+  const int shift = kSlabShift;
   const int S = (int)(((long)cols + (1L << shift) - 1) >> shift);
   const int nchunks = (rows + R - 1) / R;
   const long nnz = rowptr[rows];

@@ -82,8 +82,9 @@ __host__ __device__ inline int cs_peel_threshold(int rpt) {
 // Chunk geometry: R rows per workgroup so that the launch is ONE wave of workgroups on the 256 CUs (every CU busy,
 // as many rows per CU as possible: the distinct lines per gather instruction fall with R), R a multiple of 64;
 // rpt = the power of two >= R / 1024.  More than 256 * 16384 rows: R = 16384 and several rounds of workgroups.
-inline void cs_pick_geometry(int rows, int &R, int &rpt, int split = 1) {
-  { const int v = opts().cs_rpt; if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) { rpt = v; R = kCsThreads * v; return; } }  // (labs knob: full chunks of 1024 * rpt rows)
+// force_rpt > 0 (a caller's geometry, or the labs knob Options::cs_rpt): full chunks of 1024 * force_rpt rows.
+inline void cs_pick_geometry(int rows, int &R, int &rpt, int split = 1, int force_rpt = 0) {
+  if (force_rpt > 0) { rpt = force_rpt; R = kCsThreads * force_rpt; return; }
   const int chunks = kCsTargetWgs / split;
   long r = ((long)rows + chunks - 1) / chunks;
   r = std::max(64L, (r + 63) / 64 * 64);
@@ -137,8 +138,8 @@ __host__ __device__ inline int cs_store_pos(int q) {
 inline bool build_cs(const int *rowptr, const int *col, const double *val, int rows, int cols, HostCs &out, int force_rpt = 0,
                      int split = 1, const unsigned *peel = nullptr, int force_R = 0) {
   int R, rpt;
-  cs_pick_geometry(rows, R, rpt, split);
-  if (force_rpt > 0) { rpt = force_rpt; R = force_R > 0 ? force_R : kCsThreads * rpt; }
+  cs_pick_geometry(rows, R, rpt, split, force_rpt);
+  if (force_rpt > 0 && force_R > 0) R = force_R;
   const int nchunks = (rows + R - 1) / R;
   const int cb = cs_count_bits(rpt);
   // longest run of one row inside one pass: what the count field holds, and not more than 2048 — the lane that owns the row adds its
@@ -224,7 +225,7 @@ struct CsVirtPlan {
   std::vector<unsigned> mask;  // bit r: long row (no epilogue in the pass kernel)
 };
 // rows longer than long_thresh nonzeros -> ceil(len / lp) pieces; the geometry of the slot space.  false: nothing to cut / too big
-inline bool cs_plan_virtual(const int *rp, int rows, int lp, int long_thresh, CsVirtPlan &P) {
+inline bool cs_plan_virtual(const int *rp, int rows, int lp, int long_thresh, CsVirtPlan &P, int force_rpt = 0) {
   P = CsVirtPlan{};
   P.rowinfo.assign((size_t)rows, int2{-1, 0});
   P.mask.assign(((size_t)rows + 31) / 32, 0u);
@@ -244,7 +245,7 @@ inline bool cs_plan_virtual(const int *rp, int rows, int lp, int long_thresh, Cs
   P.V = (int)V;
   const long total = (long)rows + V;
   if (total > 2000000000L) return false;
-  cs_pick_geometry((int)total, P.R, P.rpt, 1);
+  cs_pick_geometry((int)total, P.R, P.rpt, 1, force_rpt);
   for (;;) {  // every chunk: Rr real-row slots + Rp piece slots
     P.nchunks = (int)((total + P.R - 1) / P.R);
     P.Rp = (P.V + P.nchunks - 1) / P.nchunks;

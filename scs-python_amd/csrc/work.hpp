@@ -35,13 +35,16 @@ static SpinChain &spin_chain(int device) {
 // SAME set to the workspace it makes: a clone allocates per-solve state only.  Reference-counted (std::shared_ptr); whichever user
 // dies last releases it, inside its own pool window (~ScsHipWork).
 struct MatrixSet {
+  // the options the layouts were built under (options.hpp: taken once by scs_init; a superseded struct is never freed).  Whatever
+  // re-derives a layout (matrix_update.hpp) and every workspace on the set — scs_hip_clone — reads this one, never the global.
+  const Options &opt;
+  explicit MatrixSet(const Options &o) : opt(o) {}
   std::shared_ptr<Arena> home;  // the arena of the workspace that built the set (FIRST member: destroyed last — the buffers below may live in it)
   DeviceCsr At, Ar, Pf;
   DevBuf<double> Pdiag, D, E;
   // what scs_hip_clone rebuilds the state of scs_init from: the data and settings scs_init was called with (scs_update moves b_orig / c_orig)
   std::vector<double> b0, c0, bl0, bu0;
   ScsSettings stgs0{};
-  bool lazy_setup = true;  // SCS_HIP_LAZY_SETUP as scs_init read it: a clone defers what its parent deferred
   // scs_hip_update_matrix (matrix_update.hpp): nothing of this exists until the first call.  One int32 source index per stored value
   // slot of every resident form but A' (whose values ARE the caller's CSC order): -1 marks a padding slot.  ar / pf index the caller's
   // arrays, the layout maps the equilibrated CSR they were built from (cs of A': CSR(A); cs of A: CSR(A'); cs of P and every slab: own CSR).
@@ -78,9 +81,10 @@ struct ScsHipWork {
     ~PoolWindowEnd() { if (armed) --t_pool_release; }
   } pool_window_end;
   std::shared_ptr<Arena> arena;  // small problems: all device buffers of the workspace come from here (FIRST member: destroyed last; the matrix set holds it too)
-  std::shared_ptr<MatrixSet> mats = std::make_shared<MatrixSet>();  // behind the arena: released before it, inside the pool window
-  ScsHipWork() = default;
+  std::shared_ptr<MatrixSet> mats;  // behind the arena: released before it, inside the pool window
+  explicit ScsHipWork(const Options &o) : mats(std::make_shared<MatrixSet>(o)) {}     // scs_init, the kernel-level entry points
   explicit ScsHipWork(std::shared_ptr<MatrixSet> shared) : mats(std::move(shared)) {}  // scs_hip_clone
+  const Options &opt = mats->opt;  // the ONE options snapshot of this workspace, for its whole life: no member reads the process-global one
   struct ScratchTurn {  // around everything that launches products of this workspace's matrices outside a grouped solve
     std::unique_lock<std::mutex> lk;
     explicit ScratchTurn(ScsHipWork *w) { if (w->mats->has_scratch()) lk = std::unique_lock<std::mutex>(w->mats->scratch_mu); }
@@ -107,6 +111,7 @@ struct ScsHipWork {
   double *h_params = nullptr, *d_params = nullptr;  // mapped pinned per-iteration scalars (P_*), slot in use (2 slots)
   double *h_params_base = nullptr, *d_params_base = nullptr;
   // run-ahead mode (see F_STALL in vec.hpp): plain iterations are enqueued whole and one ahead of the host's view
+  // (both from `opt`, for real workspaces only: setup.hpp init_streams_and_pinned)
   bool pipelined = false;
   int pipe_chunk_override = 0, pipe_stalls = 0;  // tests: SCS_HIP_PIPELINE=N forces CG chunks of N steps (=> stalls)
   const int *stall = nullptr;      // fl + F_STALL while a run-ahead iteration is being enqueued, else nullptr
@@ -248,7 +253,9 @@ struct ScsHipWork {
         hipLaunchKernelGGL(k_psd_gemm<PSD_G1>, gg, gb, 0, stream, base, B, psd_scratch.p, psd_warm, stall, gper);
         hipLaunchKernelGGL(k_psd_gemm<PSD_G2>, gg, gb, 0, stream, base, B, psd_scratch.p, psd_warm, stall, gper);
         int mc = !fl.p ? 1 : psd_mc_members(big);  // (the multi-CU kernel polls the workspace's error flag at its barriers)
-        PsdRefineCfg R = psd_refine;
+        // Round 5: GEMM-only refinement of the sign split instead of the last Jacobi sweep(s) (psd.hpp psd_stop_test).
+        // SCS_HIP_PSD_REFINE=0: strict sweeps only (bit-identical to the one-launch kernel)
+        PsdRefineCfg R = psd_refine_default(opt.psd_refine);
         if ((size_t)32 * psd_max_np * sizeof(double) > 160 * 1024) R.on = 0;  // k_psd_apply_q keeps two 16-row strips in LDS
         std::unique_ptr<SpinLink> link;
         if (mc > 1) link.reset(new SpinLink(this));  // spinning launches of this device, one grid at a time (SpinChain)
@@ -269,13 +276,20 @@ struct ScsHipWork {
             int G = mc, rnd = round;
             int *err = fl.p + F_PERSIST_ERR;
             const int *st = stall;
-            int la = psd_mc_look_ahead;
+            int la = opt.psd_la ? 1 : 0;  // (labs switch) one barrier per step
             const double *tl = psd_tol2;
             PsdRefineCfg Rr = R;
             int pst = post;
-            long budget = spin_budget;
+            long budget = 1L << opt.spin_budget_log2;  // barrier polls before a member gives up (SCS_HIP_SPIN_BUDGET_LOG2; tests: 0)
             void *args[] = {&B, &scr, &rnd, &G, &la, &err, &st, &tl, &Rr, &pst, &budget};
-            if (psd_mc_coop) {
+            // Round 4: ORDINARY launch by default.  hipLaunchCooperativeKernel guarantees co-residency of the grid, but on this runtime it costs
+            // ~0.1 ms per launch in a fresh process and ~2 ms per launch once the process has driven other workspaces / streams before (config 4 as
+            // the second workload of a bench run: 224 iters/s in the steady window and 245 over a whole solve against 462 / 521 with the ordinary
+            // launch; cold window 495 vs 522; tools/dbg/c4_after.py, profiles/r04_psd_coop.txt).  The ordinary launch is safe for the same reason the
+            // cooperative one is accepted: the grid is sized to fit the device at one workgroup per CU (psd_mc_cap, occupancy query), the
+            // dispatcher places workgroups in order, and a kernel of another stream that holds CUs finishes without waiting for this one — a group
+            // whose members are late spins within its budget (F_PERSIST_ERR otherwise: an error, not a hang).  (labs) SCS_HIP_PSD_COOP=1: cooperative launch.
+            if (opt.psd_coop) {
               const hipError_t e = hipLaunchCooperativeKernel(reinterpret_cast<const void *>(k_psd_sweep_mc), dim3((unsigned)psd_mc_grid(big, mc)),
                                                              dim3(kPsdThreads), args, (unsigned)kPsdMcLdsBytes, stream);
               if (e != hipSuccess) {  // the runtime cannot co-schedule the grid (it only refuses the FIRST round: nothing ran yet)
@@ -284,7 +298,7 @@ struct ScsHipWork {
                 psd_mc_cap = 0;  // from now on: one workgroup per matrix
                 mc = 1;
               }
-            } else  // SCS_HIP_PSD_COOP=0: ordinary launch (rocprofv3 7.2 crashes at exit after a cooperative launch)
+            } else  // ordinary launch (rocprofv3 7.2 crashes at exit after a cooperative launch)
               hipLaunchKernelGGL(k_psd_sweep_mc, dim3((unsigned)psd_mc_grid(big, mc)), dim3(kPsdThreads), kPsdMcLdsBytes, stream, B, scr, rnd, G,
                                  la, err, st, tl, Rr, pst, budget);
           }
@@ -304,44 +318,16 @@ struct ScsHipWork {
       }
     }
     if (count > big) {
+      // small matrices (order <= 32): four wavefronts per matrix (psd.hpp d_proj_psd_small4)
       PsdBatch B{off + big, order + big, woff + big, count - big};
-      if (psd_small_one_wave)
-        hipLaunchKernelGGL(k_proj_psd_small, dim3(count - big), dim3(64), 0, stream, base, B, psd_scratch.p, psd_warm, stall, psd_tol2);
-      else
-        hipLaunchKernelGGL(k_proj_psd_small4, dim3(count - big), dim3(kPsdSmallThreads), 0, stream, base, B, psd_scratch.p, psd_warm, stall,
-                           psd_tol2);
+      hipLaunchKernelGGL(k_proj_psd_small4, dim3(count - big), dim3(kPsdSmallThreads), 0, stream, base, B, psd_scratch.p, psd_warm, stall,
+                         psd_tol2);
     }
   }
   // Members (CUs) per matrix for the split-mode sweeps: as many as fit when every matrix gets the same number and a
   // group stays inside one XCD (grid = 8 * G * ceil(count / 8) workgroups, all co-resident: cooperative launch).
   // SCS_HIP_PSD_MC=G forces G (0 / 1: the one-workgroup sweep kernel).
-  // small matrices (order <= 32): four wavefronts per matrix (psd.hpp d_proj_psd_small4); SCS_HIP_PSD_SMALL_WAVES=1: the one-wavefront kernel (lab; agrees to rounding)
-  // SCS_HIP_SOC_PSD_FUSE=0: separate launches for short SOCs and small PSD matrices (same bits)
-  bool soc_psd_one_launch = opts().soc_psd_fuse;  // (labs switch)
-  // Round 5: GEMM-only refinement of the sign split instead of the last Jacobi sweep(s) in split mode (psd.hpp psd_stop_test).
-  // SCS_HIP_PSD_REFINE=0: strict sweeps only (bit-identical to the one-launch kernel); SCS_HIP_PSD_GATE_K / _OFF / _OMEGA: the gate (lab knobs).
-  PsdRefineCfg psd_refine = [] {
-    const Options &o = opts();
-    PsdRefineCfg r = psd_refine_default(o.psd_refine);
-    if (o.psd_gate_k > 0.) r.k2 = o.psd_gate_k * o.psd_gate_k;      // (labs: the gate)
-    if (o.psd_gate_off > 0.) r.off2 = o.psd_gate_off * o.psd_gate_off;
-    if (o.psd_gate_omega > 0.) r.omega = o.psd_gate_omega;
-    return r;
-  }();
-  bool psd_small_one_wave = opts().psd_small_one_wave;  // (labs)
-  int psd_mc_look_ahead = opts().psd_la ? 1 : 0;        // (labs switch) one barrier per step
-  // Round 4: ORDINARY launch by default.  hipLaunchCooperativeKernel guarantees co-residency of the grid, but on this runtime it costs
-  // ~0.1 ms per launch in a fresh process and ~2 ms per launch once the process has driven other workspaces / streams before (config 4 as
-  // the second workload of a bench run: 224 iters/s in the steady window and 245 over a whole solve against 462 / 521 with the ordinary
-  // launch; cold window 495 vs 522; tools/dbg/c4_after.py, profiles/r04_psd_coop.txt).  The ordinary launch is safe for the same reason the
-  // cooperative one is accepted: the grid is sized to fit the device at one workgroup per CU (psd_mc_cap, occupancy query), the
-  // dispatcher places workgroups in order, and a kernel of another stream that holds CUs finishes without waiting for this one — a group
-  // whose members are late spins within its budget (F_PERSIST_ERR otherwise: an error, not a hang).  SCS_HIP_PSD_COOP=1: cooperative launch.
-  bool psd_mc_coop = opts().psd_coop;  // (labs)
   int psd_mc_cap = -1;  // co-resident workgroups of k_psd_sweep_mc on this device (0: no cooperative launch)
-  long spin_budget = 1L << opts().spin_budget_log2;  // barrier polls before a member gives up (SCS_HIP_SPIN_BUDGET_LOG2; tests: 0)
-  int psd_mc_forced = opts().psd_mc;                 // SCS_HIP_PSD_MC at the workspace's creation (-1: pick)
-  bool psd_mc_nocheck = opts().psd_mc_nocheck;       // (labs: tests of the refused launch)
   bool spin_user = false;
   hipEvent_t ev_spin = nullptr;
   void spin_register() {  // before this workspace's first spinning launch
@@ -399,15 +385,14 @@ struct ScsHipWork {
     // (tools/psd_mc_lab.sh: order 200 x 50, G = 4: 3.57 -> 2.24 ms per projection; order 64 x 100, G = 2: 0.29 -> 0.42 ms)
     const int pivots = psd_max_np / (2 * kPsdB);
     int G = std::min(std::min(psd_mc_cap / groups, kPsdMcMaxG), pivots / 3);
-    if (psd_mc_forced >= 0) {
-      G = psd_mc_forced;
-      if (G > kPsdMcMaxG || ((long)G * groups > (long)psd_mc_cap && !psd_mc_nocheck)) G = 1;  // (NOCHECK: tests of the refused launch)
+    if (opt.psd_mc >= 0) {  // SCS_HIP_PSD_MC at the workspace's creation (-1: pick)
+      G = opt.psd_mc;
+      if (G > kPsdMcMaxG || ((long)G * groups > (long)psd_mc_cap && !opt.psd_mc_nocheck)) G = 1;  // ((labs) NOCHECK: tests of the refused launch)
     }
     return std::max(G, 1);
   }
   // stopping level of the PSD sweeps (psd.hpp psd_offtol2): inside the ADMM loop the iteration's P_PSD_TOL2, else nullptr = fixed 1e-8
   const double *psd_tol2 = nullptr;
-  static bool psd_tol_adaptive() { return opts().psd_tol_adaptive; }  // SCS_HIP_PSD_TOL=fixed: A/B
   // ... and only while no Anderson extrapolation can happen yet (the history is still filling: iteration < lookback x interval;
   // always, without acceleration): plain ADMM tolerates inexact projections, the secant model of the acceleration does not —
   // with interval 1 and type-II steps a golden infeasible instance stalled for good (tools/dbg/psd_tol_infeas.py).
@@ -415,13 +400,10 @@ struct ScsHipWork {
     const bool plain_phase = aa.mem <= 0 || (long)iter < (long)aa.mem * stgs.acceleration_interval;
     return plain_phase ? psd_tol2_of(psd_res_min) : kPsdOffTol2;
   }
-  static double psd_kappa() {
-    return opts().psd_tol_k;  // (labs knob; see psd.hpp psd_offtol2 for why 1e-2)
-  }
-  static double psd_tol2_of(double level) {  // level = what note_check_residuals left in psd_res_min
-    if (!psd_tol_adaptive()) return kPsdOffTol2;
-    const double cap = opts().psd_tol_max;  // (labs knob)
-    const double t = std::min(std::max(level, 1e-8), cap);
+  static constexpr double kPsdTolMax = 1e-3;  // the loosest level the sweeps ever stop at
+  double psd_tol2_of(double level) const {  // level = what note_check_residuals left in psd_res_min
+    if (!opt.psd_tol_adaptive) return kPsdOffTol2;  // SCS_HIP_PSD_TOL=fixed: A/B
+    const double t = std::min(std::max(level, 1e-8), kPsdTolMax);
     return t * t;
   }
   int psd_warm = 1;  // warm-start the eigen-solves from the previous call's eigenvectors (0 in the one-shot test entry)
@@ -439,16 +421,14 @@ struct ScsHipWork {
   int last_cg_iters = 8;
   int cg_hist[8] = {8, 8, 8, 8, 8, 8, 8, 8}, cg_hist_pos = 0;  // CG steps of the last 8 linear solves (chunk sizing)
   void note_cg_iters(int it) { cg_hist[cg_hist_pos++ & 7] = it; }
-  // largest step count of the last `chunk_window()` linear solves (SCS_HIP_CHUNK_WINDOW, 1..8): what a queued iteration's CG chunk is sized
+  // largest step count of the last kChunkWindow linear solves: what a queued iteration's CG chunk is sized
   // for.  Round 4: 3 instead of 8 — in the cold-start phase the counts FALL from iteration to iteration, and a window of 8 kept
   // enqueuing the counts of eight iterations ago: 36 % of the K1 / K2 launches of the bench window were early-exit launches
   // (profiles/r03_bench_kernel_trace.txt: 3581 launched, 2309 with work).
-  static int chunk_window() {
-    return opts().chunk_window;  // (labs knob)
-  }
+  static constexpr int kChunkWindow = 3;
   int recent_cg_max() const {
     int mx = 1;
-    for (int k = 1; k <= chunk_window(); ++k) mx = std::max(mx, cg_hist[(cg_hist_pos - k) & 7]);
+    for (int k = 1; k <= kChunkWindow; ++k) mx = std::max(mx, cg_hist[(cg_hist_pos - k) & 7]);
     return mx;
   }
   int recent_cg_q3() const {  // third quartile of the last 8 linear solves (the grouped loop's prediction: a short round is cheap there)
@@ -463,7 +443,7 @@ struct ScsHipWork {
   double psd_res_min = 0;
   void note_check_residuals() {
     cg_res_min = std::min(r.nm_pri_n, r.nm_dual_n);
-    psd_res_min = psd_kappa() * cg_res_min;
+    psd_res_min = opt.psd_tol_k * cg_res_min;  // ((labs) SCS_HIP_PSD_TOL_K; see psd.hpp psd_offtol2 for why 1e-2)
     if (std::isfinite(r.res_infeas)) psd_res_min = std::min(psd_res_min, r.res_infeas);
     // (an unboundedness certificate needs BOTH of its residuals small; |Px| / -c'x is identically 0 for an LP)
     if (std::isfinite(r.res_unbdd_a) && std::isfinite(r.res_unbdd_p)) psd_res_min = std::min(psd_res_min, std::max(r.res_unbdd_a, r.res_unbdd_p));

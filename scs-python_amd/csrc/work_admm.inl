@@ -9,8 +9,8 @@
     h_params[P_IPOW] = std::pow((double)iter + 1, 1.5);
     h_params[P_FIRST] = iter < 1 ? 1.0 : 0.0;
     h_params[P_PSD_TOL2] = psd_tol2_for(iter);
-    const bool dbg_tol = (opts().debug & DBG_TOL) != 0;  // SCS_HIP_DEBUG=tol (tools/dbg/run_ahead_tol.py)
-    if (dbg_tol) std::fprintf(stderr, "[scs-hip] iter %d slot %d: res_min %.17g psd level %.3e tol2 %.3e\n", iter, slot, cg_res_min, psd_res_min, h_params[P_PSD_TOL2]);
+    if (opt.debug & DBG_TOL)  // SCS_HIP_DEBUG=tol (tools/dbg/run_ahead_tol.py)
+      std::fprintf(stderr, "[scs-hip] iter %d slot %d: res_min %.17g psd level %.3e tol2 %.3e\n", iter, slot, cg_res_min, psd_res_min, h_params[P_PSD_TOL2]);
   }
   // everything of project_lin_sys up to (and including) the fused, warm-started CG start
   void enqueue_lin_sys_head() {
@@ -82,7 +82,7 @@
     stall = fl.p + F_STALL;
     stall_fl = fl.p;
     enqueue_lin_sys_head();
-    // the largest step count of the last 8 solves + 1 (the newest count is one iteration stale here; is_plain caps it):
+    // the largest step count of the last kChunkWindow solves + 1 (the newest count is one iteration stale here; is_plain caps it):
     // an unused step costs four ~1-2 us launches, a stall a drained queue and a host round trip (~100 us)
     int chunk = std::max(2, recent_cg_max() + 1);
     if (pipe_chunk_override > 0) chunk = pipe_chunk_override;
@@ -120,28 +120,11 @@
   // Wait for iteration `iter` of the run-ahead queue.  Returns false if its CG chunk was too short: the rest of that
   // iteration and everything queued behind it did nothing; the caller finishes the iteration synchronously.
   // SCS_HIP_DEBUG=pipe: per-iteration CG step counts and run-ahead stalls on stderr.
-  static bool debug_pipe() {
-    return (opts().debug & DBG_PIPE) != 0;
-  }
-  // host wait for an event: SCS_HIP_WAIT=block -> hipEventSynchronize, spin -> poll hipEventQuery (lab knob)
-  static int wait_mode() {
-    return opts().wait_spin ? 1 : 0;  // (labs knob)
-  }
-  static void wait_event(hipEvent_t e) {
-    if (wait_mode() == 1) {
-      for (;;) {
-        const hipError_t q = hipEventQuery(e);
-        if (q == hipSuccess) return;
-        if (q != hipErrorNotReady) HIP_CHECK(q);
-        __builtin_ia32_pause();
-      }
-    }
-    HIP_CHECK(hipEventSynchronize(e));
-  }
+  bool debug_pipe() const { return (opt.debug & DBG_PIPE) != 0; }
   bool finish_plain_iteration(int iter) {
     const int slot = iter & 1;
     HIP_CHECK(hipGetLastError());  // a refused launch (hipLaunchKernelGGL reports nothing) surfaces here, once per iteration
-    wait_event(ev_iter[slot]);
+    HIP_CHECK(hipEventSynchronize(ev_iter[slot]));
     const int *hf = h_flags_slot[slot];
     if (hf[F_STALL]) {
       ++pipe_stalls;
@@ -211,8 +194,9 @@
       hipLaunchKernelGGL(k_proj_box, dim3(1), dim3(kBoxThreads), 0, stream, y + cone.off_box, box_bl.p, box_bu.p, cone.bsize,
                          sc.p + S_BOX_T, dual, stall);
     }
-    // short SOCs + small PSD matrices (nothing big of either kind): one launch for both (psd.hpp k_proj_soc_psd_small)
-    const bool soc_psd_fused = soc_psd_one_launch && n_soc > 0 && n_soc_big == 0 && n_psd > 0 && n_psd_big == 0 && !psd_small_one_wave;
+    // short SOCs + small PSD matrices (nothing big of either kind): one launch for both (psd.hpp k_proj_soc_psd_small);
+    // (labs switch) SCS_HIP_SOC_PSD_FUSE=0: separate launches (same bits)
+    const bool soc_psd_fused = opt.soc_psd_fuse && n_soc > 0 && n_soc_big == 0 && n_psd > 0 && n_psd_big == 0;
     if (soc_psd_fused) {
       const int sb = soc_wave_blocks(n_soc, soc_G);
       hipLaunchKernelGGL(k_proj_soc_psd_small, dim3(sb + n_psd), dim3(kPsdSmallThreads), 0, stream, y, soc_off.p, soc_dim.p, n_soc, soc_G, sb,

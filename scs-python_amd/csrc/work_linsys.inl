@@ -5,7 +5,7 @@
 
   // ---- dense direct linsys (dense.hpp; linsys == 1): G^{-1} = (R_x + P + A' R_y^{-1} A)^{-1} resident in HBM, rebuilt whenever R changes
   int linsys = 0;  // 0: indirect (PCG), 1: dense direct
-  DevBuf<double> dn_G, dn_Pk, dn_L, dn_Rt, dn_part;
+  DevBuf<double> dn_G, dn_Pk, dn_L, dn_Rt;
   int dn_NP = 0, dense_factorisations = 0;
   bool dense() const { return linsys == 1; }
   DenseMat dense_mat() const { return DenseMat{dn_G.p, dn_Pk.p, dn_L.p, dn_Rt.p, n, dn_NP}; }
@@ -19,21 +19,9 @@
     dn_Pk.alloc((size_t)kDenseB * kDenseB);
     dn_L.alloc((size_t)dn_NP * kDenseB);
     dn_Rt.alloc((size_t)dn_NP * kDenseB);
-    dn_part.alloc_zero(dense_symv_part_len(dn_NP), stream);
-  }
-  // x = X' b over the WHOLE computed inverse X (default), or SCS_HIP_DENSE_GEMV=half: the two-launch product that reads only the tiles on
-  // and below the diagonal.  The half product is NOT the default although it halves the bytes of the HBM-bound part of a batch: a
-  // Gauss-Jordan inverse is accurate on ONE side (here || X G - I || ~ eps kappa, so X' b solves G x = b to ~ kappa eps), while its
-  // asymmetry — what a product that mirrors one triangle sees — is kappa times larger: measured on the KKT test systems
-  // (kappa = 2e4) 1e-11 against 3.5e-8 relative error (tools/dbg/dense_gemv_err.py, profiles/r04_dense_linsys.txt).
-  static bool dense_full_gemv() {
-    return opts().dense_full_gemv;  // (labs: SCS_HIP_DENSE_GEMV=half)
   }
   void dense_gemv(const double *b, double *x, const int *st) {
-    if (dense_full_gemv())
-      hipLaunchKernelGGL(k_dense_gemv, dim3(dense_gemv_blocks(n)), dim3(kDenseThreads), 0, stream, (const double *)dn_G.p, dn_NP, n, b, x, st);
-    else
-      dense_apply(dn_G.p, dn_NP, n, b, dn_part.p, x, st, stream);
+    hipLaunchKernelGGL(k_dense_gemv, dim3(dense_gemv_blocks(n)), dim3(kDenseThreads), 0, stream, (const double *)dn_G.p, dn_NP, n, b, x, st);
   }
   // Dense workspaces finish their setup — R, G^{-1}, g = KKT^{-1} [c; -b] — at the first solve (or update) instead of inside scs_init:
   // a batch of them then forms and inverts all its matrices in ONE batched sweep (GroupSolve::run), 66 launches for the whole group
@@ -148,8 +136,7 @@
     hipLaunchKernelGGL(k_cg_dir, dim3(vb(n)), dim3(kVecThreads), 0, stream, cg_p.p, cg_r.p, cg_M.p, n, part2.p, nb, sc.p, fl.p);
   }
   // SCS_HIP_CG_FUSE=0: always two launches
-  bool cg_fuse_on = opts().cg_fuse;  // (labs switch) read when the workspace is made
-  bool cg_fuse() const { return cg_fuse_on && n <= kCgFuseMaxN; }
+  bool cg_fuse() const { return opt.cg_fuse && n <= kCgFuseMaxN; }  // ((labs switch) SCS_HIP_CG_FUSE)
 
   // PCG on cg_b (rhs, length n); solution accumulates in xout.  S_TOL / F_DONE must be set on device.
   // Returns CG iterations taken.
