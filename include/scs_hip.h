@@ -96,6 +96,10 @@ SCS_HIP_API double scs_hip_spmv_bench(const ScsMatrix *A, int transpose, int rep
  * exp_cone.c, R:meson.build:188,190). */
 SCS_HIP_API int scs_hip_proj_cone(scs_float *x, const ScsCone *k, scs_int m, int dual);
 
+/* The derivative of that projection (csrc/dproj.hpp) at v, applied to u: out_Wu = W u and out_WmIu = (W - I) u with W = D Pi_K(v)
+ * (v, u, the outputs: `len` doubles, host pointers; an output may be NULL).  Zero, nonnegative and second-order cones only.  (parity tests) */
+SCS_HIP_API int scs_hip_dproj_cone(const scs_float *v, const scs_float *u, const ScsCone *cone, scs_int len, scs_float *out_Wu, scs_float *out_WmIu);
+
 /* The same projection applied to `count` vectors one after the other (xs: count x m, row-major, in place) through ONE set of cone
  * workspaces, warm-started from call to call as inside the ADMM loop (K9: eigenvectors of the previous call, periodic
  * re-orthogonalisation, refinement stage; box cone: the previous t).  stats (may be NULL): scs_hip_psd_refine_stats records of the
@@ -190,6 +194,49 @@ SCS_HIP_API scs_int scs_hip_solve_batch_device(ScsWork **w, scs_float **x_dev, s
  * 4 bytes per slot, INTEGRATION.md has the total); later calls allocate nothing new (temporaries come back from the block pool). */
 SCS_HIP_API scs_int scs_hip_update_matrix(ScsWork *w, const scs_float *Ax, const scs_float *Px);
 SCS_HIP_API scs_int scs_hip_update_matrix_device(ScsWork *w, const scs_float *Ax_dev, const scs_float *Px_dev);
+/* Derivatives of the last solve, on the device (csrc/diff.hpp, lsqr.hpp, dproj.hpp).  At a solution with v = s - y the optimality
+ * conditions F(x, v) = 0 have the Jacobian J = [[P, A'(W - I)], [A, W]], W = the derivative of the projection onto K at v.
+ *   adjoint:    given gx = dL/dx (n), gy = dL/dy (m), gs = dL/ds (m) — NULL counts as 0 — solves J' lambda = (gx ; W gs + (W - I) gy) and
+ *               writes dL/db (m), dL/dc (n), dL/dA (nnz(A) values in the order of the CSC arrays scs_init got) and dL/dP (nnz(P) values
+ *               of the triangle as passed; an off-diagonal entry stands for both of its mirror images); a NULL output is skipped.
+ *   derivative: given db (m), dc (n) — NULL counts as 0 — solves J (dx ; dv) = (-dc ; db) and writes dx (n), dy (m), ds (m).
+ * Both run LSQR on the resident, equilibrated matrices; the results are in the caller's coordinates.  opts may be NULL (tol 1e-8,
+ * max_iters 0 = 4 (n + m)); info may be NULL.  info->residual and info->normal_residual are LSQR's running estimates of
+ * |M l - g| / |g| and |M' r| / (|M| |r|) (|M|: the Frobenius-norm estimate of the bidiagonalisation); stop = 1: the system is
+ * consistent to tol, 2: the least-squares conditions hold to tol, 3: the iteration cap.  A singular J (a degenerate solution: a
+ * tight row with a zero multiplier, more tight rows than columns) is NOT an error: LSQR then returns the minimum-norm least-squares
+ * answer, usually with stop = 2.
+ *
+ * The *_device entries take DEVICE pointers of the workspace's device under the stream contract above; scs_hip_adjoint and
+ * scs_hip_derivative take HOST pointers, stage them into device buffers and run the same path (same bits).  The first call of a
+ * workspace takes 8 m + 6 n doubles of scratch from the block pool and keeps them until scs_finish; a request for dL/dP adds n + 1
+ * ints.  A call reads the resident solution and matrices and writes nothing a later solve reads.  Two calls on the same state give
+ * the same bits.  Clones and both linear solvers are served; users of a matrix set with pass layouts take turns, as for a solve.
+ *
+ * Returns 0, or -1 with the reason in scs_hip_last_error — refused before any device work, the workspace unchanged and usable: a NULL
+ * workspace; no solve yet, or the last solve did not end SCS_SOLVED / SCS_SOLVED_INACCURATE; scs_update, scs_hip_update_device or
+ * scs_hip_update_matrix[_device] ran since the last solve (the resident solution is stale); a cone other than z, l, q (named in the
+ * message); (device entries) a pointer that is not device memory of the workspace's device; dPx for a workspace created without P, or
+ * with a P whose values scs_hip_update_matrix would refuse (entries below the diagonal, unsorted rows). */
+typedef struct {
+  scs_float tol;      /* LSQR's atol = btol; <= 0: 1e-8 */
+  scs_int max_iters;  /* <= 0: 4 (n + m) */
+} ScsHipDiffOpts;
+typedef struct {
+  scs_int iters;
+  scs_float residual, normal_residual;
+  scs_int stop;
+  scs_float time_ms;
+} ScsHipDiffInfo;
+SCS_HIP_API scs_int scs_hip_adjoint_device(ScsWork *w, const scs_float *gx_dev, const scs_float *gy_dev, const scs_float *gs_dev,
+                                           scs_float *db_dev, scs_float *dc_dev, scs_float *dAx_dev, scs_float *dPx_dev,
+                                           const ScsHipDiffOpts *opts, ScsHipDiffInfo *info);
+SCS_HIP_API scs_int scs_hip_adjoint(ScsWork *w, const scs_float *gx, const scs_float *gy, const scs_float *gs, scs_float *db, scs_float *dc,
+                                    scs_float *dAx, scs_float *dPx, const ScsHipDiffOpts *opts, ScsHipDiffInfo *info);
+SCS_HIP_API scs_int scs_hip_derivative_device(ScsWork *w, const scs_float *db_dev, const scs_float *dc_dev, scs_float *dx_dev,
+                                              scs_float *dy_dev, scs_float *ds_dev, const ScsHipDiffOpts *opts, ScsHipDiffInfo *info);
+SCS_HIP_API scs_int scs_hip_derivative(ScsWork *w, const scs_float *db, const scs_float *dc, scs_float *dx, scs_float *dy, scs_float *ds,
+                                       const ScsHipDiffOpts *opts, ScsHipDiffInfo *info);
 /* the HIP device a workspace lives on (-1: NULL) */
 SCS_HIP_API int scs_hip_work_device(const ScsWork *w);
 

@@ -1,0 +1,277 @@
+// diff.hpp — derivatives of a solve on the device (include/scs_hip.h: scs_hip_adjoint[_device], scs_hip_derivative[_device]).
+//
+// At a solution let v = s - y: s = Pi_K(v), y = Pi_K(v) - v.  The optimality conditions in (x, v) are
+//     F1 = P x + A'(Pi(v) - v) + c = 0,   F2 = A x + Pi(v) - b = 0,   J = [[P, A'(W - I)], [A, W]],  W = D Pi_K(v)  (dproj.hpp)
+// adjoint:   g = (gx ; W gs + (W - I) gy),  J' lambda = g,  dL/dc = -lambda1,  dL/db = lambda2,
+//            dL/dA_ij = -(y_i lambda1_j + lambda2_i x_j),  dL/dP_ij = -(lambda1_i x_j + lambda1_j x_i) (i < j),  dL/dP_ii = -lambda1_i x_i
+// forward:   J (dx ; dv) = (-dc ; db),  ds = W dv,  dy = (W - I) dv
+// The systems are solved by LSQR (lsqr.hpp) on the RESIDENT, equilibrated matrices A^ = D A E, P^ = E P E at v^ = sigma (D s - y / D):
+// the hatted problem has the same F, and D is constant on every SOC block.  In: gx^ = E gx / sigma, gy^ = D gy / sigma,
+// gs^ = gs / (D sigma), dc^ = sigma E dc, db^ = sigma D db.  Out: dL/dc = sigma E dL/dc^, dL/db = sigma D dL/db^,
+// dL/dA_ij = D_i E_j dL/dA^_ij, dL/dP_ij = E_i E_j dL/dP^_ij; dx = E dx^ / sigma, dy = D dy^ / sigma, ds = ds^ / (D sigma).  With
+// mu = sigma E lambda1 = -dL/dc and nu = sigma D lambda2 = dL/db the matrix gradients need the caller's x, y only:
+//     dL/dA_ij = -(y_i mu_j + nu_i x_j),   dL/dP_ij = -(mu_i x_j + mu_j x_i).
+// D, E and sigma are constants here, which is exact: the solution of the caller's problem does not depend on them.
+//
+//     J' l = [P l1 + A' l2 ; (W - I)(A l1) + W l2] = [.. ; W (A l1 + l2) - A l1]        J q = [P q1 + A'((W - I) q2) ; A q1 + W q2]
+// The products go through launch_spmv with EpiStore (every layout finishes it: the split pass layout through k_epi_finish).
+//
+// A call reads solx / soly / sols and the matrices, and writes the workspace's DiffScratch only.
+#pragma once
+
+namespace scship {
+
+// uh[0..n) = E gx / sigma;  gyh = D gy / sigma;  gsh = gs / (D sigma)   (a missing input counts as 0; D == nullptr: as they are)
+__global__ __launch_bounds__(kVecThreads) void k_adj_in(const double *gx, const double *gy, const double *gs, const double *__restrict__ D,
+                                                        const double *__restrict__ E, double sigma, int n, int m, double *uh, double *gyh,
+                                                        double *gsh) {
+  for (long i = (long)blockIdx.x * kVecThreads + threadIdx.x; i < (long)n + m; i += (long)gridDim.x * kVecThreads) {
+    if (i < n) {
+      uh[i] = gx ? (E ? E[i] * gx[i] / sigma : gx[i]) : 0.;
+    } else {
+      const long k = i - n;
+      gyh[k] = gy ? (D ? D[k] * gy[k] / sigma : gy[k]) : 0.;
+      gsh[k] = gs ? (D ? gs[k] / (D[k] * sigma) : gs[k]) : 0.;
+    }
+  }
+}
+// uh = (-sigma E dc ; sigma D db)
+__global__ __launch_bounds__(kVecThreads) void k_fwd_in(const double *db, const double *dc, const double *__restrict__ D,
+                                                        const double *__restrict__ E, double sigma, int n, int m, double *uh) {
+  for (long i = (long)blockIdx.x * kVecThreads + threadIdx.x; i < (long)n + m; i += (long)gridDim.x * kVecThreads) {
+    if (i < n) uh[i] = dc ? -(E ? sigma * E[i] * dc[i] : dc[i]) : 0.;
+    else uh[i] = db ? (D ? sigma * D[i - n] * db[i - n] : db[i - n]) : 0.;
+  }
+}
+// dc = -sigma E lambda1;  db = sigma D lambda2
+__global__ __launch_bounds__(kVecThreads) void k_adj_out(const double *__restrict__ lam, const double *__restrict__ D, const double *__restrict__ E,
+                                                         double sigma, int n, int m, double *dc, double *db) {
+  for (long i = (long)blockIdx.x * kVecThreads + threadIdx.x; i < (long)n + m; i += (long)gridDim.x * kVecThreads) {
+    if (i < n) dc[i] = -(E ? sigma * E[i] * lam[i] : lam[i]);
+    else db[i - n] = D ? sigma * D[i - n] * lam[i] : lam[i];
+  }
+}
+// dx = E dx^ / sigma;  dy = D (W - I) dv^ / sigma;  ds = W dv^ / (D sigma)   (a nullptr output is skipped)
+__global__ __launch_bounds__(kVecThreads) void k_fwd_out(const double *__restrict__ q, const double *__restrict__ Wq, const double *__restrict__ WmIq,
+                                                         const double *__restrict__ D, const double *__restrict__ E, double sigma, int n, int m,
+                                                         double *dx, double *dy, double *ds) {
+  for (long i = (long)blockIdx.x * kVecThreads + threadIdx.x; i < (long)n + m; i += (long)gridDim.x * kVecThreads) {
+    if (i < n) {
+      if (dx) dx[i] = E ? E[i] * q[i] / sigma : q[i];
+    } else {
+      const long k = i - n;
+      if (dy) dy[k] = D ? D[k] * WmIq[k] / sigma : WmIq[k];
+      if (ds) ds[k] = D ? Wq[k] / (D[k] * sigma) : Wq[k];
+    }
+  }
+}
+// dL/dA over the caller's CSC order = the CSR of A': slot p = (row j of A' = column of A, column i = row of A)
+__global__ __launch_bounds__(kVecThreads) void k_grad_a(const int *__restrict__ rp, const int *__restrict__ ci, int rows, long nnz,
+                                                        const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ dc,
+                                                        const double *__restrict__ db, double *dA) {
+  for (long p = (long)blockIdx.x * kVecThreads + threadIdx.x; p < nnz; p += (long)gridDim.x * kVecThreads) {
+    const int j = vm_row_of(rp, rows, p), i = ci[p];
+    dA[p] = y[i] * dc[j] - db[i] * x[j];  // -(y_i mu_j + nu_i x_j), mu = -dc, nu = db
+  }
+}
+// dL/dP over the caller's triangle: the entries of row r of the full matrix on or below the diagonal are column r of the triangle, in
+// order (matrix_update.hpp k_map_pf); up = the triangle's column pointers
+__global__ __launch_bounds__(kVecThreads) void k_grad_p(const int *__restrict__ rp, const int *__restrict__ ci, int n, long nnz,
+                                                        const int *__restrict__ up, const double *__restrict__ x, const double *__restrict__ dc,
+                                                        double *dP) {
+  for (long q = (long)blockIdx.x * kVecThreads + threadIdx.x; q < nnz; q += (long)gridDim.x * kVecThreads) {
+    const int r = vm_row_of(rp, n, q), c = ci[q];
+    if (c > r) continue;
+    const int k = (int)(q - rp[r]);
+    if (k >= up[r + 1] - up[r]) continue;
+    dP[up[r] + k] = c < r ? dc[c] * x[r] + dc[r] * x[c] : dc[r] * x[r];  // -(mu_c x_r + mu_r x_c), mu = -dc
+  }
+}
+
+}  // namespace scship
+
+// why this workspace cannot be differentiated ("" = it can): argument-free refusals, before any device work
+static std::string diff_refusal(const ScsHipWork *w) {
+  if (w->diff_state == 0) return "no solve yet: differentiate after scs_solve";
+  if (w->diff_state == 2) return "the last solve did not end solved (status " + std::to_string(w->last_status_val) + "): there is no solution to differentiate";
+  if (w->diff_state == 3) return "the resident solution is stale: b, c or the matrix changed since the last solve; solve again first";
+  const HostCone &c = w->cone;
+  const char *other = c.bsize > 1 ? "box" : !c.s.empty() ? "PSD (s)" : !c.cs.empty() ? "complex PSD (cs)" : c.ep > 0 ? "exponential (ep)" :
+                      c.ed > 0 ? "dual exponential (ed)" : !c.p.empty() ? "power (p)" : !c.d.empty() ? "log-det (d)" :
+                      !c.nuc_m.empty() ? "nuclear norm (nuc)" : !c.ell1.empty() ? "ell1" : !c.sl_n.empty() ? "sum-of-largest (sl)" : nullptr;
+  if (other) return std::string("the derivative of the ") + other + " cone projection is not implemented (z, l and q cones only)";
+  return "";
+}
+
+struct DiffCall {
+  bool adjoint = true;
+  const double *in[3] = {nullptr, nullptr, nullptr};          // adjoint: gx, gy, gs;  forward: db, dc
+  double *out[4] = {nullptr, nullptr, nullptr, nullptr};      // adjoint: db, dc, dAx, dPx;  forward: dx, dy, ds
+};
+
+static void diff_alloc(ScsHipWork *w) {
+  DiffScratch &d = w->diff;
+  if (d.ready) return;
+  ArenaScope no_arena(nullptr);  // exact-size blocks from the block pool, returned to it by scs_finish
+  const size_t n = (size_t)w->n, m = (size_t)w->m, N = n + m;
+  for (DevBuf<double> *b : {&d.uh, &d.vh, &d.w, &d.x}) b->alloc(N);
+  for (DevBuf<double> *b : {&d.tA, &d.dW, &d.dWmI, &d.vhat}) b->alloc(m);
+  for (DevBuf<double> *b : {&d.tAt, &d.tP}) b->alloc(n);
+  d.cinfo.alloc((size_t)3 * std::max(w->n_soc, 1));
+  const size_t nb = (size_t)vec_blocks((long)N);
+  for (DevBuf<double> *b : {&d.partU, &d.partV, &d.partX}) b->alloc(nb);
+  d.st.alloc(L_COUNT);
+  d.fl.alloc(LF_COUNT);
+  d.ready = true;
+}
+
+// column pointers of the caller's triangle of P from the resident full matrix (once per workspace)
+static void diff_build_tri(ScsHipWork *w) {
+  DiffScratch &d = w->diff;
+  if (d.tri_ready) return;
+  ArenaScope no_arena(nullptr);
+  hipStream_t s = w->stream;
+  const int n = w->n;
+  DevBuf<int> cnt, tmp;
+  cnt.alloc((size_t)n);
+  d.tri_up.alloc((size_t)n + 1);
+  tmp.alloc_zero((size_t)(n / kScanTile + 4), s);
+  hipLaunchKernelGGL(k_pf_lowcount, dim3(vec_blocks(n)), dim3(kVecThreads), 0, s, (const int *)w->Pf.rowptr.p, (const int *)w->Pf.col.p, n, cnt.p);
+  device_exclusive_scan(cnt.p, d.tri_up.p, n, tmp.p, s);
+  int total = 0;
+  HIP_CHECK(hipMemcpyAsync(&total, d.tri_up.p + n, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));  // (cnt / tmp are locals)
+  if ((long)total != w->mats->p_nnz_in) {
+    d.tri_up.release();
+    throw std::runtime_error("P was given with " + std::to_string(w->mats->p_nnz_in) + " entries of which " + std::to_string(total) +
+                             " lie in the upper triangle: its gradient cannot be gathered");
+  }
+  d.tri_ready = true;
+}
+
+// The caller holds w->mtx and the scratch turn, has selected the device and refused bad arguments.  All pointers are device pointers.
+static void diff_impl(ScsHipWork *w, const DiffCall &a, const ScsHipDiffOpts *o, ScsHipDiffInfo *info) {
+  const double t0 = now_ms();
+  hipStream_t s = w->stream;
+  const int n = w->n, m = w->m;
+  const long N = (long)n + m;
+  const double tol = o && o->tol > 0. ? o->tol : 1e-8;
+  const long cap = o && o->max_iters > 0 ? (long)o->max_iters : 4 * N;
+  diff_alloc(w);
+  if (a.adjoint && a.out[3]) diff_build_tri(w);
+  DiffScratch &d = w->diff;
+  const double *D = w->normalized ? w->D.p : nullptr, *E = w->normalized ? w->E.p : nullptr;
+  const double sigma = w->normalized ? w->scal.sigma : 1.0;
+  const int nbN = vec_blocks(N);
+  const dim3 gN(nbN), bV(kVecThreads);
+  const int *done = d.fl.p + LF_DONE;
+
+  // ---- the fixed point and the cone records ----
+  hipLaunchKernelGGL(k_dproj_vhat, dim3(vec_blocks(m)), bV, 0, s, (const double *)w->sols.p, (const double *)w->soly.p, D, sigma, m, d.vhat.p);
+  DprojPlan plan;
+  plan.z = w->cone.z; plan.l = w->cone.l; plan.n_soc = w->n_soc; plan.n_soc_big = w->n_soc_big; plan.G = w->soc_G;
+  plan.off = w->soc_off.p; plan.dim = w->soc_dim.p; plan.big = w->soc_big.p;
+  plan.vh = d.vhat.p; plan.cinfo = d.cinfo.p;
+  launch_dproj_prep(plan, s);
+
+  // ---- right-hand side into uh, x = w = 0 ----
+  if (a.adjoint) {
+    double *gyh = d.x.p + n, *gsh = d.tA.p;
+    hipLaunchKernelGGL(k_adj_in, gN, bV, 0, s, a.in[0], a.in[1], a.in[2], D, E, sigma, n, m, d.uh.p, gyh, gsh);
+    launch_dproj(plan, DprojIo{gsh, nullptr, d.dW.p, nullptr}, nullptr, s);
+    launch_dproj(plan, DprojIo{gyh, nullptr, nullptr, d.dWmI.p}, nullptr, s);
+    hipLaunchKernelGGL(k_lsqr_start, gN, bV, 0, s, d.uh.p, (const double *)d.dW.p, (const double *)d.dWmI.p, n, N, d.x.p, d.w.p, d.partU.p, d.st.p,
+                       d.fl.p);
+  } else {
+    hipLaunchKernelGGL(k_fwd_in, gN, bV, 0, s, a.in[0], a.in[1], D, E, sigma, n, m, d.uh.p);
+    hipLaunchKernelGGL(k_lsqr_start, gN, bV, 0, s, d.uh.p, (const double *)nullptr, (const double *)nullptr, n, N, d.x.p, d.w.p, d.partU.p, d.st.p,
+                       d.fl.p);
+  }
+
+  // ---- the two products (results in tAt, tP, tA, dW) ----
+  const double *tP = w->has_P ? d.tP.p : nullptr;
+  auto prod_J = [&](const double *q) {
+    launch_dproj(plan, DprojIo{q + n, nullptr, d.dW.p, d.dWmI.p}, done, s);
+    launch_spmv(w->Ar.view(), q, EpiStore{d.tA.p, 0}, done, s);
+    launch_spmv(w->At.view(), d.dWmI.p, EpiStore{d.tAt.p, 0}, done, s);
+    if (w->has_P) launch_spmv(w->Pf.view(), q, EpiStore{d.tP.p, 0}, done, s);
+    return LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 0};
+  };
+  auto prod_Jt = [&](const double *l) {
+    launch_spmv(w->Ar.view(), l, EpiStore{d.tA.p, 0}, done, s);
+    launch_dproj(plan, DprojIo{d.tA.p, l + n, d.dW.p, nullptr}, done, s);
+    launch_spmv(w->At.view(), l + n, EpiStore{d.tAt.p, 0}, done, s);
+    if (w->has_P) launch_spmv(w->Pf.view(), l, EpiStore{d.tP.p, 0}, done, s);
+    return LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 1};
+  };
+  // M = J' (adjoint) or J (forward): M v and M' u
+  auto prod_M = [&](const double *v) { return a.adjoint ? prod_Jt(v) : prod_J(v); };
+  auto prod_Mt = [&](const double *u) { return a.adjoint ? prod_J(u) : prod_Jt(u); };
+  auto step_v = [&](int k) {
+    const LsqrProd tv = prod_Mt(d.uh.p);
+    hipLaunchKernelGGL(k_lsqr_v, gN, bV, 0, s, k, tv, d.vh.p, (const double *)d.w.p, d.x.p, n, N, (const double *)d.partU.p, nbN, d.partV.p, d.partX.p,
+                       d.st.p, d.fl.p);
+  };
+  auto step_u = [&](int k) {
+    const LsqrProd tu = prod_M(d.vh.p);
+    hipLaunchKernelGGL(k_lsqr_u, gN, bV, 0, s, k, tu, d.uh.p, (const double *)d.vh.p, d.w.p, n, N, (const double *)d.partV.p, (const double *)d.partX.p,
+                       nbN, d.partU.p, d.st.p, d.fl.p, tol);
+  };
+  int hfl[LF_COUNT] = {0, 0, 0, 0};
+  auto read_flags = [&] {
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(hfl, d.fl.p, sizeof(hfl), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  };
+
+  // ---- LSQR: chunks of iterations between looks at the flag block ----
+  step_v(0);
+  long k = 0;  // iterations enqueued
+  long chunk = 8;
+  while (true) {
+    const long upto = std::min(cap, k + chunk);
+    while (k < upto) {
+      ++k;
+      step_u((int)k);
+      step_v((int)k);
+    }
+    read_flags();
+    if (hfl[LF_DONE] || k >= cap) break;
+    chunk = std::max(4L, std::min(k / 2, 64L));
+  }
+  if (!hfl[LF_DONE]) {  // the cap: the tests (and the figures of info) for x_cap need alpha_{cap+1}
+    step_u((int)(k + 1));
+    read_flags();
+  }
+  double hst[L_COUNT];
+  HIP_CHECK(hipMemcpyAsync(hst, d.st.p, sizeof(hst), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+
+  // ---- results ----
+  if (a.adjoint) {
+    double *dc = d.tP.p, *db = d.tA.p;  // (free now)
+    hipLaunchKernelGGL(k_adj_out, gN, bV, 0, s, (const double *)d.x.p, D, E, sigma, n, m, dc, db);
+    if (a.out[0]) HIP_CHECK(hipMemcpyAsync(a.out[0], db, sizeof(double) * m, hipMemcpyDeviceToDevice, s));
+    if (a.out[1]) HIP_CHECK(hipMemcpyAsync(a.out[1], dc, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+    if (a.out[2] && w->At.nnz > 0)
+      hipLaunchKernelGGL(k_grad_a, dim3(vec_blocks((long)w->At.nnz)), bV, 0, s, (const int *)w->At.rowptr.p, (const int *)w->At.col.p, w->At.rows,
+                         (long)w->At.nnz, (const double *)w->solx.p, (const double *)w->soly.p, (const double *)dc, (const double *)db, a.out[2]);
+    if (a.out[3] && w->Pf.nnz > 0)
+      hipLaunchKernelGGL(k_grad_p, dim3(vec_blocks((long)w->Pf.nnz)), bV, 0, s, (const int *)w->Pf.rowptr.p, (const int *)w->Pf.col.p, n, (long)w->Pf.nnz,
+                         (const int *)d.tri_up.p, (const double *)w->solx.p, (const double *)dc, a.out[3]);
+  } else {
+    launch_dproj(plan, DprojIo{d.x.p + n, nullptr, d.dW.p, d.dWmI.p}, nullptr, s);
+    hipLaunchKernelGGL(k_fwd_out, gN, bV, 0, s, (const double *)d.x.p, (const double *)d.dW.p, (const double *)d.dWmI.p, D, E, sigma, n, m, a.out[0],
+                       a.out[1], a.out[2]);
+  }
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (info) {
+    info->iters = (scs_int)std::min((long)hfl[LF_ITERS], cap);
+    info->stop = hfl[LF_STOP] ? hfl[LF_STOP] : 3;
+    info->residual = hst[L_BNORM] > 0. ? hst[L_RNORM] / hst[L_BNORM] : 0.;
+    const double den = hst[L_ANORM] * hst[L_RNORM];
+    info->normal_residual = den > 0. ? hst[L_ARNORM] / den : 0.;
+    info->time_ms = now_ms() - t0;
+  }
+}

@@ -273,6 +273,43 @@ int scs_hip_proj_cone(scs_float *x, const ScsCone *k, scs_int m, int dual) {
 }
 int scs_hip_proj_cone_spectral(scs_float *x, const ScsCone *k, scs_int m, int dual) { return proj_cone_impl(x, k, m, dual); }
 
+// W u and (W - I) u at v for the z, l, q cones (csrc/dproj.hpp): the kernels of the derivative entry points on host vectors
+int scs_hip_dproj_cone(const scs_float *v, const scs_float *u, const ScsCone *cone, scs_int len, scs_float *out_Wu, scs_float *out_WmIu) {
+  try {
+    set_last_error("");
+    if (!v || !u) throw std::runtime_error("scs_hip_dproj_cone: null vector");
+    refresh_options();
+    const ScsCone kk = short_cone(cone);
+    ScsHipWork w(opts());
+    TmpStream ts;
+    oneshot_cone_work(w, cone ? &kk : nullptr, len, /*warm=*/0, ts.s, /*no_spin=*/true);
+    w.diff_state = 1;
+    const std::string why = diff_refusal(&w);
+    if (!why.empty()) throw std::runtime_error("scs_hip_dproj_cone: " + why);
+    const size_t m = (size_t)len;
+    DevBuf<double> dv, du, dWu, dWmI, cinfo;
+    dv.upload(v, m, ts.s);
+    du.upload(u, m, ts.s);
+    dWu.alloc(m);
+    dWmI.alloc(m);
+    cinfo.alloc((size_t)3 * std::max(w.n_soc, 1));
+    DprojPlan plan;
+    plan.z = w.cone.z; plan.l = w.cone.l; plan.n_soc = w.n_soc; plan.n_soc_big = w.n_soc_big; plan.G = w.soc_G;
+    plan.off = w.soc_off.p; plan.dim = w.soc_dim.p; plan.big = w.soc_big.p;
+    plan.vh = dv.p; plan.cinfo = cinfo.p;
+    launch_dproj_prep(plan, ts.s);
+    launch_dproj(plan, DprojIo{du.p, nullptr, dWu.p, dWmI.p}, nullptr, ts.s);
+    HIP_CHECK(hipGetLastError());
+    if (out_Wu) dWu.download(out_Wu, m, ts.s);
+    if (out_WmIu) dWmI.download(out_WmIu, m, ts.s);
+    HIP_CHECK(hipStreamSynchronize(ts.s));
+    return 0;
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return -1;
+  }
+}
+
 int scs_hip_proj_cone_seq(scs_float *xs, const ScsCone *k_in, scs_int m, int dual, int count, scs_float *stats, int stats_cap) {
   const ScsCone k_short = short_cone(k_in);
   const ScsCone *k = k_in ? &k_short : nullptr;

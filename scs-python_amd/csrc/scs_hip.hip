@@ -37,6 +37,8 @@
 #include "spmv.hpp"
 #include "vec.hpp"
 #include "device_io.hpp"
+#include "dproj.hpp"
+#include "lsqr.hpp"
 
 #include "runtime.hpp"
 #include "device_csr.hpp"
@@ -46,6 +48,7 @@
 #include "loop.hpp"
 #include "batch.hpp"
 #include "matrix_update.hpp"
+#include "diff.hpp"
 
 // ================================================================ C ABI
 // A consumer compiled without USE_SPECTRAL_CONES hands over a ScsCone that ends at psize: the plain entry points copy that
@@ -190,6 +193,7 @@ scs_int scs_hip_update_device(ScsWork *w, const scs_float *b_dev, const scs_floa
     std::lock_guard<std::mutex> lock(w->mtx);
     HIP_CHECK(hipSetDevice(w->device));
     ScsHipWork::ScratchTurn turn(w);
+    w->diff_mark_stale();
     w->update_device(b_dev, c_dev);
     return 0;
   } catch (const std::exception &e) {
@@ -379,6 +383,7 @@ scs_int scs_update(ScsWork *w, scs_float *b, scs_float *c) {
     std::lock_guard<std::mutex> lock(w->mtx);
     HIP_CHECK(hipSetDevice(w->device));
     ScsHipWork::ScratchTurn turn(w);
+    w->diff_mark_stale();
     const int n = w->n, m = w->m;
     if ((!b && w->b_host_stale) || (!c && w->c_host_stale)) w->refresh_host_bc(!b, !c);  // (a kept vector that a device update replaced)
     if (b) { w->b_orig.assign(b, b + m); w->b_host_stale = false; w->b_raw_fresh = false; }
@@ -434,6 +439,7 @@ static scs_int update_matrix_entry(ScsWork *w, const scs_float *Ax, const scs_fl
                                " workspaces (live clones read it): finish the clones first");
     HIP_CHECK(hipSetDevice(w->device));
     ScsHipWork::ScratchTurn turn(w);
+    w->diff_mark_stale();
     update_matrix_impl(w, Ax, Px, dev);
     return 0;
   } catch (const std::exception &e) {
@@ -446,6 +452,102 @@ scs_int scs_hip_update_matrix(ScsWork *w, const scs_float *Ax, const scs_float *
 }
 scs_int scs_hip_update_matrix_device(ScsWork *w, const scs_float *Ax_dev, const scs_float *Px_dev) {
   return update_matrix_entry(w, Ax_dev, Px_dev, /*dev=*/true, "scs_hip_update_matrix_device");
+}
+
+// ---- derivatives of the last solve (include/scs_hip.h; csrc/diff.hpp) ----
+// every refusal comes before device work and leaves the workspace as it was.  dev: the pointers are device pointers; else host
+// pointers, staged into device buffers around the same path.
+static scs_int diff_entry(ScsWork *w, DiffCall call, const ScsHipDiffOpts *o, ScsHipDiffInfo *info, bool dev, const char *who) {
+  if (!w) {
+    set_last_error(std::string(who) + ": null workspace");
+    return -1;
+  }
+  try {
+    set_last_error("");
+    static const char *const in_adj[3] = {"gx", "gy", "gs"}, *const in_fwd[3] = {"db", "dc", ""};
+    static const char *const out_adj[4] = {"db", "dc", "dAx", "dPx"}, *const out_fwd[4] = {"dx", "dy", "ds", ""};
+    const int n = w->n, m = w->m;
+    const long in_len_adj[3] = {n, m, m}, in_len_fwd[3] = {m, n, 0};
+    const long out_len_adj[4] = {m, n, w->mats->a_nnz_in, w->mats->p_nnz_in}, out_len_fwd[4] = {n, m, m, 0};
+    const long *in_len = call.adjoint ? in_len_adj : in_len_fwd, *out_len = call.adjoint ? out_len_adj : out_len_fwd;
+    std::lock_guard<std::mutex> lock(w->mtx);
+    {
+      const std::string why = diff_refusal(w);
+      if (!why.empty()) throw std::runtime_error(std::string(who) + ": " + why);
+    }
+    if (call.adjoint && call.out[2] && w->At.nnz != w->mats->a_nnz_in)
+      throw std::runtime_error(std::string(who) + ": the resident A' does not hold nnz(A) values: dAx cannot be gathered");
+    if (call.adjoint && call.out[3]) {
+      if (!w->has_P) throw std::runtime_error(std::string(who) + ": dPx for a workspace created without P");
+      if (!w->mats->p_update_refusal.empty()) throw std::runtime_error(std::string(who) + ": " + w->mats->p_update_refusal);
+    }
+    if (dev) {
+      for (int k = 0; k < 3; ++k)
+        if (call.in[k]) check_device_vector(call.in[k], w->device, who, (std::string(call.adjoint ? in_adj[k] : in_fwd[k]) + "_dev").c_str());
+      for (int k = 0; k < 4; ++k)
+        if (call.out[k]) check_device_vector(call.out[k], w->device, who, (std::string(call.adjoint ? out_adj[k] : out_fwd[k]) + "_dev").c_str());
+    }
+    HIP_CHECK(hipSetDevice(w->device));
+    ScsHipWork::ScratchTurn turn(w);
+    if (dev) {
+      diff_impl(w, call, o, info);
+      return 0;
+    }
+    // host twin: stage, run the device path, bring the results back
+    ArenaScope no_arena(nullptr);
+    DevBuf<double> bin[3], bout[4];
+    DiffCall dc = call;
+    for (int k = 0; k < 3; ++k)
+      if (call.in[k]) {
+        bin[k].upload(call.in[k], (size_t)in_len[k], w->stream);
+        dc.in[k] = bin[k].p;
+      }
+    for (int k = 0; k < 4; ++k)
+      if (call.out[k]) {
+        bout[k].alloc((size_t)std::max(out_len[k], 1L));
+        dc.out[k] = bout[k].p;
+      }
+    HIP_CHECK(hipStreamSynchronize(w->stream));
+    diff_impl(w, dc, o, info);
+    for (int k = 0; k < 4; ++k)
+      if (call.out[k]) bout[k].download(call.out[k], (size_t)out_len[k], w->stream);
+    HIP_CHECK(hipStreamSynchronize(w->stream));
+    return 0;
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return -1;
+  }
+}
+static DiffCall adjoint_call(const scs_float *gx, const scs_float *gy, const scs_float *gs, scs_float *db, scs_float *dc, scs_float *dAx,
+                             scs_float *dPx) {
+  DiffCall c;
+  c.adjoint = true;
+  c.in[0] = gx; c.in[1] = gy; c.in[2] = gs;
+  c.out[0] = db; c.out[1] = dc; c.out[2] = dAx; c.out[3] = dPx;
+  return c;
+}
+static DiffCall derivative_call(const scs_float *db, const scs_float *dc, scs_float *dx, scs_float *dy, scs_float *ds) {
+  DiffCall c;
+  c.adjoint = false;
+  c.in[0] = db; c.in[1] = dc;
+  c.out[0] = dx; c.out[1] = dy; c.out[2] = ds;
+  return c;
+}
+scs_int scs_hip_adjoint_device(ScsWork *w, const scs_float *gx_dev, const scs_float *gy_dev, const scs_float *gs_dev, scs_float *db_dev,
+                               scs_float *dc_dev, scs_float *dAx_dev, scs_float *dPx_dev, const ScsHipDiffOpts *opts, ScsHipDiffInfo *info) {
+  return diff_entry(w, adjoint_call(gx_dev, gy_dev, gs_dev, db_dev, dc_dev, dAx_dev, dPx_dev), opts, info, /*dev=*/true, "scs_hip_adjoint_device");
+}
+scs_int scs_hip_adjoint(ScsWork *w, const scs_float *gx, const scs_float *gy, const scs_float *gs, scs_float *db, scs_float *dc, scs_float *dAx,
+                        scs_float *dPx, const ScsHipDiffOpts *opts, ScsHipDiffInfo *info) {
+  return diff_entry(w, adjoint_call(gx, gy, gs, db, dc, dAx, dPx), opts, info, /*dev=*/false, "scs_hip_adjoint");
+}
+scs_int scs_hip_derivative_device(ScsWork *w, const scs_float *db_dev, const scs_float *dc_dev, scs_float *dx_dev, scs_float *dy_dev,
+                                  scs_float *ds_dev, const ScsHipDiffOpts *opts, ScsHipDiffInfo *info) {
+  return diff_entry(w, derivative_call(db_dev, dc_dev, dx_dev, dy_dev, ds_dev), opts, info, /*dev=*/true, "scs_hip_derivative_device");
+}
+scs_int scs_hip_derivative(ScsWork *w, const scs_float *db, const scs_float *dc, scs_float *dx, scs_float *dy, scs_float *ds,
+                           const ScsHipDiffOpts *opts, ScsHipDiffInfo *info) {
+  return diff_entry(w, derivative_call(db, dc, dx, dy, ds), opts, info, /*dev=*/false, "scs_hip_derivative");
 }
 
 void scs_finish(ScsWork *w) {

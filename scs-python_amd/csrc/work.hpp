@@ -140,6 +140,12 @@ struct ScsHipWork {
   DevBuf<int> fl;
   DevBuf<double> solx, soly, sols;
   bool sol_on_device = false;  // solx/soly/sols hold the final (x, y, s) of the last solve
+  // derivatives of the solve (diff.hpp): whether solx / soly / sols can be differentiated — 0: no solve yet, 1: the last solve ended
+  // solved and nothing changed since, 2: it did not end solved, 3: b, c or the matrix changed since (the resident solution is stale) —
+  // and the scratch of those calls (nothing is allocated before the first one)
+  int diff_state = 0, last_status_val = 0;
+  void diff_mark_stale() { if (diff_state == 1) diff_state = 3; }
+  DiffScratch diff;
   // device-resident endpoints (device_io.hpp, scs_hip_update_device): the caller's b / c as they arrived, allocated by the first device
   // update.  A vector lives where it was last written: *_raw_fresh = the device copy is current, *_host_stale = b_orig / c_orig is not
   // (scs_update with one NULL argument refreshes the mirror it keeps: refresh_host_bc)

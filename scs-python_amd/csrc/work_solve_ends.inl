@@ -5,6 +5,7 @@
   void begin_solve(ScsSolution *sol, ScsInfo *info, int warm_start, bool dev_io = false) {
     std::memset(info, 0, sizeof(*info));
     info->setup_time = setup_time;
+    diff_state = 2;  // (until finish_solve says the solve ended solved)
     if (dense())
       std::snprintf(info->lin_sys_solver, sizeof(info->lin_sys_solver), "dense-direct HIP gfx950 (explicit inverse of the reduced KKT matrix, order %d; fp64 MFMA Gauss-Jordan)", n);
     else {
@@ -138,6 +139,8 @@
     if (dev_io) hand_over_solution(sol);
     else download_solution(sol);
     sol_on_device = true;
+    last_status_val = (int)info->status_val;
+    diff_state = (info->status_val == SCS_SOLVED || info->status_val == SCS_SOLVED_INACCURATE) ? 1 : 2;
     {
       double cs = 0.;
       for (double v : cs_part) cs += v;

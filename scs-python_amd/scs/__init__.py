@@ -267,6 +267,26 @@ class SCS(object):
     return self._solver.solve_many_device(b, c, warm_start, x, y, s)
 
 
+  def adjoint(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+    """Gradients of a scalar L of the last solution: given dL/dx, dL/dy, dL/ds (numpy vectors, None = 0) returns {"db", "dc", "info"}
+    and, when `want` names "A" / "P", "dA" / "dP": value arrays in the order of the (sorted CSC, upper-triangle) matrices the
+    constructor used.  Solved on the GPU by LSQR to `tol`; a degenerate solution gives the minimum-norm least-squares answer
+    (info["stop"] == 2).  Zero, nonnegative and second-order cones; ValueError after an update without a new solve."""
+    return self._solver.adjoint(dx, dy, ds, want, tol, max_iters)
+
+  def adjoint_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+    """`adjoint` over float64 torch tensors on the solver's GPU (taken and returned); same bits."""
+    return self._solver.adjoint_device(dx, dy, ds, want, tol, max_iters)
+
+  def derivative(self, db=None, dc=None, tol=1e-8, max_iters=None):
+    """The change {"dx", "dy", "ds", "info"} of the last solution for a change db, dc of the data (numpy vectors, None = 0)."""
+    return self._solver.derivative(db, dc, tol, max_iters)
+
+  def derivative_device(self, db=None, dc=None, tol=1e-8, max_iters=None):
+    """`derivative` over float64 torch tensors on the solver's GPU."""
+    return self._solver.derivative_device(db, dc, tol, max_iters)
+
+
 def solve(data, cone, **settings):
   """Legacy one-shot API; warm-start vectors may ride along in `data`."""
   solver = SCS(data, cone, **settings)

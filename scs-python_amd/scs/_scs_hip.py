@@ -88,6 +88,14 @@ class _ScsInfo(C.Structure):
                 ("aa_stats", _ScsAaStats), ("cg_iters", c_int)]
 
 
+class _ScsHipDiffOpts(C.Structure):
+    _fields_ = [("tol", c_dbl), ("max_iters", c_int)]
+
+
+class _ScsHipDiffInfo(C.Structure):
+    _fields_ = [("iters", c_int), ("residual", c_dbl), ("normal_residual", c_dbl), ("stop", c_int), ("time_ms", c_dbl)]
+
+
 class _ScsHipPoolStats(C.Structure):
     _fields_ = [("held_bytes", C.c_size_t), ("held_blocks", C.c_size_t), ("live_bytes", C.c_size_t),
                 ("hits", C.c_size_t), ("misses", C.c_size_t)]
@@ -216,6 +224,16 @@ def _load():
     lib.scs_hip_solve_batch_device.restype = c_int
     lib.scs_hip_solve_batch_device.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                C.POINTER(C.POINTER(_ScsInfo)), c_int, c_int]
+    for name in ("scs_hip_adjoint", "scs_hip_adjoint_device"):
+        fn = getattr(lib, name)
+        fn.restype = c_int
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 7 + [C.POINTER(_ScsHipDiffOpts), C.POINTER(_ScsHipDiffInfo)]
+    for name in ("scs_hip_derivative", "scs_hip_derivative_device"):
+        fn = getattr(lib, name)
+        fn.restype = c_int
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.POINTER(_ScsHipDiffOpts), C.POINTER(_ScsHipDiffInfo)]
+    lib.scs_hip_dproj_cone.restype = c_int
+    lib.scs_hip_dproj_cone.argtypes = [_PD, _PD, C.POINTER(_ScsCone), c_int, _PD, _PD]
     lib.scs_hip_work_device.restype = c_int
     lib.scs_hip_work_device.argtypes = [C.c_void_p]
     lib.scs_hip_set_mark.restype = None
@@ -893,6 +911,90 @@ class SCS(object):
             raise RuntimeError("libscs_hip: " + err)
         return out
 
+    # ------------------------------------------------------ derivatives of the last solve (include/scs_hip.h)
+    def _diff_call(self, fn, ptrs, opts):
+        info = _ScsHipDiffInfo()
+        with self._lock:
+            if not self._work:
+                raise ValueError("Workspace not initialized!")
+            rc = fn(self._work, *(list(ptrs) + [C.byref(opts), C.byref(info)]))
+            err = last_error() if rc != 0 else ""
+        if rc != 0:
+            raise ValueError("libscs_hip: " + err)
+        return {"iters": int(info.iters), "residual": float(info.residual), "normal_residual": float(info.normal_residual),
+                "stop": int(info.stop), "time_ms": float(info.time_ms)}
+
+    def _want_sizes(self, want):
+        want = _diff_want(want, self._pattern["P"] is not None)
+        sizes = {"b": self.m, "c": self.n, "A": int(self._pattern["A"][1].shape[0]),
+                 "P": int(self._pattern["P"][1].shape[0]) if self._pattern["P"] is not None else 0}
+        return want, sizes
+
+    def adjoint(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+        """The adjoint of the last solve: given dL/dx (n), dL/dy (m), dL/ds (m) — None = 0 — returns {"db", "dc", ["dA"], ["dP"],
+        "info"}, the gradients of L with respect to b, c and (`want` adds "A" / "P") the stored values of A and of the upper triangle
+        of P in the constructor's order.  One LSQR solve on the device with tolerance `tol` and at most `max_iters` iterations (None:
+        4 (n + m)); info = {"iters", "residual", "normal_residual", "stop", "time_ms"}.  A degenerate solution is not an error: the
+        minimum-norm least-squares answer comes back with stop == 2."""
+        if not self._work:
+            raise ValueError("Workspace not initialized!")
+        want, sizes = self._want_sizes(want)
+        g = [_diff_vec("dx", dx, self.n), _diff_vec("dy", dy, self.m), _diff_vec("ds", ds, self.m)]
+        opts = _diff_opts(tol, max_iters)
+        out = {k: np.zeros(sizes[k]) for k in want}
+        ptrs = [_pd(v) if v is not None else None for v in g] + [_pd(out[k]) if k in out else None for k in ("b", "c", "A", "P")]
+        info = self._diff_call(_lib.scs_hip_adjoint, ptrs, opts)
+        res = {"d" + k: out[k] for k in want}
+        res["info"] = info
+        return res
+
+    def adjoint_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+        """`adjoint` over float64 torch tensors on the solver's GPU: takes and returns device tensors; nothing of length n or m
+        crosses the host.  Same bits as `adjoint` on the same values."""
+        if not self._work:
+            raise ValueError("Workspace not initialized!")
+        want, sizes = self._want_sizes(want)
+        opts = _diff_opts(tol, max_iters)
+        dev = self._device_index()
+        g = [_device_vec(nm, t, ln, dev) if t is not None else None for nm, t, ln in (("dx", dx, self.n), ("dy", dy, self.m), ("ds", ds, self.m))]
+        import torch
+        tdev = torch.device("cuda", dev)
+        out = {k: torch.zeros(sizes[k], dtype=torch.float64, device=tdev) for k in want}
+        _sync_torch_stream(dev)  # the stream contract: inputs complete before the library's own stream reads them
+        ptrs = g + [out[k].data_ptr() if k in out and sizes[k] > 0 else None for k in ("b", "c", "A", "P")]
+        info = self._diff_call(_lib.scs_hip_adjoint_device, ptrs, opts)
+        res = {"d" + k: out[k] for k in want}
+        res["info"] = info
+        return res
+
+    def derivative(self, db=None, dc=None, tol=1e-8, max_iters=None):
+        """The forward derivative of the last solve: the change {"dx", "dy", "ds", "info"} of the solution for a change db (m), dc (n)
+        of the data (None = 0); LSQR as in `adjoint`."""
+        if not self._work:
+            raise ValueError("Workspace not initialized!")
+        d = [_diff_vec("db", db, self.m), _diff_vec("dc", dc, self.n)]
+        opts = _diff_opts(tol, max_iters)
+        out = {"dx": np.zeros(self.n), "dy": np.zeros(self.m), "ds": np.zeros(self.m)}
+        ptrs = [_pd(v) if v is not None else None for v in d] + [_pd(out[k]) for k in ("dx", "dy", "ds")]
+        out["info"] = self._diff_call(_lib.scs_hip_derivative, ptrs, opts)
+        return out
+
+    def derivative_device(self, db=None, dc=None, tol=1e-8, max_iters=None):
+        """`derivative` over float64 torch tensors on the solver's GPU."""
+        if not self._work:
+            raise ValueError("Workspace not initialized!")
+        opts = _diff_opts(tol, max_iters)
+        dev = self._device_index()
+        d = [_device_vec(nm, t, ln, dev) if t is not None else None for nm, t, ln in (("db", db, self.m), ("dc", dc, self.n))]
+        import torch
+        tdev = torch.device("cuda", dev)
+        out = {"dx": torch.zeros(self.n, dtype=torch.float64, device=tdev), "dy": torch.zeros(self.m, dtype=torch.float64, device=tdev),
+               "ds": torch.zeros(self.m, dtype=torch.float64, device=tdev)}
+        _sync_torch_stream(dev)
+        ptrs = d + [out[k].data_ptr() for k in ("dx", "dy", "ds")]
+        out["info"] = self._diff_call(_lib.scs_hip_derivative_device, ptrs, opts)
+        return out
+
     # -------------------------------------------------- bench hooks (not part of the reference surface)
     def _set_profiling(self, on):
         with self._lock:
@@ -985,6 +1087,45 @@ def _matrix_values(name, M, pattern):
     if M.shape[0] != nnz:
         raise ValueError("%s has %d values, the solver's pattern has %d" % (name, M.shape[0], nnz))
     return np.array(M, dtype=np.float64, order="C", copy=True)
+
+
+def _diff_vec(name, a, length):
+    """A host vector of `adjoint` / `derivative`, checked before the library is called (no GPU needed): None, or a 1-D numpy float array
+    of `length` elements; returns a fresh contiguous float64 copy."""
+    if a is None:
+        return None
+    if not isinstance(a, np.ndarray) or not np.issubdtype(a.dtype, np.floating) or a.ndim != 1:
+        raise TypeError("%s must be a 1-D numpy array of floats" % name)
+    if a.shape[0] != length:
+        raise ValueError("%s has incompatible dimension with A" % name)
+    return np.array(a, dtype=np.float64, order="C", copy=True)
+
+
+def _diff_want(want, have_P):
+    """`want` of `adjoint`: a tuple or list of distinct names out of "b", "c", "A", "P"; returns it as a tuple."""
+    if isinstance(want, (str, bytes)) or not isinstance(want, (tuple, list)):
+        raise TypeError("want must be a tuple of names out of 'b', 'c', 'A', 'P', not %s" % type(want).__name__)
+    for k in want:
+        if not isinstance(k, str) or k not in ("b", "c", "A", "P"):
+            raise ValueError("want holds %r: the names are 'b', 'c', 'A', 'P'" % (k,))
+    if len(set(want)) != len(want):
+        raise ValueError("want names an output twice")
+    if "P" in want and not have_P:
+        raise ValueError("dP wanted, but the solver was created without P")
+    return tuple(want)
+
+
+def _diff_opts(tol, max_iters):
+    """tol: a positive finite real; max_iters: None (the default, 4 (n + m)) or a positive int"""
+    t = _as_c_double("tol", tol)
+    if isinstance(tol, (bool, np.bool_)) or not np.isfinite(t) or t <= 0:
+        raise ValueError("tol must be a positive finite number")
+    it = 0
+    if max_iters is not None:
+        it = _as_c_int("max_iters", max_iters)
+        if isinstance(max_iters, (bool, np.bool_)) or it <= 0:
+            raise ValueError("max_iters must be positive")
+    return _ScsHipDiffOpts(t, it)
 
 
 def _device_vec(name, t, length, device):
@@ -1225,6 +1366,18 @@ def proj_cone(z, cone, dual=False):
     k, keep = _cone_struct(cone)
     _check(_lib.scs_hip_proj_cone_spectral(_pd(x), C.byref(k), x.size, 1 if dual else 0))
     return x
+
+
+def dproj_cone(v, u, cone):
+    """(W u, (W - I) u) with W the derivative of the projection onto the cone at v: the kernels of `SCS.adjoint` (z, l, q cones)"""
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    u = np.ascontiguousarray(u, dtype=np.float64)
+    if v.ndim != 1 or v.shape != u.shape:
+        raise ValueError("v and u must be 1-D arrays of one length")
+    k, _keep = _cone_struct(cone)
+    wu, wmiu = np.zeros_like(v), np.zeros_like(v)
+    _check(_lib.scs_hip_dproj_cone(_pd(v), _pd(u), C.byref(k), v.shape[0], _pd(wu), _pd(wmiu)))
+    return wu, wmiu
 
 
 def trim_pool():
