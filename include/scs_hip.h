@@ -97,7 +97,7 @@ SCS_HIP_API double scs_hip_spmv_bench(const ScsMatrix *A, int transpose, int rep
 SCS_HIP_API int scs_hip_proj_cone(scs_float *x, const ScsCone *k, scs_int m, int dual);
 
 /* The derivative of that projection (csrc/dproj.hpp) at v, applied to u: out_Wu = W u and out_WmIu = (W - I) u with W = D Pi_K(v)
- * (v, u, the outputs: `len` doubles, host pointers; an output may be NULL).  Zero, nonnegative and second-order cones only.  (parity tests) */
+ * (v, u, the outputs: `len` doubles, host pointers; an output may be NULL).  Zero, nonnegative, second-order and real PSD (s) cones only.  (parity tests) */
 SCS_HIP_API int scs_hip_dproj_cone(const scs_float *v, const scs_float *u, const ScsCone *cone, scs_int len, scs_float *out_Wu, scs_float *out_WmIu);
 
 /* The same projection applied to `count` vectors one after the other (xs: count x m, row-major, in place) through ONE set of cone
@@ -215,7 +215,7 @@ SCS_HIP_API scs_int scs_hip_update_matrix_device(ScsWork *w, const scs_float *Ax
  *
  * Returns 0, or -1 with the reason in scs_hip_last_error — refused before any device work, the workspace unchanged and usable: a NULL
  * workspace; no solve yet, or the last solve did not end SCS_SOLVED / SCS_SOLVED_INACCURATE; scs_update, scs_hip_update_device or
- * scs_hip_update_matrix[_device] ran since the last solve (the resident solution is stale); a cone other than z, l, q (named in the
+ * scs_hip_update_matrix[_device] ran since the last solve (the resident solution is stale); a cone other than z, l, q, s (named in the
  * message); (device entries) a pointer that is not device memory of the workspace's device; dPx for a workspace created without P, or
  * with a P whose values scs_hip_update_matrix would refuse (entries below the diagonal, unsorted rows). */
 typedef struct {

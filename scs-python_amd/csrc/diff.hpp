@@ -6,7 +6,9 @@
 //            dL/dA_ij = -(y_i lambda1_j + lambda2_i x_j),  dL/dP_ij = -(lambda1_i x_j + lambda1_j x_i) (i < j),  dL/dP_ii = -lambda1_i x_i
 // forward:   J (dx ; dv) = (-dc ; db),  ds = W dv,  dy = (W - I) dv
 // The systems are solved by LSQR (lsqr.hpp) on the RESIDENT, equilibrated matrices A^ = D A E, P^ = E P E at v^ = sigma (D s - y / D):
-// the hatted problem has the same F, and D is constant on every SOC block.  In: gx^ = E gx / sigma, gy^ = D gy / sigma,
+// the hatted problem has the same F, and D is constant on every SOC block and on every PSD block (normalize_dev.hpp k_enforce_blocks), so
+// Pi commutes with the scaling there and the derivation carries over to the s cones unchanged (dproj_psd.hpp).
+// In: gx^ = E gx / sigma, gy^ = D gy / sigma,
 // gs^ = gs / (D sigma), dc^ = sigma E dc, db^ = sigma D db.  Out: dL/dc = sigma E dL/dc^, dL/db = sigma D dL/db^,
 // dL/dA_ij = D_i E_j dL/dA^_ij, dL/dP_ij = E_i E_j dL/dP^_ij; dx = E dx^ / sigma, dy = D dy^ / sigma, ds = ds^ / (D sigma).  With
 // mu = sigma E lambda1 = -dL/dc and nu = sigma D lambda2 = dL/db the matrix gradients need the caller's x, y only:
@@ -16,7 +18,8 @@
 //     J' l = [P l1 + A' l2 ; (W - I)(A l1) + W l2] = [.. ; W (A l1 + l2) - A l1]        J q = [P q1 + A'((W - I) q2) ; A q1 + W q2]
 // The products go through launch_spmv with EpiStore (every layout finishes it: the split pass layout through k_epi_finish).
 //
-// A call reads solx / soly / sols and the matrices, and writes the workspace's DiffScratch only.
+// A call reads solx / soly / sols and the matrices, and writes the workspace's DiffScratch only (the eigen-decomposition of the PSD
+// blocks borrows a block of the pool for the call; the solve's psd_scratch is not touched).
 #pragma once
 
 namespace scship {
@@ -96,10 +99,10 @@ static std::string diff_refusal(const ScsHipWork *w) {
   if (w->diff_state == 2) return "the last solve did not end solved (status " + std::to_string(w->last_status_val) + "): there is no solution to differentiate";
   if (w->diff_state == 3) return "the resident solution is stale: b, c or the matrix changed since the last solve; solve again first";
   const HostCone &c = w->cone;
-  const char *other = c.bsize > 1 ? "box" : !c.s.empty() ? "PSD (s)" : !c.cs.empty() ? "complex PSD (cs)" : c.ep > 0 ? "exponential (ep)" :
+  const char *other = c.bsize > 1 ? "box" : !c.cs.empty() ? "complex PSD (cs)" : c.ep > 0 ? "exponential (ep)" :
                       c.ed > 0 ? "dual exponential (ed)" : !c.p.empty() ? "power (p)" : !c.d.empty() ? "log-det (d)" :
                       !c.nuc_m.empty() ? "nuclear norm (nuc)" : !c.ell1.empty() ? "ell1" : !c.sl_n.empty() ? "sum-of-largest (sl)" : nullptr;
-  if (other) return std::string("the derivative of the ") + other + " cone projection is not implemented (z, l and q cones only)";
+  if (other) return std::string("the derivative of the ") + other + " cone projection is not implemented (z, l, q and s cones only)";
   return "";
 }
 
@@ -118,6 +121,7 @@ static void diff_alloc(ScsHipWork *w) {
   for (DevBuf<double> *b : {&d.tA, &d.dW, &d.dWmI, &d.vhat}) b->alloc(m);
   for (DevBuf<double> *b : {&d.tAt, &d.tP}) b->alloc(n);
   d.cinfo.alloc((size_t)3 * std::max(w->n_soc, 1));
+  d.psd.build(w->psd_order_h, w->psd_off.p, w->psd_order.p, w->psd_woff.p, w->stream);
   const size_t nb = (size_t)vec_blocks((long)N);
   for (DevBuf<double> *b : {&d.partU, &d.partV, &d.partX}) b->alloc(nb);
   d.st.alloc(L_COUNT);
@@ -171,7 +175,9 @@ static void diff_impl(ScsHipWork *w, const DiffCall &a, const ScsHipDiffOpts *o,
   DprojPlan plan;
   plan.z = w->cone.z; plan.l = w->cone.l; plan.n_soc = w->n_soc; plan.n_soc_big = w->n_soc_big; plan.G = w->soc_G;
   plan.off = w->soc_off.p; plan.dim = w->soc_dim.p; plan.big = w->soc_big.p;
-  plan.vh = d.vhat.p; plan.cinfo = d.cinfo.p;
+  plan.vh = d.vhat.p; plan.cinfo = d.cinfo.p; plan.m = m;
+  plan.psd = d.psd.plan;
+  plan.psd.tmp_m = d.dW.p;  // (free until the right-hand side is formed)
   launch_dproj_prep(plan, s);
 
   // ---- right-hand side into uh, x = w = 0 ----

@@ -1,4 +1,4 @@
-// dproj.hpp — W = D Pi_K(v), the derivative of the cone projection, applied to a vector: zero, nonnegative and second-order cones.
+// dproj.hpp — W = D Pi_K(v), the derivative of the cone projection, applied to a vector: zero, nonnegative, second-order and real PSD cones.
 //
 // The adjoint and the forward derivative of a solve (lsqr.hpp, diff.hpp) need W u and (W - I) u at the fixed point v = s - y of the
 // last solve.  W is symmetric and block diagonal by cone:
@@ -6,6 +6,7 @@
 //   nonnegative rows   W_ii = 1 if v_i > 0 else 0
 //   SOC, v = (t, z), r = |z|:   W = I if r <= t;   W = 0 if r <= -t;   else
 //                      W = 1/(2r) [[r, z'], [z, (t + r) I - t z z'/r^2]]
+//   PSD blocks         dproj_psd.hpp
 //
 // Mapping to the machine follows the projections (cones.hpp): the off / dim tables, one lane group of soc_group() = 8/16/32/64 lanes per
 // cone up to kSocBig entries, one workgroup per longer cone, q == 1 treated as a nonnegative row.  A preparation pass runs once per
@@ -15,6 +16,23 @@
 #include "common.hpp"
 #include "cones.hpp"
 #include "vec.hpp"
+
+namespace scship {
+
+// ---- apply: u = a (+ b);  Wu = W u, WmIu = (W - I) u  (either output may be nullptr; outputs never alias inputs) ----
+struct DprojIo {
+  const double *a, *b;  // b nullable
+  double *Wu, *WmIu;
+  __device__ __forceinline__ double u(long i) const { return b ? a[i] + b[i] : a[i]; }
+  __device__ __forceinline__ void put(long i, double wu, double ui) const {
+    if (Wu) Wu[i] = wu;
+    if (WmIu) WmIu[i] = wu - ui;
+  }
+};
+
+}  // namespace scship
+
+#include "dproj_psd.hpp"  // the PSD blocks (needs DprojIo)
 
 namespace scship {
 
@@ -70,16 +88,7 @@ __global__ __launch_bounds__(kConeThreads) void k_dproj_prep_block(const double 
   cinfo[3 * c + 2] = r;
 }
 
-// ---- apply: u = a (+ b);  Wu = W u, WmIu = (W - I) u  (either output may be nullptr; outputs never alias inputs) ----
-struct DprojIo {
-  const double *a, *b;  // b nullable
-  double *Wu, *WmIu;
-  __device__ __forceinline__ double u(long i) const { return b ? a[i] + b[i] : a[i]; }
-  __device__ __forceinline__ void put(long i, double wu, double ui) const {
-    if (Wu) Wu[i] = wu;
-    if (WmIu) WmIu[i] = wu - ui;
-  }
-};
+// ---- apply (DprojIo above) ----
 // the z zero rows and the l nonnegative rows
 __global__ __launch_bounds__(kVecThreads) void k_dproj_zl(DprojIo io, const double *__restrict__ vh, int z, int l, const int *done) {
   if (done && *done) return;
@@ -167,14 +176,18 @@ struct DprojPlan {
   const int *off = nullptr, *dim = nullptr, *big = nullptr;
   const double *vh = nullptr;  // the fixed point (m)
   double *cinfo = nullptr;     // 3 doubles per SOC
+  long m = 0;                  // length of vh
+  DprojPsdPlan psd;            // the PSD blocks (dproj_psd.hpp); count == 0: none
 };
 inline void launch_dproj_prep(const DprojPlan &p, hipStream_t s) {
+  launch_dproj_psd_prep(p.psd, p.vh, p.m, s);
   if (p.n_soc <= 0) return;
   hipLaunchKernelGGL(k_dproj_prep_wave, dim3(soc_wave_blocks(p.n_soc, p.G)), dim3(kConeThreads), 0, s, p.vh, p.off, p.dim, p.n_soc, p.G, p.cinfo);
   if (p.n_soc_big > 0) hipLaunchKernelGGL(k_dproj_prep_block, dim3(p.n_soc_big), dim3(kConeThreads), 0, s, p.vh, p.off, p.dim, p.big, p.cinfo);
 }
 inline void launch_dproj(const DprojPlan &p, const DprojIo &io, const int *done, hipStream_t s) {
   if (p.z + p.l > 0) hipLaunchKernelGGL(k_dproj_zl, dim3(vec_blocks(p.z + p.l)), dim3(kVecThreads), 0, s, io, p.vh, p.z, p.l, done);
+  launch_dproj_psd(p.psd, io, done, s);
   if (p.n_soc <= 0) return;
   hipLaunchKernelGGL(k_dproj_soc_wave, dim3(soc_wave_blocks(p.n_soc, p.G)), dim3(kConeThreads), 0, s, io, p.vh, (const double *)p.cinfo, p.off, p.dim,
                      p.n_soc, p.G, done);

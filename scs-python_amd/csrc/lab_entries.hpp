@@ -273,7 +273,7 @@ int scs_hip_proj_cone(scs_float *x, const ScsCone *k, scs_int m, int dual) {
 }
 int scs_hip_proj_cone_spectral(scs_float *x, const ScsCone *k, scs_int m, int dual) { return proj_cone_impl(x, k, m, dual); }
 
-// W u and (W - I) u at v for the z, l, q cones (csrc/dproj.hpp): the kernels of the derivative entry points on host vectors
+// W u and (W - I) u at v for the z, l, q, s cones (csrc/dproj.hpp, dproj_psd.hpp): the kernels of the derivative entry points on host vectors
 int scs_hip_dproj_cone(const scs_float *v, const scs_float *u, const ScsCone *cone, scs_int len, scs_float *out_Wu, scs_float *out_WmIu) {
   try {
     set_last_error("");
@@ -296,7 +296,11 @@ int scs_hip_dproj_cone(const scs_float *v, const scs_float *u, const ScsCone *co
     DprojPlan plan;
     plan.z = w.cone.z; plan.l = w.cone.l; plan.n_soc = w.n_soc; plan.n_soc_big = w.n_soc_big; plan.G = w.soc_G;
     plan.off = w.soc_off.p; plan.dim = w.soc_dim.p; plan.big = w.soc_big.p;
-    plan.vh = dv.p; plan.cinfo = cinfo.p;
+    plan.vh = dv.p; plan.cinfo = cinfo.p; plan.m = len;
+    DprojPsdTables psd;
+    psd.build(w.psd_order_h, w.psd_off.p, w.psd_order.p, w.psd_woff.p, ts.s);
+    plan.psd = psd.plan;
+    plan.psd.tmp_m = dWu.p;  // (overwritten by the apply)
     launch_dproj_prep(plan, ts.s);
     launch_dproj(plan, DprojIo{du.p, nullptr, dWu.p, dWmI.p}, nullptr, ts.s);
     HIP_CHECK(hipGetLastError());

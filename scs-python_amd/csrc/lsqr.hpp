@@ -174,10 +174,12 @@ __global__ __launch_bounds__(kVecThreads) void k_lsqr_u(int k, LsqrProd tu, doub
 }
 
 // Scratch of the derivative entry points (diff.hpp): taken from the block pool at a workspace's first call, kept until scs_finish.
-// 4 vectors of n + m (uh, vh, w, x), 4 of m (tA, dW, dWmI, vhat), 2 of n (tAt, tP): 8 m + 6 n doubles, plus partials and cone records.
+// 4 vectors of n + m (uh, vh, w, x), 4 of m (tA, dW, dWmI, vhat), 2 of n (tAt, tP): 8 m + 6 n doubles, plus partials and cone records,
+// plus 4 NP^2 + NP doubles per PSD block (dproj_psd.hpp DprojPsdTables: V, V', lam, two apply frames).
 struct DiffScratch {
   bool ready = false, tri_ready = false;
   DevBuf<double> uh, vh, w, x, tA, dW, dWmI, vhat, tAt, tP, cinfo, partU, partV, partX, st;
+  DprojPsdTables psd;
   DevBuf<int> fl, tri_up;  // tri_up: column pointers of the caller's triangle of P (the gather of dL/dP), built at the first request
 };
 

@@ -254,7 +254,15 @@ __device__ __forceinline__ double psd_fmap(double a, double dj, double dk, bool 
   const double gdd = lo > 0. ? 1. : (hi <= 0. ? 0. : hi / (hi - lo));
   return diag ? fmax(dk, 0.) : a * gdd;
 }
-template <bool FMAP = false>
+// FMAP == kPsdMapDiff: the B operand is B o A with the first divided differences B_jk of max(., 0) at d (the derivative of the
+// projection, dproj_psd.hpp): the same gdd off the diagonal, and on it gdd's own limit — 1 where d_k > 0, else 0 — times A_kk
+constexpr int kPsdMapDiff = 2;
+__device__ __forceinline__ double psd_dmap(double a, double dj, double dk) {
+  const double hi = fmax(dj, dk), lo = fmin(dj, dk);
+  const double gdd = lo > 0. ? 1. : (hi <= 0. ? 0. : hi / (hi - lo));
+  return a * gdd;
+}
+template <int FMAP = 0>
 __device__ __forceinline__ void mma_row(const double *__restrict__ Aop, const double *__restrict__ Bop, int ld, int NP, int ti,
                                         int tj0, int tjmax, int li, int lk, f64x4 (&acc)[kPsdNJ], const double *lam = nullptr) {
   const double *pa = Aop + (ti * 16 + li) + (size_t)ld * lk;
@@ -277,7 +285,7 @@ __device__ __forceinline__ void mma_row(const double *__restrict__ Aop, const do
     if (FMAP) {
       const double dk = lam[k0 + lk];
 #pragma unroll
-      for (int j = 0; j < kPsdNJ; ++j) b[j] = psd_fmap(b[j], dj[j], dk, rowj[j] == k0 + lk);
+      for (int j = 0; j < kPsdNJ; ++j) b[j] = FMAP == kPsdMapDiff ? psd_dmap(b[j], dj[j], dk) : psd_fmap(b[j], dj[j], dk, rowj[j] == k0 + lk);
     }
 #pragma unroll
     for (int j = 0; j < kPsdNJ; ++j) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[j], acc[j], 0, 0, 0);
@@ -338,7 +346,7 @@ __device__ __forceinline__ void psd_task_g2(int task, int NP, double *A, const d
 // R1: T = V F  (F symmetric, formed on the fly from the diagonalised A and lam = its diagonal)
 // (FMAP = false: `A` is F itself, formed once by k_psd_fmap — the split pipeline; the divided differences cost a division each and
 // every element of F is an operand of NP / 16 row tiles)
-template <bool FMAP = true>
+template <int FMAP = 1>
 __device__ __forceinline__ void psd_task_r1(int task, int NP, const double *A, const double *V, double *Tm, const double *lam,
                                             double *Sw, int li, int lk) {
   const int ld = NP, ntile = NP / 16;

@@ -271,7 +271,7 @@ class SCS(object):
     """Gradients of a scalar L of the last solution: given dL/dx, dL/dy, dL/ds (numpy vectors, None = 0) returns {"db", "dc", "info"}
     and, when `want` names "A" / "P", "dA" / "dP": value arrays in the order of the (sorted CSC, upper-triangle) matrices the
     constructor used.  Solved on the GPU by LSQR to `tol`; a degenerate solution gives the minimum-norm least-squares answer
-    (info["stop"] == 2).  Zero, nonnegative and second-order cones; ValueError after an update without a new solve."""
+    (info["stop"] == 2).  Zero, nonnegative, second-order and real PSD (s) cones; ValueError after an update without a new solve."""
     return self._solver.adjoint(dx, dy, ds, want, tol, max_iters)
 
   def adjoint_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):

@@ -1369,7 +1369,7 @@ def proj_cone(z, cone, dual=False):
 
 
 def dproj_cone(v, u, cone):
-    """(W u, (W - I) u) with W the derivative of the projection onto the cone at v: the kernels of `SCS.adjoint` (z, l, q cones)"""
+    """(W u, (W - I) u) with W the derivative of the projection onto the cone at v: the kernels of `SCS.adjoint` (z, l, q and s cones)"""
     v = np.ascontiguousarray(v, dtype=np.float64)
     u = np.ascontiguousarray(u, dtype=np.float64)
     if v.ndim != 1 or v.shape != u.shape:
