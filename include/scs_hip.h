@@ -237,6 +237,36 @@ SCS_HIP_API scs_int scs_hip_derivative_device(ScsWork *w, const scs_float *db_de
                                               scs_float *dy_dev, scs_float *ds_dev, const ScsHipDiffOpts *opts, ScsHipDiffInfo *info);
 SCS_HIP_API scs_int scs_hip_derivative(ScsWork *w, const scs_float *db, const scs_float *dc, scs_float *dx, scs_float *dy, scs_float *ds,
                                        const ScsHipDiffOpts *opts, ScsHipDiffInfo *info);
+
+/* The same for a batch of `count` solved workspaces (csrc/diff_batch.hpp).  Members that agree in device, n, m, has-P, normalisation,
+ * the z / l / q / s cone structure and in whether dAx / dPx are requested, whose matrices use the CSR-stream layout and whose PSD blocks
+ * have order <= 32, are differentiated in lock step and SHARE every launch of the LSQR iteration (blockIdx.y = member); every other
+ * member is served by the one-workspace path in turn.  Each member's outputs, info->iters, stop, residual and normal_residual are
+ * bit-identical to its own scs_hip_adjoint[_device] / scs_hip_derivative[_device] call (time_ms is the group's).  A call writes nothing
+ * a later solve reads.
+ *   Every array argument holds `count` entries and may be NULL ("no such input or output for any member"); an entry may be NULL too.
+ *   opts (tol, max_iters) hold for every member; info may be NULL, and so may info[i].
+ *   Refusals are those of the one-workspace entries, checked for EVERY member before any device work: the call returns -1, writes no
+ *   output, scs_hip_last_error() names the member index and the reason, and every workspace stays usable.  A workspace that appears
+ *   twice, a NULL member and count <= 0 are refused as well.  The workspaces must live on one device and must not be used by other
+ *   threads meanwhile (as scs_hip_solve_batch).  The grouped preparation of PSD members borrows at most 256 MiB of pool scratch at once.
+ * scs_hip_adjoint_batch / scs_hip_derivative_batch take HOST pointers, stage them and run the device path (same bits). */
+SCS_HIP_API scs_int scs_hip_adjoint_batch_device(ScsWork **w, const scs_float **gx_dev, const scs_float **gy_dev, const scs_float **gs_dev,
+                                                 scs_float **db_dev, scs_float **dc_dev, scs_float **dAx_dev, scs_float **dPx_dev,
+                                                 const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count);
+SCS_HIP_API scs_int scs_hip_adjoint_batch(ScsWork **w, const scs_float **gx, const scs_float **gy, const scs_float **gs, scs_float **db,
+                                          scs_float **dc, scs_float **dAx, scs_float **dPx, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info,
+                                          scs_int count);
+SCS_HIP_API scs_int scs_hip_derivative_batch_device(ScsWork **w, const scs_float **db_dev, const scs_float **dc_dev, scs_float **dx_dev,
+                                                    scs_float **dy_dev, scs_float **ds_dev, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info,
+                                                    scs_int count);
+SCS_HIP_API scs_int scs_hip_derivative_batch(ScsWork **w, const scs_float **db, const scs_float **dc, scs_float **dx, scs_float **dy,
+                                             scs_float **ds, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count);
+/* The grouping those entries would use for members that all request (want_dA, want_dP), as scs_hip_batch_plan: group_of[i] = the index
+ * of member i's group, -1 = served alone.  Returns the number of groups, -1 on error. */
+SCS_HIP_API int scs_hip_diff_batch_plan(ScsWork **w, scs_int count, int want_dA, int want_dP, scs_int *group_of);
+/* grouped launches issued by the batch derivative entries since the process started (tests, tools; as scs_hip_tiled_launches) */
+SCS_HIP_API long scs_hip_diff_group_launches(void);
 /* the HIP device a workspace lives on (-1: NULL) */
 SCS_HIP_API int scs_hip_work_device(const ScsWork *w);
 

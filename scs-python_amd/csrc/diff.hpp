@@ -18,6 +18,9 @@
 //     J' l = [P l1 + A' l2 ; (W - I)(A l1) + W l2] = [.. ; W (A l1 + l2) - A l1]        J q = [P q1 + A'((W - I) q2) ; A q1 + W q2]
 // The products go through launch_spmv with EpiStore (every layout finishes it: the split pass layout through k_epi_finish).
 //
+// Every kernel here, in lsqr.hpp, dproj.hpp and dproj_psd.hpp is a __device__ body d_X with its one-problem entry k_X; a batch of
+// workspaces is differentiated in lock step through the grouped entries of the same bodies (diff_batch.hpp).
+//
 // A call reads solx / soly / sols and the matrices, and writes the workspace's DiffScratch only (the eigen-decomposition of the PSD
 // blocks borrows a block of the pool for the call; the solve's psd_scratch is not touched).
 #pragma once
@@ -25,9 +28,9 @@
 namespace scship {
 
 // uh[0..n) = E gx / sigma;  gyh = D gy / sigma;  gsh = gs / (D sigma)   (a missing input counts as 0; D == nullptr: as they are)
-__global__ __launch_bounds__(kVecThreads) void k_adj_in(const double *gx, const double *gy, const double *gs, const double *__restrict__ D,
-                                                        const double *__restrict__ E, double sigma, int n, int m, double *uh, double *gyh,
-                                                        double *gsh) {
+__device__ __forceinline__ void d_adj_in(const double *gx, const double *gy, const double *gs, const double *__restrict__ D,
+                                         const double *__restrict__ E, double sigma, int n, int m, double *uh, double *gyh,
+                                         double *gsh) {
   for (long i = (long)blockIdx.x * kVecThreads + threadIdx.x; i < (long)n + m; i += (long)gridDim.x * kVecThreads) {
     if (i < n) {
       uh[i] = gx ? (E ? E[i] * gx[i] / sigma : gx[i]) : 0.;
@@ -38,26 +41,39 @@ __global__ __launch_bounds__(kVecThreads) void k_adj_in(const double *gx, const 
     }
   }
 }
+__global__ __launch_bounds__(kVecThreads) void k_adj_in(const double *gx, const double *gy, const double *gs, const double *__restrict__ D,
+                                                        const double *__restrict__ E, double sigma, int n, int m, double *uh, double *gyh,
+                                                        double *gsh) {
+  d_adj_in(gx, gy, gs, D, E, sigma, n, m, uh, gyh, gsh);
+}
 // uh = (-sigma E dc ; sigma D db)
-__global__ __launch_bounds__(kVecThreads) void k_fwd_in(const double *db, const double *dc, const double *__restrict__ D,
-                                                        const double *__restrict__ E, double sigma, int n, int m, double *uh) {
+__device__ __forceinline__ void d_fwd_in(const double *db, const double *dc, const double *__restrict__ D,
+                                         const double *__restrict__ E, double sigma, int n, int m, double *uh) {
   for (long i = (long)blockIdx.x * kVecThreads + threadIdx.x; i < (long)n + m; i += (long)gridDim.x * kVecThreads) {
     if (i < n) uh[i] = dc ? -(E ? sigma * E[i] * dc[i] : dc[i]) : 0.;
     else uh[i] = db ? (D ? sigma * D[i - n] * db[i - n] : db[i - n]) : 0.;
   }
 }
+__global__ __launch_bounds__(kVecThreads) void k_fwd_in(const double *db, const double *dc, const double *__restrict__ D,
+                                                        const double *__restrict__ E, double sigma, int n, int m, double *uh) {
+  d_fwd_in(db, dc, D, E, sigma, n, m, uh);
+}
 // dc = -sigma E lambda1;  db = sigma D lambda2
-__global__ __launch_bounds__(kVecThreads) void k_adj_out(const double *__restrict__ lam, const double *__restrict__ D, const double *__restrict__ E,
-                                                         double sigma, int n, int m, double *dc, double *db) {
+__device__ __forceinline__ void d_adj_out(const double *__restrict__ lam, const double *__restrict__ D, const double *__restrict__ E,
+                                          double sigma, int n, int m, double *dc, double *db) {
   for (long i = (long)blockIdx.x * kVecThreads + threadIdx.x; i < (long)n + m; i += (long)gridDim.x * kVecThreads) {
     if (i < n) dc[i] = -(E ? sigma * E[i] * lam[i] : lam[i]);
     else db[i - n] = D ? sigma * D[i - n] * lam[i] : lam[i];
   }
 }
+__global__ __launch_bounds__(kVecThreads) void k_adj_out(const double *__restrict__ lam, const double *__restrict__ D, const double *__restrict__ E,
+                                                         double sigma, int n, int m, double *dc, double *db) {
+  d_adj_out(lam, D, E, sigma, n, m, dc, db);
+}
 // dx = E dx^ / sigma;  dy = D (W - I) dv^ / sigma;  ds = W dv^ / (D sigma)   (a nullptr output is skipped)
-__global__ __launch_bounds__(kVecThreads) void k_fwd_out(const double *__restrict__ q, const double *__restrict__ Wq, const double *__restrict__ WmIq,
-                                                         const double *__restrict__ D, const double *__restrict__ E, double sigma, int n, int m,
-                                                         double *dx, double *dy, double *ds) {
+__device__ __forceinline__ void d_fwd_out(const double *__restrict__ q, const double *__restrict__ Wq, const double *__restrict__ WmIq,
+                                          const double *__restrict__ D, const double *__restrict__ E, double sigma, int n, int m,
+                                          double *dx, double *dy, double *ds) {
   for (long i = (long)blockIdx.x * kVecThreads + threadIdx.x; i < (long)n + m; i += (long)gridDim.x * kVecThreads) {
     if (i < n) {
       if (dx) dx[i] = E ? E[i] * q[i] / sigma : q[i];
@@ -68,20 +84,30 @@ __global__ __launch_bounds__(kVecThreads) void k_fwd_out(const double *__restric
     }
   }
 }
+__global__ __launch_bounds__(kVecThreads) void k_fwd_out(const double *__restrict__ q, const double *__restrict__ Wq, const double *__restrict__ WmIq,
+                                                         const double *__restrict__ D, const double *__restrict__ E, double sigma, int n, int m,
+                                                         double *dx, double *dy, double *ds) {
+  d_fwd_out(q, Wq, WmIq, D, E, sigma, n, m, dx, dy, ds);
+}
 // dL/dA over the caller's CSC order = the CSR of A': slot p = (row j of A' = column of A, column i = row of A)
-__global__ __launch_bounds__(kVecThreads) void k_grad_a(const int *__restrict__ rp, const int *__restrict__ ci, int rows, long nnz,
-                                                        const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ dc,
-                                                        const double *__restrict__ db, double *dA) {
+__device__ __forceinline__ void d_grad_a(const int *__restrict__ rp, const int *__restrict__ ci, int rows, long nnz,
+                                         const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ dc,
+                                         const double *__restrict__ db, double *dA) {
   for (long p = (long)blockIdx.x * kVecThreads + threadIdx.x; p < nnz; p += (long)gridDim.x * kVecThreads) {
     const int j = vm_row_of(rp, rows, p), i = ci[p];
     dA[p] = y[i] * dc[j] - db[i] * x[j];  // -(y_i mu_j + nu_i x_j), mu = -dc, nu = db
   }
 }
+__global__ __launch_bounds__(kVecThreads) void k_grad_a(const int *__restrict__ rp, const int *__restrict__ ci, int rows, long nnz,
+                                                        const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ dc,
+                                                        const double *__restrict__ db, double *dA) {
+  d_grad_a(rp, ci, rows, nnz, x, y, dc, db, dA);
+}
 // dL/dP over the caller's triangle: the entries of row r of the full matrix on or below the diagonal are column r of the triangle, in
 // order (matrix_update.hpp k_map_pf); up = the triangle's column pointers
-__global__ __launch_bounds__(kVecThreads) void k_grad_p(const int *__restrict__ rp, const int *__restrict__ ci, int n, long nnz,
-                                                        const int *__restrict__ up, const double *__restrict__ x, const double *__restrict__ dc,
-                                                        double *dP) {
+__device__ __forceinline__ void d_grad_p(const int *__restrict__ rp, const int *__restrict__ ci, int n, long nnz,
+                                         const int *__restrict__ up, const double *__restrict__ x, const double *__restrict__ dc,
+                                         double *dP) {
   for (long q = (long)blockIdx.x * kVecThreads + threadIdx.x; q < nnz; q += (long)gridDim.x * kVecThreads) {
     const int r = vm_row_of(rp, n, q), c = ci[q];
     if (c > r) continue;
@@ -89,6 +115,11 @@ __global__ __launch_bounds__(kVecThreads) void k_grad_p(const int *__restrict__ 
     if (k >= up[r + 1] - up[r]) continue;
     dP[up[r] + k] = c < r ? dc[c] * x[r] + dc[r] * x[c] : dc[r] * x[r];  // -(mu_c x_r + mu_r x_c), mu = -dc
   }
+}
+__global__ __launch_bounds__(kVecThreads) void k_grad_p(const int *__restrict__ rp, const int *__restrict__ ci, int n, long nnz,
+                                                        const int *__restrict__ up, const double *__restrict__ x, const double *__restrict__ dc,
+                                                        double *dP) {
+  d_grad_p(rp, ci, n, nnz, up, x, dc, dP);
 }
 
 }  // namespace scship

@@ -1,0 +1,432 @@
+// diff_batch.hpp — grouped derivative: G equally shaped, solved workspaces are differentiated in lock step, ONE launch per kernel of
+// the LSQR iteration for the whole group (include/scs_hip.h: scs_hip_adjoint_batch[_device], scs_hip_derivative_batch[_device]).
+//
+// The reason is the one of batch.hpp: a small problem's LSQR iteration is 10-16 dependent launches of ~5 us, a hardware queue retires
+// them one after the other, so K members differentiated in turn are bound by the command queue.  The means are the ones of batch.hpp
+// too: every kernel of diff.hpp / lsqr.hpp / dproj.hpp / dproj_psd.hpp is a __device__ body with its one-problem entry k_X and the
+// generic entry k_grouped<d_X, ..> (blockIdx.y = member, blockIdx.x = what the one-problem launch uses, arguments from a per-member
+// record).  Same code, same block decomposition, same partial sums => every member's outputs, iteration count, stopping rule and
+// residual figures are bit-identical to a call of its own (tests/test_adjoint_batch_gpu.py).
+//
+// GroupDiff::run is diff_impl applied to every member.  The members share the iteration index k (a launch-level argument of the two
+// LSQR kernels: k_grouped_k); a member that has converged drops out of the member list, and until the host has seen its flag its
+// kernels return at once on its own done flag.  Per chunk of iterations ONE gather launch and ONE copy of G x LF_COUNT ints cross the
+// host.  Each member keeps its own DiffScratch; the group owns the argument tables, the member lists and the two gathered blocks, and
+// gives its device blocks back to the block pool when the call ends.
+#pragma once
+
+namespace scship {
+
+// a table body whose FIRST argument is launch-level (the same for every member): the LSQR iteration index
+template <auto Fn, int Threads, class... A>
+__global__ __launch_bounds__(Threads) void k_grouped_k(const Pack<A...> *tab, const int *list, int k) {
+  pack_call(Fn, tab[list[blockIdx.y]], k);
+}
+template <auto Fn, int Threads, class... A> GTable<Fn, Threads, A...> gtable_k_of(void (*)(int, A...));
+#define SCS_GTABLE_K(threads, ...) decltype(gtable_k_of<__VA_ARGS__, threads>(__VA_ARGS__))
+template <auto Fn, int Threads, class... A>
+inline void launch_grouped_k(const GTable<Fn, Threads, A...> &t, const int *list, int cnt, int k, hipStream_t s) {
+  if (!t.used || cnt <= 0 || t.gx <= 0) return;
+  hipLaunchKernelGGL((k_grouped_k<Fn, Threads, A...>), dim3((unsigned)t.gx, (unsigned)cnt), dim3(Threads), t.lds, s,
+                     (const Pack<A...> *)t.dev.p, list, k);
+}
+
+static std::atomic<long> g_diff_group_launches{0};  // scs_hip_diff_group_launches(): tests, tools/adjoint_batch_bench.py
+
+constexpr size_t kDiffPsdBorrowMax = (size_t)256 << 20;  // K9-layout scratch borrowed at once by the grouped decomposition (bytes)
+
+struct GroupDiff {
+  std::vector<ScsHipWork *> W;
+  std::vector<DiffCall> calls;
+  std::vector<ScsHipDiffInfo *> infos;
+  bool adjoint = true;
+  int G = 0, n = 0, m = 0;
+  long N = 0;
+  bool has_P = false;
+  hipStream_t s = nullptr;
+
+  // one apply of W (dproj.hpp launch_dproj) over the group
+  struct DprojTabs {
+    SCS_GTABLE(kVecThreads, d_dproj_zl) zl;
+    SCS_GTABLE(kDprojPsdThreads, d_dproj_psd_fused) psd;
+    SCS_GTABLE(kConeThreads, d_dproj_soc_wave) soc;
+    SCS_GTABLE(kConeThreads, d_dproj_soc_block) soc_big;
+    void size(const DprojPlan &p, size_t G) {
+      if (p.z + p.l > 0) { zl.resize(G); zl.gx = vec_blocks(p.z + p.l); }
+      if (p.psd.n_small > 0) { psd.resize(G); psd.gx = ceil_div(p.psd.n_small, kDprojPsdThreads / 64); psd.lds = kDprojPsdFusedLds; }
+      if (p.n_soc > 0) { soc.resize(G); soc.gx = soc_wave_blocks(p.n_soc, p.G); }
+      if (p.n_soc > 0 && p.n_soc_big > 0) { soc_big.resize(G); soc_big.gx = p.n_soc_big; }
+    }
+    void set(int g, const DprojPlan &p, const DprojIo &io, const int *done) {
+      if (zl.used) zl.set(g, io, p.vh, p.z, p.l, done);
+      if (psd.used) psd.set(g, io, p.psd, done);
+      if (soc.used) soc.set(g, io, p.vh, (const double *)p.cinfo, p.off, p.dim, p.n_soc, p.G, done);
+      if (soc_big.used) soc_big.set(g, io, p.vh, (const double *)p.cinfo, p.off, p.dim, p.big, done);
+    }
+  };
+  // one product J q or J' l (diff.hpp prod_J / prod_Jt) over the group
+  struct ProdTabs {
+    DprojTabs dp;
+    SCS_GTABLE(kSpmvThreads, d_spmv_stream<EpiStore>) ar, at, pf;
+    bool transposed = false;  // J': A l first, then the apply
+  };
+
+  SCS_GTABLE(kVecThreads, d_dproj_vhat) t_vhat;
+  SCS_GTABLE(kConeThreads, d_dproj_prep_wave) t_prep_wave;
+  SCS_GTABLE(kConeThreads, d_dproj_prep_block) t_prep_block;
+  SCS_GTABLE(kVecThreads, d_copy_f64) t_psd_copy, t_copy_out0, t_copy_out1, t_gather_st;
+  SCS_GTABLE(kPsdThreads, d_proj_psd<0>) t_psd_eig;
+  SCS_GTABLE(kDprojPsdThreads, d_dproj_psd_gather) t_psd_gather;
+  SCS_GTABLE(kVecThreads, d_adj_in) t_adj_in;
+  SCS_GTABLE(kVecThreads, d_fwd_in) t_fwd_in;
+  SCS_GTABLE(kVecThreads, d_lsqr_start) t_start;
+  SCS_GTABLE_K(kVecThreads, d_lsqr_v) t_lsqr_v;
+  SCS_GTABLE_K(kVecThreads, d_lsqr_u) t_lsqr_u;
+  SCS_GTABLE(kVecThreads, d_adj_out) t_adj_out;
+  SCS_GTABLE(kVecThreads, d_fwd_out) t_fwd_out;
+  SCS_GTABLE(kVecThreads, d_grad_a) t_grad_a;
+  SCS_GTABLE(kVecThreads, d_grad_p) t_grad_p;
+  SCS_GTABLE(kVecThreads, d_copy_i32) t_gather_fl;
+  DprojTabs rhs1, rhs2;  // adjoint: W gs, (W - I) gy;  forward: rhs1 = the final apply
+  ProdTabs pv, pu;       // the product step_v consumes (input uh) and the one step_u consumes (input vh)
+
+  DevBuf<int> flags_d, lists_d;   // G x LF_COUNT;  [identity | active]
+  DevBuf<double> st_d;            // G x L_COUNT
+  int *flags_h = nullptr, *lists_h = nullptr;  // (pinned: every copy here is asynchronous)
+  double *st_h = nullptr;
+  std::vector<DprojPlan> plans;
+  long launches = 0;
+
+  ~GroupDiff() {
+    if (s && hipStreamSynchronize(s) == hipSuccess) {  // the stream is drained: the group's device blocks are the pool's
+      ++t_pool_release;
+      for_tables([](auto &t) { t.dev.release(); });
+      flags_d.release(); lists_d.release(); st_d.release();
+      --t_pool_release;
+    }
+    g_diff_group_launches.fetch_add(launches, std::memory_order_relaxed);
+    if (flags_h) (void)hipHostFree(flags_h);
+    if (lists_h) (void)hipHostFree(lists_h);
+    if (st_h) (void)hipHostFree(st_h);
+  }
+
+  // Can this workspace be differentiated inside a group?  The CSR-stream layouts (every product is one launch whose grid follows from
+  // the row blocks) and PSD blocks on the fused apply; the five-launch tile path stays with diff_impl.
+  static bool member_ok(const ScsHipWork *w) {
+    if (w->At.cs.ok || w->Ar.cs.ok || w->At.has_slab || w->Ar.has_slab) return false;
+    if (w->has_P && (w->Pf.cs.ok || w->Pf.has_slab)) return false;
+    for (int o : w->psd_order_h)
+      if (o > kDprojPsdFusedMax) return false;
+    return true;
+  }
+  // the part of GroupSolve::same_shape the derivative depends on
+  static bool same_shape(const ScsHipWork *a, const ScsHipWork *b) {
+    const HostCone &x = a->cone, &y = b->cone;
+    return a->device == b->device && a->n == b->n && a->m == b->m && a->has_P == b->has_P && a->normalized == b->normalized &&
+           x.z == y.z && x.l == y.l && x.q == y.q && x.s == y.s;
+  }
+
+  template <class F> void for_dproj(DprojTabs &d, F &&f) { f(d.zl); f(d.psd); f(d.soc); f(d.soc_big); }
+  template <class F> void for_tables(F &&f) {
+    f(t_vhat); f(t_prep_wave); f(t_prep_block); f(t_psd_copy); f(t_copy_out0); f(t_copy_out1); f(t_gather_st); f(t_psd_eig);
+    f(t_psd_gather); f(t_adj_in); f(t_fwd_in); f(t_start); f(t_lsqr_v); f(t_lsqr_u); f(t_adj_out); f(t_fwd_out); f(t_grad_a);
+    f(t_grad_p); f(t_gather_fl);
+    for (DprojTabs *d : {&rhs1, &rhs2, &pv.dp, &pu.dp}) for_dproj(*d, f);
+    for (ProdTabs *p : {&pv, &pu}) { f(p->ar); f(p->at); f(p->pf); }
+  }
+  template <class T> void go(const T &t, const int *list, int count) {
+    t.launch(list, count, s);
+    if (t.used && count > 0 && t.gx > 0) ++launches;
+  }
+  template <class T> void go_k(const T &t, const int *list, int count, int k) {
+    launch_grouped_k(t, list, count, k, s);
+    if (t.used && count > 0 && t.gx > 0) ++launches;
+  }
+  void go_dproj(const DprojTabs &d, const int *list, int count) {  // (the order of launch_dproj)
+    go(d.zl, list, count);
+    go(d.psd, list, count);
+    go(d.soc, list, count);
+    go(d.soc_big, list, count);
+  }
+  void go_prod(const ProdTabs &p, const int *list, int count) {  // (the orders of prod_J and prod_Jt)
+    if (!p.transposed) {
+      go_dproj(p.dp, list, count);
+      go(p.ar, list, count);
+      go(p.at, list, count);
+      go(p.pf, list, count);
+    } else {
+      go(p.ar, list, count);
+      go_dproj(p.dp, list, count);
+      go(p.at, list, count);
+      go(p.pf, list, count);
+    }
+  }
+  void sync() {
+    HIP_CHECK(hipGetLastError());  // (launches are not checked one by one)
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  static CsrView csr_of(const DeviceCsr &M) {
+    CsrView V = M.view().csr;
+    V.pstride = V.nblk;
+    return V;
+  }
+
+  // the records of one product for member g: q (or l) is the LSQR vector it reads
+  void set_prod(ProdTabs &p, int g, bool jt, const double *q) {
+    ScsHipWork *w = W[(size_t)g];
+    DiffScratch &d = w->diff;
+    const int *done = d.fl.p + LF_DONE;
+    p.transposed = jt;
+    if (!jt) {
+      p.dp.set(g, plans[(size_t)g], DprojIo{q + n, nullptr, d.dW.p, d.dWmI.p}, done);
+      p.ar.set(g, csr_of(w->Ar), q, EpiStore{d.tA.p, 0}, done, nullptr);
+      p.at.set(g, csr_of(w->At), d.dWmI.p, EpiStore{d.tAt.p, 0}, done, nullptr);
+    } else {
+      p.ar.set(g, csr_of(w->Ar), q, EpiStore{d.tA.p, 0}, done, nullptr);
+      p.dp.set(g, plans[(size_t)g], DprojIo{d.tA.p, q + n, d.dW.p, nullptr}, done);
+      p.at.set(g, csr_of(w->At), q + n, EpiStore{d.tAt.p, 0}, done, nullptr);
+    }
+    if (has_P) p.pf.set(g, csr_of(w->Pf), q, EpiStore{d.tP.p, 0}, done, nullptr);
+  }
+
+  // The caller holds every member's mutex, has selected the device, refused bad arguments and run diff_alloc / diff_build_tri for
+  // every member.  All pointers are device pointers.
+  void run(const ScsHipDiffOpts *o) {
+    const double t0 = now_ms();
+    G = (int)W.size();
+    ScsHipWork *w0 = W[0];
+    n = w0->n; m = w0->m; N = (long)n + m; has_P = w0->has_P;
+    const double tol = o && o->tol > 0. ? o->tol : 1e-8;
+    const long cap = o && o->max_iters > 0 ? (long)o->max_iters : 4 * N;
+    const int nbN = vec_blocks(N);
+    const bool want_dA = adjoint && calls[0].out[2], want_dP = adjoint && calls[0].out[3];
+    ArenaScope no_arena(nullptr);
+
+    HIP_CHECK(hipHostMalloc((void **)&flags_h, sizeof(int) * LF_COUNT * G));
+    HIP_CHECK(hipHostMalloc((void **)&lists_h, sizeof(int) * 2 * G));
+    HIP_CHECK(hipHostMalloc((void **)&st_h, sizeof(double) * L_COUNT * G));
+    flags_d.alloc((size_t)LF_COUNT * G);
+    st_d.alloc((size_t)L_COUNT * G);
+    lists_d.alloc((size_t)2 * G);
+    for (int g = 0; g < G; ++g) lists_h[g] = lists_h[G + g] = g;
+    HIP_CHECK(hipMemcpyAsync(lists_d.p, lists_h, sizeof(int) * 2 * G, hipMemcpyHostToDevice, s));
+    const int *all_d = lists_d.p;
+    int *active_d = lists_d.p + G, *active_h = lists_h + G;
+
+    // ---- the members' cone plans (as diff_impl forms them) ----
+    plans.resize((size_t)G);
+    for (int g = 0; g < G; ++g) {
+      ScsHipWork *w = W[(size_t)g];
+      DiffScratch &d = w->diff;
+      DprojPlan &plan = plans[(size_t)g];
+      plan.z = w->cone.z; plan.l = w->cone.l; plan.n_soc = w->n_soc; plan.n_soc_big = w->n_soc_big; plan.G = w->soc_G;
+      plan.off = w->soc_off.p; plan.dim = w->soc_dim.p; plan.big = w->soc_big.p;
+      plan.vh = d.vhat.p; plan.cinfo = d.cinfo.p; plan.m = m;
+      plan.psd = d.psd.plan;
+      plan.psd.tmp_m = d.dW.p;
+    }
+    const DprojPlan &p0 = plans[0];
+    const size_t SG = (size_t)G;
+
+    // ---- tables ----
+    t_vhat.resize(SG); t_vhat.gx = vec_blocks(m);
+    if (p0.n_soc > 0) { t_prep_wave.resize(SG); t_prep_wave.gx = soc_wave_blocks(p0.n_soc, p0.G); }
+    if (p0.n_soc > 0 && p0.n_soc_big > 0) { t_prep_block.resize(SG); t_prep_block.gx = p0.n_soc_big; }
+    // the decomposition borrows K9-layout scratch for a slice of the members at a time (stream order protects its reuse)
+    const size_t per_member = (size_t)std::max(p0.psd.scratch_doubles, 1L);
+    const int slice = (int)std::max<size_t>(1, std::min<size_t>(SG, kDiffPsdBorrowMax / (per_member * sizeof(double))));
+    DevBuf<double> psd_scratch;
+    if (p0.psd.count > 0) {
+      psd_scratch.alloc(per_member * (size_t)slice);
+      t_psd_copy.resize(SG); t_psd_copy.gx = vec_blocks(m);
+      t_psd_eig.resize(SG); t_psd_eig.gx = p0.psd.count; t_psd_eig.lds = kPsdLdsBytes;
+      t_psd_gather.resize(SG); t_psd_gather.gx = p0.psd.count;
+    }
+    if (adjoint) {
+      t_adj_in.resize(SG); t_adj_in.gx = nbN;
+      rhs1.size(p0, SG); rhs2.size(p0, SG);
+      t_adj_out.resize(SG); t_adj_out.gx = nbN;
+      t_copy_out0.resize(SG); t_copy_out0.gx = vec_blocks(m);
+      t_copy_out1.resize(SG); t_copy_out1.gx = vec_blocks(n);
+      if (want_dA) t_grad_a.resize(SG);
+      if (want_dP) t_grad_p.resize(SG);
+    } else {
+      t_fwd_in.resize(SG); t_fwd_in.gx = nbN;
+      rhs1.size(p0, SG);
+      t_fwd_out.resize(SG); t_fwd_out.gx = nbN;
+    }
+    t_start.resize(SG); t_lsqr_v.resize(SG); t_lsqr_u.resize(SG);
+    t_start.gx = t_lsqr_v.gx = t_lsqr_u.gx = nbN;
+    for (ProdTabs *p : {&pv, &pu}) {
+      p->dp.size(p0, SG);
+      p->ar.resize(SG); p->at.resize(SG);
+      if (has_P) p->pf.resize(SG);
+    }
+    t_gather_fl.resize(SG); t_gather_fl.gx = 1;
+    t_gather_st.resize(SG); t_gather_st.gx = 1;
+
+    int gx_ar = 0, gx_at = 0, gx_pf = 0, gx_ga = 0, gx_gp = 0;
+    const PsdRefineCfg refine_off = psd_refine_default(false);
+    for (int g = 0; g < G; ++g) {
+      ScsHipWork *w = W[(size_t)g];
+      DiffScratch &d = w->diff;
+      const DiffCall &a = calls[(size_t)g];
+      const DprojPlan &plan = plans[(size_t)g];
+      const double *D = w->normalized ? w->D.p : nullptr, *E = w->normalized ? w->E.p : nullptr;
+      const double sigma = w->normalized ? w->scal.sigma : 1.0;
+      gx_ar = std::max(gx_ar, w->Ar.view().csr.nblk);
+      gx_at = std::max(gx_at, w->At.view().csr.nblk);
+      if (has_P) gx_pf = std::max(gx_pf, w->Pf.view().csr.nblk);
+      t_vhat.set(g, (const double *)w->sols.p, (const double *)w->soly.p, D, sigma, m, d.vhat.p);
+      if (t_prep_wave.used) t_prep_wave.set(g, plan.vh, plan.off, plan.dim, plan.n_soc, plan.G, plan.cinfo);
+      if (t_prep_block.used) t_prep_block.set(g, plan.vh, plan.off, plan.dim, plan.big, plan.cinfo);
+      if (t_psd_eig.used) {
+        double *scr = psd_scratch.p + per_member * (size_t)(g % slice);
+        t_psd_copy.set(g, plan.vh, plan.psd.tmp_m, (long)m);
+        t_psd_eig.set(g, plan.psd.tmp_m, PsdBatch{plan.psd.off, plan.psd.order, plan.psd.woff, plan.psd.count}, scr, /*allow_warm=*/0, 0,
+                      (const int *)nullptr, plan.psd.tol2, refine_off, 0);
+        t_psd_gather.set(g, plan.psd, (const double *)scr, plan.vh);
+      }
+      const double *tP = has_P ? d.tP.p : nullptr;
+      if (adjoint) {
+        double *gyh = d.x.p + n, *gsh = d.tA.p;
+        t_adj_in.set(g, a.in[0], a.in[1], a.in[2], D, E, sigma, n, m, d.uh.p, gyh, gsh);
+        rhs1.set(g, plan, DprojIo{gsh, nullptr, d.dW.p, nullptr}, nullptr);
+        rhs2.set(g, plan, DprojIo{gyh, nullptr, nullptr, d.dWmI.p}, nullptr);
+        t_start.set(g, d.uh.p, (const double *)d.dW.p, (const double *)d.dWmI.p, n, N, d.x.p, d.w.p, d.partU.p, d.st.p, d.fl.p);
+        // M = J': step_v consumes M' uh = J uh, step_u consumes M vh = J' vh
+        set_prod(pv, g, /*jt=*/false, d.uh.p);
+        set_prod(pu, g, /*jt=*/true, d.vh.p);
+        t_lsqr_v.set(g, LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 0}, d.vh.p, (const double *)d.w.p, d.x.p, n, N, (const double *)d.partU.p, nbN,
+                     d.partV.p, d.partX.p, d.st.p, d.fl.p);
+        t_lsqr_u.set(g, LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 1}, d.uh.p, (const double *)d.vh.p, d.w.p, n, N, (const double *)d.partV.p,
+                     (const double *)d.partX.p, nbN, d.partU.p, d.st.p, d.fl.p, tol);
+        double *dc = d.tP.p, *db = d.tA.p;  // (free after the loop)
+        t_adj_out.set(g, (const double *)d.x.p, D, E, sigma, n, m, dc, db);
+        t_copy_out0.set(g, (const double *)db, a.out[0], a.out[0] ? (long)m : 0L);
+        t_copy_out1.set(g, (const double *)dc, a.out[1], a.out[1] ? (long)n : 0L);
+        if (want_dA) {
+          t_grad_a.set(g, (const int *)w->At.rowptr.p, (const int *)w->At.col.p, w->At.rows, (long)w->At.nnz, (const double *)w->solx.p,
+                       (const double *)w->soly.p, (const double *)dc, (const double *)db, a.out[2]);
+          gx_ga = std::max(gx_ga, vec_blocks((long)w->At.nnz));
+        }
+        if (want_dP) {
+          t_grad_p.set(g, (const int *)w->Pf.rowptr.p, (const int *)w->Pf.col.p, n, (long)w->Pf.nnz, (const int *)d.tri_up.p,
+                       (const double *)w->solx.p, (const double *)dc, a.out[3]);
+          gx_gp = std::max(gx_gp, vec_blocks((long)w->Pf.nnz));
+        }
+      } else {
+        t_fwd_in.set(g, a.in[0], a.in[1], D, E, sigma, n, m, d.uh.p);
+        t_start.set(g, d.uh.p, (const double *)nullptr, (const double *)nullptr, n, N, d.x.p, d.w.p, d.partU.p, d.st.p, d.fl.p);
+        // M = J: step_v consumes J' uh, step_u consumes J vh
+        set_prod(pv, g, /*jt=*/true, d.uh.p);
+        set_prod(pu, g, /*jt=*/false, d.vh.p);
+        t_lsqr_v.set(g, LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 1}, d.vh.p, (const double *)d.w.p, d.x.p, n, N, (const double *)d.partU.p, nbN,
+                     d.partV.p, d.partX.p, d.st.p, d.fl.p);
+        t_lsqr_u.set(g, LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 0}, d.uh.p, (const double *)d.vh.p, d.w.p, n, N, (const double *)d.partV.p,
+                     (const double *)d.partX.p, nbN, d.partU.p, d.st.p, d.fl.p, tol);
+        rhs1.set(g, plan, DprojIo{d.x.p + n, nullptr, d.dW.p, d.dWmI.p}, nullptr);
+        t_fwd_out.set(g, (const double *)d.x.p, (const double *)d.dW.p, (const double *)d.dWmI.p, D, E, sigma, n, m, a.out[0], a.out[1], a.out[2]);
+      }
+      t_gather_fl.set(g, (const int *)d.fl.p, flags_d.p + (size_t)g * LF_COUNT, (int)LF_COUNT);
+      t_gather_st.set(g, (const double *)d.st.p, st_d.p + (size_t)g * L_COUNT, (long)L_COUNT);
+    }
+    for (ProdTabs *p : {&pv, &pu}) { p->ar.gx = gx_ar; p->at.gx = gx_at; p->pf.gx = gx_pf; }
+    t_grad_a.gx = gx_ga; t_grad_p.gx = gx_gp;
+    for_tables([&](auto &t) { t.upload(s); });
+
+    // ---- the fixed point and the cone records ----
+    go(t_vhat, all_d, G);
+    if (t_psd_eig.used) {
+      for (int lo = 0; lo < G; lo += slice) {
+        const int cnt = std::min(slice, G - lo);
+        go(t_psd_copy, all_d + lo, cnt);
+        go(t_psd_eig, all_d + lo, cnt);
+        go(t_psd_gather, all_d + lo, cnt);
+      }
+      sync();  // one synchronisation for the group: the borrowed scratch is the pool's again
+      ++t_pool_release;
+      psd_scratch.release();
+      --t_pool_release;
+    }
+    go(t_prep_wave, all_d, G);
+    go(t_prep_block, all_d, G);
+
+    // ---- right-hand side into uh, x = w = 0 ----
+    if (adjoint) {
+      go(t_adj_in, all_d, G);
+      go_dproj(rhs1, all_d, G);
+      go_dproj(rhs2, all_d, G);
+    } else {
+      go(t_fwd_in, all_d, G);
+    }
+    go(t_start, all_d, G);
+
+    // ---- LSQR: chunks of iterations between looks at the gathered flags ----
+    int na = G;  // members of the active list
+    auto step_v = [&](int k) { go_prod(pv, active_d, na); go_k(t_lsqr_v, active_d, na, k); };
+    auto step_u = [&](int k) { go_prod(pu, active_d, na); go_k(t_lsqr_u, active_d, na, k); };
+    auto read_flags = [&] {  // every member's flags (a finished member's block no longer changes)
+      go(t_gather_fl, all_d, G);
+      HIP_CHECK(hipMemcpyAsync(flags_h, flags_d.p, sizeof(int) * LF_COUNT * G, hipMemcpyDeviceToHost, s));
+      sync();
+    };
+    auto drop_finished = [&] {  // (after a synchronisation: the pinned list may be rewritten)
+      int keep = 0;
+      for (int i = 0; i < na; ++i)
+        if (!flags_h[(size_t)active_h[i] * LF_COUNT + LF_DONE]) active_h[keep++] = active_h[i];
+      if (keep == na) return;
+      na = keep;
+      if (na > 0) HIP_CHECK(hipMemcpyAsync(active_d, active_h, sizeof(int) * (size_t)na, hipMemcpyHostToDevice, s));
+    };
+    step_v(0);
+    long k = 0;
+    long chunk = 8;
+    while (true) {
+      const long upto = std::min(cap, k + chunk);
+      while (k < upto) {
+        ++k;
+        step_u((int)k);
+        step_v((int)k);
+      }
+      read_flags();
+      drop_finished();
+      if (na == 0 || k >= cap) break;
+      chunk = std::max(4L, std::min(k / 2, 64L));
+    }
+    if (na > 0) {  // the cap: the tests (and the figures of info) for x_cap need alpha_{cap+1}
+      step_u((int)(k + 1));
+      read_flags();
+    }
+    go(t_gather_st, all_d, G);
+    HIP_CHECK(hipMemcpyAsync(st_h, st_d.p, sizeof(double) * L_COUNT * G, hipMemcpyDeviceToHost, s));
+
+    // ---- results ----
+    if (adjoint) {
+      go(t_adj_out, all_d, G);
+      go(t_copy_out0, all_d, G);
+      go(t_copy_out1, all_d, G);
+      go(t_grad_a, all_d, G);
+      go(t_grad_p, all_d, G);
+    } else {
+      go_dproj(rhs1, all_d, G);
+      go(t_fwd_out, all_d, G);
+    }
+    sync();
+    const double dt = now_ms() - t0;
+    for (int g = 0; g < G; ++g) {
+      ScsHipDiffInfo *info = infos[(size_t)g];
+      if (!info) continue;
+      const int *hfl = flags_h + (size_t)g * LF_COUNT;
+      const double *hst = st_h + (size_t)g * L_COUNT;
+      info->iters = (scs_int)std::min((long)hfl[LF_ITERS], cap);
+      info->stop = hfl[LF_STOP] ? hfl[LF_STOP] : 3;
+      info->residual = hst[L_BNORM] > 0. ? hst[L_RNORM] / hst[L_BNORM] : 0.;
+      const double den = hst[L_ANORM] * hst[L_RNORM];
+      info->normal_residual = den > 0. ? hst[L_ARNORM] / den : 0.;
+      info->time_ms = dt;
+    }
+  }
+};
+
+}  // namespace scship

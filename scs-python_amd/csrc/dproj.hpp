@@ -39,15 +39,19 @@ namespace scship {
 enum : int { DP_INSIDE = 0, DP_POLAR = 1, DP_BOUNDARY = 2 };  // cinfo[3 c]: W = I, W = 0, the rank-structured block
 
 // v_hat = sigma (D s - y / D) from the un-normalised solution (D == nullptr: s - y): the fixed point in the solver's coordinates
-__global__ __launch_bounds__(kVecThreads) void k_dproj_vhat(const double *__restrict__ s, const double *__restrict__ y,
-                                                            const double *__restrict__ D, double sigma, int m, double *vh) {
+__device__ __forceinline__ void d_dproj_vhat(const double *__restrict__ s, const double *__restrict__ y,
+                                             const double *__restrict__ D, double sigma, int m, double *vh) {
   for (long i = (long)blockIdx.x * kVecThreads + threadIdx.x; i < m; i += (long)gridDim.x * kVecThreads)
     vh[i] = D ? sigma * (D[i] * s[i] - y[i] / D[i]) : s[i] - y[i];
 }
+__global__ __launch_bounds__(kVecThreads) void k_dproj_vhat(const double *__restrict__ s, const double *__restrict__ y,
+                                                            const double *__restrict__ D, double sigma, int m, double *vh) {
+  d_dproj_vhat(s, y, D, sigma, m, vh);
+}
 
 // ---- preparation: case, t, r of every cone ----
-__global__ __launch_bounds__(kConeThreads) void k_dproj_prep_wave(const double *__restrict__ vh, const int *__restrict__ off,
-                                                                  const int *__restrict__ dim, int ncones, int G, double *cinfo) {
+__device__ __forceinline__ void d_dproj_prep_wave(const double *__restrict__ vh, const int *__restrict__ off,
+                                                  const int *__restrict__ dim, int ncones, int G, double *cinfo) {
   const int lane = threadIdx.x & 63, gl = lane & (G - 1);
   const int wave = (int)blockIdx.x * (kConeThreads / 64) + (threadIdx.x >> 6);
   const int c = wave * (64 / G) + lane / G;
@@ -72,8 +76,12 @@ __global__ __launch_bounds__(kConeThreads) void k_dproj_prep_wave(const double *
   cinfo[3 * c + 1] = t;
   cinfo[3 * c + 2] = r;
 }
-__global__ __launch_bounds__(kConeThreads) void k_dproj_prep_block(const double *__restrict__ vh, const int *__restrict__ off,
-                                                                   const int *__restrict__ dim, const int *__restrict__ big, double *cinfo) {
+__global__ __launch_bounds__(kConeThreads) void k_dproj_prep_wave(const double *__restrict__ vh, const int *__restrict__ off,
+                                                                  const int *__restrict__ dim, int ncones, int G, double *cinfo) {
+  d_dproj_prep_wave(vh, off, dim, ncones, G, cinfo);
+}
+__device__ __forceinline__ void d_dproj_prep_block(const double *__restrict__ vh, const int *__restrict__ off,
+                                                   const int *__restrict__ dim, const int *__restrict__ big, double *cinfo) {
   __shared__ double sm[kConeThreads / 64];
   const int c = big[blockIdx.x];
   const int q = dim[c];
@@ -87,15 +95,22 @@ __global__ __launch_bounds__(kConeThreads) void k_dproj_prep_block(const double 
   cinfo[3 * c + 1] = t;
   cinfo[3 * c + 2] = r;
 }
+__global__ __launch_bounds__(kConeThreads) void k_dproj_prep_block(const double *__restrict__ vh, const int *__restrict__ off,
+                                                                   const int *__restrict__ dim, const int *__restrict__ big, double *cinfo) {
+  d_dproj_prep_block(vh, off, dim, big, cinfo);
+}
 
 // ---- apply (DprojIo above) ----
 // the z zero rows and the l nonnegative rows
-__global__ __launch_bounds__(kVecThreads) void k_dproj_zl(DprojIo io, const double *__restrict__ vh, int z, int l, const int *done) {
+__device__ __forceinline__ void d_dproj_zl(DprojIo io, const double *__restrict__ vh, int z, int l, const int *done) {
   if (done && *done) return;
   for (long i = (long)blockIdx.x * kVecThreads + threadIdx.x; i < (long)z + l; i += (long)gridDim.x * kVecThreads) {
     const double ui = io.u(i);
     io.put(i, (i >= z && vh[i] > 0.) ? ui : 0., ui);
   }
+}
+__global__ __launch_bounds__(kVecThreads) void k_dproj_zl(DprojIo io, const double *__restrict__ vh, int z, int l, const int *done) {
+  d_dproj_zl(io, vh, z, l, done);
 }
 // the coefficients of a boundary block: W u = (top ; cz z + cw w) with u = (u0 ; w), d = z'w
 __device__ __forceinline__ void dproj_coef(double t, double r, double u0, double d, double &top, double &cz, double &cw) {
@@ -104,9 +119,9 @@ __device__ __forceinline__ void dproj_coef(double t, double r, double u0, double
   cz = 0.5 * (u0 - t * dr / r) / r;
   cw = 0.5 * (1. + t / r);
 }
-__global__ __launch_bounds__(kConeThreads) void k_dproj_soc_wave(DprojIo io, const double *__restrict__ vh, const double *__restrict__ cinfo,
-                                                                 const int *__restrict__ off, const int *__restrict__ dim, int ncones, int G,
-                                                                 const int *done) {
+__device__ __forceinline__ void d_dproj_soc_wave(DprojIo io, const double *__restrict__ vh, const double *__restrict__ cinfo,
+                                                 const int *__restrict__ off, const int *__restrict__ dim, int ncones, int G,
+                                                 const int *done) {
   if (done && *done) return;
   const int lane = threadIdx.x & 63, gl = lane & (G - 1);
   const int wave = (int)blockIdx.x * (kConeThreads / 64) + (threadIdx.x >> 6);
@@ -138,9 +153,14 @@ __global__ __launch_bounds__(kConeThreads) void k_dproj_soc_wave(DprojIo io, con
   }
   if (gl == 0) io.put(o0, top, u0);
 }
-__global__ __launch_bounds__(kConeThreads) void k_dproj_soc_block(DprojIo io, const double *__restrict__ vh, const double *__restrict__ cinfo,
-                                                                  const int *__restrict__ off, const int *__restrict__ dim,
-                                                                  const int *__restrict__ big, const int *done) {
+__global__ __launch_bounds__(kConeThreads) void k_dproj_soc_wave(DprojIo io, const double *__restrict__ vh, const double *__restrict__ cinfo,
+                                                                 const int *__restrict__ off, const int *__restrict__ dim, int ncones, int G,
+                                                                 const int *done) {
+  d_dproj_soc_wave(io, vh, cinfo, off, dim, ncones, G, done);
+}
+__device__ __forceinline__ void d_dproj_soc_block(DprojIo io, const double *__restrict__ vh, const double *__restrict__ cinfo,
+                                                  const int *__restrict__ off, const int *__restrict__ dim,
+                                                  const int *__restrict__ big, const int *done) {
   if (done && *done) return;
   __shared__ double sm[kConeThreads / 64];
   __shared__ double bc;
@@ -168,6 +188,11 @@ __global__ __launch_bounds__(kConeThreads) void k_dproj_soc_block(DprojIo io, co
     io.put(o0 + i, cz * vh[o0 + i] + cw * ui, ui);
   }
   if (threadIdx.x == 0) io.put(o0, top, u0);
+}
+__global__ __launch_bounds__(kConeThreads) void k_dproj_soc_block(DprojIo io, const double *__restrict__ vh, const double *__restrict__ cinfo,
+                                                                  const int *__restrict__ off, const int *__restrict__ dim,
+                                                                  const int *__restrict__ big, const int *done) {
+  d_dproj_soc_block(io, vh, cinfo, off, dim, big, done);
 }
 
 // the cone plan the launches below read: the tables of the projections (work.hpp soc_off / soc_dim / soc_big)

@@ -61,8 +61,8 @@ struct DprojPsdPlan {
 };
 
 // V, V' and lam from the K9 scratch of block c into its frames; an order-1 block keeps its entry of v as lam[0]
-__global__ __launch_bounds__(kDprojPsdThreads) void k_dproj_psd_gather(DprojPsdPlan P, const double *__restrict__ scratch,
-                                                                       const double *__restrict__ vh) {
+__device__ __forceinline__ void d_dproj_psd_gather(DprojPsdPlan P, const double *__restrict__ scratch,
+                                                   const double *__restrict__ vh) {
   const int c = blockIdx.x;
   const int n = P.order[c];
   if (n < 1) return;
@@ -81,6 +81,10 @@ __global__ __launch_bounds__(kDprojPsdThreads) void k_dproj_psd_gather(DprojPsdP
     Vt[j + (size_t)NP * i] = v;
   }
   for (int j = threadIdx.x; j < NP; j += kDprojPsdThreads) lam[j] = j < n ? A[j + (size_t)NP * j] : 0.;
+}
+__global__ __launch_bounds__(kDprojPsdThreads) void k_dproj_psd_gather(DprojPsdPlan P, const double *__restrict__ scratch,
+                                                                       const double *__restrict__ vh) {
+  d_dproj_psd_gather(P, scratch, vh);
 }
 
 // ---- tile path ----
@@ -150,7 +154,7 @@ __global__ __launch_bounds__(64) void k_dproj_psd_tile(DprojIo io, DprojPsdPlan 
 // ---- fused path: one wavefront per matrix of order 1 .. kDprojPsdFusedMax ----
 constexpr int kDprojPsdSz = 32 * kPsdSLd;                                                      // one 32 x 33 matrix
 constexpr size_t kDprojPsdFusedLds = (size_t)(kDprojPsdThreads / 64) * 3 * kDprojPsdSz * sizeof(double);  // Q, U, T per wavefront
-__global__ __launch_bounds__(kDprojPsdThreads) void k_dproj_psd_fused(DprojIo io, DprojPsdPlan P, const int *done) {
+__device__ __forceinline__ void d_dproj_psd_fused(DprojIo io, DprojPsdPlan P, const int *done) {
   if (done && *done) return;
   extern __shared__ __attribute__((aligned(16))) double dpsd_lds[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -236,6 +240,9 @@ __global__ __launch_bounds__(kDprojPsdThreads) void k_dproj_psd_fused(DprojIo io
       io.put(at, i == j ? acc[r] : acc[r] * sq2, io.u(at));
     }
   }
+}
+__global__ __launch_bounds__(kDprojPsdThreads) void k_dproj_psd_fused(DprojIo io, DprojPsdPlan P, const int *done) {
+  d_dproj_psd_fused(io, P, done);
 }
 
 // ---- launches ----

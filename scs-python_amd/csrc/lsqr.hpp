@@ -47,8 +47,8 @@ __device__ __forceinline__ double lsqr_bcast(double v, double *slot) {  // tid 0
 __device__ __forceinline__ double lsqr_inv(double a) { return a > 0. ? 1. / a : 0.; }
 
 // start: uh = g (rows >= n: add1 + add2 when given, else what uh holds), x = w = 0, partials of |uh|^2, the state cleared
-__global__ __launch_bounds__(kVecThreads) void k_lsqr_start(double *uh, const double *__restrict__ add1, const double *__restrict__ add2, int n,
-                                                            long N, double *x, double *w, double *partU, double *st, int *fl) {
+__device__ __forceinline__ void d_lsqr_start(double *uh, const double *__restrict__ add1, const double *__restrict__ add2, int n,
+                                             long N, double *x, double *w, double *partU, double *st, int *fl) {
   __shared__ double sm[kVecThreads / 64];
   double s = 0.;
   for (long i = (long)blockIdx.x * kVecThreads + threadIdx.x; i < N; i += (long)gridDim.x * kVecThreads) {
@@ -66,11 +66,15 @@ __global__ __launch_bounds__(kVecThreads) void k_lsqr_start(double *uh, const do
   if (blockIdx.x == 0 && threadIdx.x < L_COUNT) st[threadIdx.x] = 0.;
   if (blockIdx.x == 0 && threadIdx.x < LF_COUNT) fl[threadIdx.x] = 0;
 }
+__global__ __launch_bounds__(kVecThreads) void k_lsqr_start(double *uh, const double *__restrict__ add1, const double *__restrict__ add2, int n,
+                                                            long N, double *x, double *w, double *partU, double *st, int *fl) {
+  d_lsqr_start(uh, add1, add2, n, N, x, w, partU, st, fl);
+}
 
 // k = 0: beta_1 = |uh|, vh = tv / beta_1.   k >= 1: see the header.
-__global__ __launch_bounds__(kVecThreads) void k_lsqr_v(int k, LsqrProd tv, double *vh, const double *__restrict__ w, double *x, int n, long N,
-                                                        const double *__restrict__ partU, int np, double *partV, double *partX, double *st,
-                                                        int *fl) {
+__device__ __forceinline__ void d_lsqr_v(int k, LsqrProd tv, double *vh, const double *__restrict__ w, double *x, int n, long N,
+                                         const double *__restrict__ partU, int np, double *partV, double *partX, double *st,
+                                         int *fl) {
   if (fl[LF_DONE]) return;
   __shared__ double sm[kVecThreads / 64];
   __shared__ double bc;
@@ -119,11 +123,16 @@ __global__ __launch_bounds__(kVecThreads) void k_lsqr_v(int k, LsqrProd tv, doub
     }
   }
 }
+__global__ __launch_bounds__(kVecThreads) void k_lsqr_v(int k, LsqrProd tv, double *vh, const double *__restrict__ w, double *x, int n, long N,
+                                                        const double *__restrict__ partU, int np, double *partV, double *partX, double *st,
+                                                        int *fl) {
+  d_lsqr_v(k, tv, vh, w, x, n, N, partU, np, partV, partX, st, fl);
+}
 
 // k >= 1.  tol: atol = btol.
-__global__ __launch_bounds__(kVecThreads) void k_lsqr_u(int k, LsqrProd tu, double *uh, const double *__restrict__ vh, double *w, int n, long N,
-                                                        const double *__restrict__ partV, const double *__restrict__ partX, int np,
-                                                        double *partU, double *st, int *fl, double tol) {
+__device__ __forceinline__ void d_lsqr_u(int k, LsqrProd tu, double *uh, const double *__restrict__ vh, double *w, int n, long N,
+                                         const double *__restrict__ partV, const double *__restrict__ partX, int np,
+                                         double *partU, double *st, int *fl, double tol) {
   // (workgroup 0 of THIS launch may raise the flag: one lane reads it for its workgroup, so a workgroup leaves or stays as a whole)
   __shared__ int leave;
   if (threadIdx.x == 0) leave = fl[LF_DONE];
@@ -171,6 +180,11 @@ __global__ __launch_bounds__(kVecThreads) void k_lsqr_u(int k, LsqrProd tu, doub
   }
   su = block_sum<kVecThreads>(su, sm);
   if (threadIdx.x == 0) partU[blockIdx.x] = su;
+}
+__global__ __launch_bounds__(kVecThreads) void k_lsqr_u(int k, LsqrProd tu, double *uh, const double *__restrict__ vh, double *w, int n, long N,
+                                                        const double *__restrict__ partV, const double *__restrict__ partX, int np,
+                                                        double *partU, double *st, int *fl, double tol) {
+  d_lsqr_u(k, tu, uh, vh, w, n, N, partV, partX, np, partU, st, fl, tol);
 }
 
 // Scratch of the derivative entry points (diff.hpp): taken from the block pool at a workspace's first call, kept until scs_finish.

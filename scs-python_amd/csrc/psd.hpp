@@ -643,8 +643,8 @@ __device__ __forceinline__ int psd_stop_test(const double *A, int ld, int n, dou
 // MODE 1, `R.on`: rounds before the refinement stage stop on PSD_STOP_GATE, the round behind it (`post`) re-tests a refined matrix with
 // PSD_STOP_RELAXED — the same decisions as k_psd_sweep_mc, bit for bit.
 template <int MODE>
-__global__ __launch_bounds__(kPsdThreads) void k_proj_psd(double *x, PsdBatch B, double *scratch, int allow_warm, int round, const int *stall,
-                                                          const double *tol2, PsdRefineCfg R, int post) {
+__device__ __forceinline__ void d_proj_psd(double *x, PsdBatch B, double *scratch, int allow_warm, int round, const int *stall,
+                                           const double *tol2, PsdRefineCfg R, int post) {
   SCS_STALL_GUARD(stall);
   const double offtol2 = psd_offtol2(tol2);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -1002,6 +1002,11 @@ __global__ __launch_bounds__(kPsdThreads) void k_proj_psd(double *x, PsdBatch B,
   if (tid == 0)
     for (int i = 1; i < 8; ++i) state[i] = prof[i];
 #endif
+}
+template <int MODE>
+__global__ __launch_bounds__(kPsdThreads) void k_proj_psd(double *x, PsdBatch B, double *scratch, int allow_warm, int round, const int *stall,
+                                                          const double *tol2, PsdRefineCfg R, int post) {
+  d_proj_psd<MODE>(x, B, scratch, allow_warm, round, stall, tol2, R, post);
 }
 
 // ---------------------------------------------------------------------------

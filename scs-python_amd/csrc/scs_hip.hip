@@ -49,6 +49,7 @@
 #include "batch.hpp"
 #include "matrix_update.hpp"
 #include "diff.hpp"
+#include "diff_batch.hpp"
 
 // ================================================================ C ABI
 // A consumer compiled without USE_SPECTRAL_CONES hands over a ScsCone that ends at psize: the plain entry points copy that
@@ -548,6 +549,200 @@ scs_int scs_hip_derivative_device(ScsWork *w, const scs_float *db_dev, const scs
 scs_int scs_hip_derivative(ScsWork *w, const scs_float *db, const scs_float *dc, scs_float *dx, scs_float *dy, scs_float *ds,
                            const ScsHipDiffOpts *opts, ScsHipDiffInfo *info) {
   return diff_entry(w, derivative_call(db, dc, dx, dy, ds), opts, info, /*dev=*/false, "scs_hip_derivative");
+}
+
+// ---- grouped derivatives (include/scs_hip.h; csrc/diff_batch.hpp) ----
+// The jobs of a derivative batch: classes of members that can share launches (GroupDiff::member_ok / same_shape, and the same request
+// for dAx / dPx), in the order of their first member; a job of one member goes through diff_impl.
+static std::vector<std::vector<int>> plan_diff_batch(ScsWork *const *works, int count, const std::vector<int> &want) {
+  std::vector<std::vector<int>> jobs;
+  std::vector<char> taken((size_t)count, 0);
+  for (int i = 0; i < count; ++i) {
+    if (taken[(size_t)i]) continue;
+    taken[(size_t)i] = 1;
+    std::vector<int> cls{i};
+    if (GroupDiff::member_ok(works[i]))
+      for (int j = i + 1; j < count && (int)cls.size() < kGroupMax; ++j)
+        if (!taken[(size_t)j] && want[(size_t)j] == want[(size_t)i] && GroupDiff::member_ok(works[j]) && GroupDiff::same_shape(works[i], works[j])) {
+          taken[(size_t)j] = 1;
+          cls.push_back(j);
+        }
+    jobs.push_back(cls);
+  }
+  return jobs;
+}
+static bool diff_batch_members_ok(ScsWork *const *works, scs_int count, const char *who) {
+  if (!works || count <= 0) {
+    set_last_error(std::string(who) + ": count must be positive and w non-NULL");
+    return false;
+  }
+  for (int i = 0; i < count; ++i) {
+    if (!works[i]) { set_last_error(std::string(who) + ": member " + std::to_string(i) + ": null workspace"); return false; }
+    for (int j = 0; j < i; ++j)
+      if (works[j] == works[i]) { set_last_error(std::string(who) + ": member " + std::to_string(i) + ": a workspace appears twice"); return false; }
+  }
+  return true;
+}
+
+int scs_hip_diff_batch_plan(ScsWork **works, scs_int count, int want_dA, int want_dP, scs_int *group_of) {
+  if (!group_of) return -1;
+  set_last_error("");
+  if (!diff_batch_members_ok(works, count, "scs_hip_diff_batch_plan")) return -1;
+  const std::vector<int> want((size_t)count, (want_dA ? 1 : 0) | (want_dP ? 2 : 0));
+  int groups = 0;
+  for (const std::vector<int> &job : plan_diff_batch(works, (int)count, want)) {
+    const int id = job.size() > 1 ? groups++ : -1;
+    for (int i : job) group_of[i] = id;
+  }
+  return groups;
+}
+long scs_hip_diff_group_launches(void) { return g_diff_group_launches.load(); }
+
+// dev: the members' pointers are device pointers; else host pointers, staged around the same path (same bits)
+static scs_int diff_batch_entry(ScsWork **works, std::vector<DiffCall> calls, const ScsHipDiffOpts *o, ScsHipDiffInfo **infos, scs_int count,
+                                bool dev, const char *who) {
+  set_last_error("");
+  if (!diff_batch_members_ok(works, count, who)) return -1;
+  const bool adjoint = calls[0].adjoint;  // (count >= 1: one call per member)
+  static const char *const in_adj[3] = {"gx", "gy", "gs"}, *const in_fwd[3] = {"db", "dc", ""};
+  static const char *const out_adj[4] = {"db", "dc", "dAx", "dPx"}, *const out_fwd[4] = {"dx", "dy", "ds", ""};
+  std::vector<std::unique_lock<std::mutex>> locks;
+  std::vector<hipStream_t> saved;
+  std::vector<int> restored;
+  scs_int rc = 0;
+  try {
+    {  // member mutexes in ADDRESS order (as solve_one_group)
+      std::vector<int> order((size_t)count);
+      std::iota(order.begin(), order.end(), 0);
+      std::sort(order.begin(), order.end(), [&](int a, int b) { return std::less<ScsHipWork *>()(works[a], works[b]); });
+      for (int j : order) locks.emplace_back(works[j]->mtx);
+    }
+    // every refusal of diff_entry, for every member, before any device work
+    std::vector<int> want((size_t)count, 0);
+    for (int i = 0; i < count; ++i) {
+      ScsHipWork *w = works[i];
+      const DiffCall &call = calls[(size_t)i];
+      const std::string mem = std::string(who) + ": member " + std::to_string(i), at = mem + ": ";
+      const std::string why = diff_refusal(w);
+      if (!why.empty()) throw std::runtime_error(at + why);
+      if (w->device != works[0]->device) throw std::runtime_error(at + "the members of a batch live on one device");
+      if (adjoint && call.out[2] && w->At.nnz != w->mats->a_nnz_in)
+        throw std::runtime_error(at + "the resident A' does not hold nnz(A) values: dAx cannot be gathered");
+      if (adjoint && call.out[3]) {
+        if (!w->has_P) throw std::runtime_error(at + "dPx for a workspace created without P");
+        if (!w->mats->p_update_refusal.empty()) throw std::runtime_error(at + w->mats->p_update_refusal);
+      }
+      if (dev) {
+        for (int k = 0; k < 3; ++k)
+          if (call.in[k]) check_device_vector(call.in[k], w->device, mem.c_str(), (std::string(adjoint ? in_adj[k] : in_fwd[k]) + "_dev").c_str());
+        for (int k = 0; k < 4; ++k)
+          if (call.out[k]) check_device_vector(call.out[k], w->device, mem.c_str(), (std::string(adjoint ? out_adj[k] : out_fwd[k]) + "_dev").c_str());
+      }
+      want[(size_t)i] = adjoint ? ((call.out[2] ? 1 : 0) | (call.out[3] ? 2 : 0)) : 0;
+    }
+    HIP_CHECK(hipSetDevice(works[0]->device));
+    hipStream_t s = works[0]->stream;
+    // host twins: stage every member's vectors
+    ArenaScope no_arena(nullptr);
+    std::vector<DevBuf<double>> bin, bout;
+    std::vector<DiffCall> host_calls;
+    auto in_len = [&](const ScsHipWork *w, int k) -> long { return adjoint ? (k == 0 ? w->n : w->m) : (k == 0 ? w->m : k == 1 ? w->n : 0); };
+    auto out_len = [&](const ScsHipWork *w, int k) -> long {
+      if (adjoint) return k == 0 ? w->m : k == 1 ? w->n : k == 2 ? w->mats->a_nnz_in : w->mats->p_nnz_in;
+      return k == 0 ? w->n : k < 3 ? w->m : 0;
+    };
+    if (!dev) {
+      host_calls = calls;
+      bin = std::vector<DevBuf<double>>((size_t)count * 3);
+      bout = std::vector<DevBuf<double>>((size_t)count * 4);
+      for (int i = 0; i < count; ++i) {
+        for (int k = 0; k < 3; ++k)
+          if (host_calls[(size_t)i].in[k]) {
+            bin[(size_t)i * 3 + k].upload(host_calls[(size_t)i].in[k], (size_t)in_len(works[i], k), s);
+            calls[(size_t)i].in[k] = bin[(size_t)i * 3 + k].p;
+          }
+        for (int k = 0; k < 4; ++k)
+          if (host_calls[(size_t)i].out[k]) {
+            bout[(size_t)i * 4 + k].alloc((size_t)std::max(out_len(works[i], k), 1L));
+            calls[(size_t)i].out[k] = bout[(size_t)i * 4 + k].p;
+          }
+      }
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+    for (const std::vector<int> &job : plan_diff_batch(works, (int)count, want)) {
+      if (job.size() == 1) {
+        ScsHipWork *w = works[job[0]];
+        ScsHipWork::ScratchTurn turn(w);
+        diff_impl(w, calls[(size_t)job[0]], o, infos ? infos[job[0]] : nullptr);
+        continue;
+      }
+      GroupDiff gd;
+      gd.adjoint = adjoint;
+      gd.s = s;
+      for (int j : job) {  // every member's kernels go to the group's stream for the duration of the call
+        saved.push_back(works[j]->stream);
+        restored.push_back(j);
+        works[j]->stream = s;
+      }
+      for (int j : job) {
+        diff_alloc(works[j]);
+        if (adjoint && calls[(size_t)j].out[3]) diff_build_tri(works[j]);
+        gd.W.push_back(works[j]);
+        gd.calls.push_back(calls[(size_t)j]);
+        gd.infos.push_back(infos ? infos[j] : nullptr);
+      }
+      gd.run(o);
+      for (size_t k = 0; k < restored.size(); ++k) works[restored[k]]->stream = saved[k];
+      saved.clear();
+      restored.clear();
+    }
+    if (!dev) {
+      for (int i = 0; i < count; ++i)
+        for (int k = 0; k < 4; ++k)
+          if (host_calls[(size_t)i].out[k]) bout[(size_t)i * 4 + k].download(host_calls[(size_t)i].out[k], (size_t)out_len(works[i], k), s);
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    rc = -1;
+  }
+  for (size_t k = 0; k < restored.size(); ++k) works[restored[k]]->stream = saved[k];
+  return rc;
+}
+static const scs_float *at_or_null(const scs_float **a, int i) { return a ? a[i] : nullptr; }
+static scs_float *at_or_null(scs_float **a, int i) { return a ? a[i] : nullptr; }
+static scs_int adjoint_batch_entry(ScsWork **w, const scs_float **gx, const scs_float **gy, const scs_float **gs, scs_float **db, scs_float **dc,
+                                   scs_float **dAx, scs_float **dPx, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count, bool dev,
+                                   const char *who) {
+  std::vector<DiffCall> calls;
+  for (int i = 0; i < count; ++i)
+    calls.push_back(adjoint_call(at_or_null(gx, i), at_or_null(gy, i), at_or_null(gs, i), at_or_null(db, i), at_or_null(dc, i),
+                                 at_or_null(dAx, i), at_or_null(dPx, i)));
+  return diff_batch_entry(w, calls, opts, info, count, dev, who);
+}
+static scs_int derivative_batch_entry(ScsWork **w, const scs_float **db, const scs_float **dc, scs_float **dx, scs_float **dy, scs_float **ds,
+                                      const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count, bool dev, const char *who) {
+  std::vector<DiffCall> calls;
+  for (int i = 0; i < count; ++i)
+    calls.push_back(derivative_call(at_or_null(db, i), at_or_null(dc, i), at_or_null(dx, i), at_or_null(dy, i), at_or_null(ds, i)));
+  return diff_batch_entry(w, calls, opts, info, count, dev, who);
+}
+scs_int scs_hip_adjoint_batch_device(ScsWork **w, const scs_float **gx_dev, const scs_float **gy_dev, const scs_float **gs_dev, scs_float **db_dev,
+                                     scs_float **dc_dev, scs_float **dAx_dev, scs_float **dPx_dev, const ScsHipDiffOpts *opts,
+                                     ScsHipDiffInfo **info, scs_int count) {
+  return adjoint_batch_entry(w, gx_dev, gy_dev, gs_dev, db_dev, dc_dev, dAx_dev, dPx_dev, opts, info, count, /*dev=*/true, "scs_hip_adjoint_batch_device");
+}
+scs_int scs_hip_adjoint_batch(ScsWork **w, const scs_float **gx, const scs_float **gy, const scs_float **gs, scs_float **db, scs_float **dc,
+                              scs_float **dAx, scs_float **dPx, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count) {
+  return adjoint_batch_entry(w, gx, gy, gs, db, dc, dAx, dPx, opts, info, count, /*dev=*/false, "scs_hip_adjoint_batch");
+}
+scs_int scs_hip_derivative_batch_device(ScsWork **w, const scs_float **db_dev, const scs_float **dc_dev, scs_float **dx_dev, scs_float **dy_dev,
+                                        scs_float **ds_dev, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count) {
+  return derivative_batch_entry(w, db_dev, dc_dev, dx_dev, dy_dev, ds_dev, opts, info, count, /*dev=*/true, "scs_hip_derivative_batch_device");
+}
+scs_int scs_hip_derivative_batch(ScsWork **w, const scs_float **db, const scs_float **dc, scs_float **dx, scs_float **dy, scs_float **ds,
+                                 const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count) {
+  return derivative_batch_entry(w, db, dc, dx, dy, ds, opts, info, count, /*dev=*/false, "scs_hip_derivative_batch");
 }
 
 void scs_finish(ScsWork *w) {

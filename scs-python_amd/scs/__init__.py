@@ -287,6 +287,24 @@ class SCS(object):
     return self._solver.derivative_device(db, dc, tol, max_iters)
 
 
+  def adjoint_many(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+    """`adjoint` of the K problems the last `solve_many` solved, differentiated in lock step: dx (K, n), dy (K, m), ds (K, m), None = 0.
+    Returns K dicts like `adjoint()`, with the bits K separate calls would give."""
+    return self._solver.adjoint_many(dx, dy, ds, want, tol, max_iters)
+
+  def adjoint_many_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+    """`adjoint_many` over (K, .) float64 torch tensors on the solver's GPU: {"db": (K, m), "dc": (K, n), ["dA"], ["dP"], "info": [K]}."""
+    return self._solver.adjoint_many_device(dx, dy, ds, want, tol, max_iters)
+
+  def derivative_many(self, db=None, dc=None, tol=1e-8, max_iters=None):
+    """`derivative` of the K problems the last `solve_many` solved, in lock step: db (K, m), dc (K, n), None = 0."""
+    return self._solver.derivative_many(db, dc, tol, max_iters)
+
+  def derivative_many_device(self, db=None, dc=None, tol=1e-8, max_iters=None):
+    """`derivative_many` over (K, .) float64 torch tensors on the solver's GPU."""
+    return self._solver.derivative_many_device(db, dc, tol, max_iters)
+
+
 def solve(data, cone, **settings):
   """Legacy one-shot API; warm-start vectors may ride along in `data`."""
   solver = SCS(data, cone, **settings)
@@ -314,3 +332,45 @@ def batch_plan(solvers):
       raise TypeError("batch_plan needs scs.SCS objects of the HIP backend")
     raw.append(sv._solver)
   return _scs_hip.batch_plan(raw)
+
+
+def _raw_solvers(solvers, who):
+  raw = []
+  for sv in solvers:
+    if not isinstance(sv, SCS) or not isinstance(sv._solver, _scs_hip.SCS):
+      raise TypeError("%s needs scs.SCS objects of the HIP backend" % who)
+    raw.append(sv._solver)
+  return raw
+
+
+def adjoint_batch(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+  """`SCS.adjoint` of several solved `SCS` objects as one batch: equally shaped problems are differentiated in lock step and share
+  every kernel launch.  dx, dy, ds: one vector per solver (a sequence, or a (K, .) array); None, or a None entry, is 0.  Returns one
+  dict per solver, with the bits `.adjoint()` gives."""
+  return _scs_hip.adjoint_batch(_raw_solvers(solvers, "adjoint_batch"), dx, dy, ds, want, tol, max_iters)
+
+
+def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None):
+  """`SCS.derivative` of several solved `SCS` objects as one batch (see `adjoint_batch`)."""
+  return _scs_hip.derivative_batch(_raw_solvers(solvers, "derivative_batch"), db, dc, tol, max_iters)
+
+
+def adjoint_batch_device(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+  """`adjoint_batch` over float64 torch tensors on the solvers' GPU (taken and returned)."""
+  return _scs_hip.adjoint_batch_device(_raw_solvers(solvers, "adjoint_batch_device"), dx, dy, ds, want, tol, max_iters)
+
+
+def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None):
+  """`derivative_batch` over float64 torch tensors on the solvers' GPU."""
+  return _scs_hip.derivative_batch_device(_raw_solvers(solvers, "derivative_batch_device"), db, dc, tol, max_iters)
+
+
+def diff_batch_plan(solvers, want=("b", "c")):
+  """How `adjoint_batch(solvers, want=want)` would split the batch: one int per solver, the index of the group it would share launches
+  with, or -1 where it is differentiated alone (a shape of its own, a pass or slab matrix layout, a PSD block above order 32)."""
+  return _scs_hip.diff_batch_plan(_raw_solvers(solvers, "diff_batch_plan"), want)
+
+
+def diff_group_launches():
+  """Grouped launches the batch derivative entries have issued in this process."""
+  return _scs_hip.diff_group_launches()

@@ -232,6 +232,17 @@ def _load():
         fn = getattr(lib, name)
         fn.restype = c_int
         fn.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.POINTER(_ScsHipDiffOpts), C.POINTER(_ScsHipDiffInfo)]
+    _PV = C.POINTER(C.c_void_p)
+    for fn in (lib.scs_hip_adjoint_batch, lib.scs_hip_adjoint_batch_device):
+        fn.restype = c_int
+        fn.argtypes = [_PV] + [_PV] * 7 + [C.POINTER(_ScsHipDiffOpts), C.POINTER(C.POINTER(_ScsHipDiffInfo)), c_int]
+    for fn in (lib.scs_hip_derivative_batch, lib.scs_hip_derivative_batch_device):
+        fn.restype = c_int
+        fn.argtypes = [_PV] + [_PV] * 5 + [C.POINTER(_ScsHipDiffOpts), C.POINTER(C.POINTER(_ScsHipDiffInfo)), c_int]
+    lib.scs_hip_diff_batch_plan.restype = c_int
+    lib.scs_hip_diff_batch_plan.argtypes = [_PV, c_int, c_int, c_int, C.POINTER(c_int)]
+    lib.scs_hip_diff_group_launches.restype = C.c_long
+    lib.scs_hip_diff_group_launches.argtypes = []
     lib.scs_hip_dproj_cone.restype = c_int
     lib.scs_hip_dproj_cone.argtypes = [_PD, _PD, C.POINTER(_ScsCone), c_int, _PD, _PD]
     lib.scs_hip_work_device.restype = c_int
@@ -995,6 +1006,69 @@ class SCS(object):
         out["info"] = self._diff_call(_lib.scs_hip_derivative_device, ptrs, opts)
         return out
 
+    # ------------------------------------- derivatives of solve_many's members in lock step (adjoint_batch below)
+    def _many_members(self, K):
+        """this solver and the clones solve_many cached on it: the first K of them (None: all)"""
+        if not self._work:
+            raise ValueError("Workspace not initialized!")
+        have = 1 + len(self._many)
+        if K is None:
+            K = have
+        if K > have:
+            raise ValueError("%d rows, but solve_many has solved %d member%s of this solver" % (K, have, "" if have == 1 else "s"))
+        return [self] + self._many[:K - 1]
+
+    def adjoint_many(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+        """`adjoint` of the K members the last `solve_many` solved, in lock step (`adjoint_batch`): dx (K, n), dy (K, m), ds (K, m),
+        None = 0.  Returns the K dicts `adjoint` would return, with the same bits."""
+        K, rows = _many_diff_args((("dx", dx, self.n), ("dy", dy, self.m), ("ds", ds, self.m)), None, want, self._pattern["P"] is not None)
+        members = self._many_members(K)
+        return adjoint_batch(members, rows["dx"], rows["dy"], rows["ds"], want, tol, max_iters)
+
+    def derivative_many(self, db=None, dc=None, tol=1e-8, max_iters=None):
+        """`derivative` of the K members the last `solve_many` solved, in lock step: db (K, m), dc (K, n), None = 0."""
+        K, rows = _many_diff_args((("db", db, self.m), ("dc", dc, self.n)), None)
+        members = self._many_members(K)
+        return derivative_batch(members, rows["db"], rows["dc"], tol, max_iters)
+
+    def adjoint_many_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+        """`adjoint_many` over float64 torch tensors (K, .) on the solver's GPU: one grouped call that writes straight into the rows of
+        {"db": (K, m), "dc": (K, n), ["dA": (K, nnz)], ["dP"], "info": [K dicts]}."""
+        dev = self._device_index()
+        K, rows = _many_diff_args((("dx", dx, self.n), ("dy", dy, self.m), ("ds", ds, self.m)), None, want,
+                                  self._pattern["P"] is not None, device=dev)
+        members = self._many_members(K)
+        K = len(members)
+        want, sizes = self._want_sizes(want)
+        opts = _diff_opts(tol, max_iters)
+        import torch
+        tdev = torch.device("cuda", dev)
+        out = {k: torch.zeros((K, sizes[k]), dtype=torch.float64, device=tdev) for k in want}
+        ins = [[t[i].data_ptr() for i in range(K)] if t is not None else None for t in (rows["dx"], rows["dy"], rows["ds"])]
+        outs = [[out[k][i].data_ptr() for i in range(K)] if k in out and sizes[k] > 0 else None for k in ("b", "c", "A", "P")]
+        _sync_torch_stream(dev)  # the stream contract: inputs complete before the library's own stream reads them
+        infos = _diff_batch_call(_lib.scs_hip_adjoint_batch_device, members, ins + outs, opts)
+        res = {"d" + k: out[k] for k in want}
+        res["info"] = infos
+        return res
+
+    def derivative_many_device(self, db=None, dc=None, tol=1e-8, max_iters=None):
+        """`derivative_many` over float64 torch tensors (K, .) on the solver's GPU: {"dx": (K, n), "dy": (K, m), "ds": (K, m), "info"}."""
+        dev = self._device_index()
+        K, rows = _many_diff_args((("db", db, self.m), ("dc", dc, self.n)), None, device=dev)
+        members = self._many_members(K)
+        K = len(members)
+        opts = _diff_opts(tol, max_iters)
+        import torch
+        tdev = torch.device("cuda", dev)
+        out = {"dx": torch.zeros((K, self.n), dtype=torch.float64, device=tdev), "dy": torch.zeros((K, self.m), dtype=torch.float64, device=tdev),
+               "ds": torch.zeros((K, self.m), dtype=torch.float64, device=tdev)}
+        ins = [[t[i].data_ptr() for i in range(K)] if t is not None else None for t in (rows["db"], rows["dc"])]
+        outs = [[out[k][i].data_ptr() for i in range(K)] for k in ("dx", "dy", "ds")]
+        _sync_torch_stream(dev)
+        out["info"] = _diff_batch_call(_lib.scs_hip_derivative_batch_device, members, ins + outs, opts)
+        return out
+
     # -------------------------------------------------- bench hooks (not part of the reference surface)
     def _set_profiling(self, on):
         with self._lock:
@@ -1288,6 +1362,233 @@ def batch_plan(solvers):
     if rc < 0:
         raise RuntimeError("libscs_hip: " + last_error())
     return [int(v) for v in out]
+
+
+# ---------------------------------------------------------------- derivatives of a batch (include/scs_hip.h: scs_hip_adjoint_batch ...)
+def _many_diff_args(spec, K, want=None, have_P=True, device=None):
+    """Argument checks of the batch derivative entries, before the library is called (pure Python; torch is touched only for device
+    arguments).  spec: (name, value, length) triples; `length` is an int or a list of one int per member.  A value is None (0 for every
+    member), a (K, length) array, or a sequence of K entries, each None or a vector of its member's length.  K: the number of members,
+    or None to take it from the values (None where every value is None).  Host values: numpy arrays of floats, C-contiguous; device
+    values (device = the GPU index): float64 contiguous torch tensors there.  Returns (K, {name: None or a list / 2-D array of K rows})."""
+    if want is not None:
+        _diff_want(want, have_P)
+    rows = {}
+    for name, val, length in spec:
+        rows[name] = None
+        if val is None:
+            continue
+        two_d = not isinstance(val, (list, tuple)) and getattr(val, "ndim", None) == 2
+        if not two_d and not isinstance(val, (list, tuple)):
+            if device is None and not isinstance(val, np.ndarray):
+                raise TypeError("%s must be a 2-D numpy array of floats, one row per problem, or a sequence of vectors" % name)
+            if device is not None and not hasattr(val, "data_ptr"):
+                raise TypeError("%s must be a 2-D torch.Tensor on the solver's GPU, one row per problem, or a sequence of tensors" % name)
+            raise ValueError("%s must be 2-D, one row per problem" % name)
+        cnt = int(val.shape[0]) if two_d else len(val)
+        if K is None:
+            K = cnt
+        if cnt != K:
+            raise ValueError("%s holds %d rows for %d problems" % (name, cnt, K))
+        if K < 1:
+            raise ValueError("a batch needs at least one problem")
+        lens = length if isinstance(length, (list, tuple)) else [length] * K
+        if two_d and device is None:
+            if not isinstance(val, np.ndarray) or not np.issubdtype(val.dtype, np.floating):
+                raise TypeError("%s must be a 2-D numpy array of floats" % name)
+            if not val.flags["C_CONTIGUOUS"]:
+                raise ValueError("%s must be C-contiguous" % name)
+        got = []
+        for i in range(K):
+            v = val[i]
+            if v is None:
+                got.append(None)
+            elif device is not None:
+                _device_vec("%s[%d]" % (name, i), v, lens[i], device)
+                got.append(v)
+            else:
+                if isinstance(v, np.ndarray) and v.ndim == 1 and not v.flags["C_CONTIGUOUS"]:
+                    raise ValueError("%s[%d] must be contiguous" % (name, i))
+                got.append(_diff_vec("%s[%d]" % (name, i), v, lens[i]))
+        rows[name] = got
+    return K, rows
+
+
+def _batch_solvers(solvers, who):
+    solvers = list(solvers)
+    for sv in solvers:
+        if not isinstance(sv, SCS):
+            raise TypeError("%s expects scs._scs_hip.SCS objects" % who)
+    if len(set(id(sv) for sv in solvers)) != len(solvers):
+        raise ValueError("%s: a solver appears twice" % who)
+    return solvers
+
+
+def _ptr_array(K, ptrs):
+    """a C array of K addresses (None entries = NULL), or None for `no such argument`"""
+    if ptrs is None or all(p is None for p in ptrs):
+        return None
+    return (C.c_void_p * K)(*ptrs)
+
+
+def _diff_batch_call(fn, solvers, ptr_lists, opts):
+    """one call of a batch derivative entry under every member's lock (the order of solve_batch); returns the K info dicts"""
+    K = len(solvers)
+    ordered = sorted(solvers, key=id)
+    for sv in ordered:
+        sv._lock.acquire()
+    try:
+        for sv in solvers:
+            if not sv._work:
+                raise ValueError("Workspace not initialized!")
+        works = (C.c_void_p * K)(*[sv._work for sv in solvers])
+        infos = [_ScsHipDiffInfo() for _ in solvers]
+        infp = (C.POINTER(_ScsHipDiffInfo) * K)(*[C.pointer(io) for io in infos])
+        rc = fn(works, *([_ptr_array(K, pl) for pl in ptr_lists] + [C.byref(opts), infp, K]))
+        err = last_error() if rc != 0 else ""
+    finally:
+        for sv in ordered:
+            sv._lock.release()
+    if rc != 0:
+        raise ValueError("libscs_hip: " + err)
+    return [{"iters": int(io.iters), "residual": float(io.residual), "normal_residual": float(io.normal_residual), "stop": int(io.stop),
+             "time_ms": float(io.time_ms)} for io in infos]
+
+
+def _host_ptrs(rows):
+    return [v.ctypes.data if v is not None else None for v in rows] if rows is not None else None
+
+
+def adjoint_batch(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+    """`adjoint` of several solved backend `SCS` objects in one call (include/scs_hip.h: scs_hip_adjoint_batch): equally shaped members
+    share every kernel launch of the LSQR iteration.  dx, dy, ds: sequences (or (K, .) arrays) with one vector per solver; None, or a
+    None entry, counts as 0.  Returns the list of dicts `adjoint` would return for each, with the same bits."""
+    solvers = _batch_solvers(solvers, "adjoint_batch")
+    if not solvers:
+        return []
+    K = len(solvers)
+    have_P = all(sv._pattern["P"] is not None for sv in solvers)
+    _, rows = _many_diff_args((("dx", dx, [sv.n for sv in solvers]), ("dy", dy, [sv.m for sv in solvers]), ("ds", ds, [sv.m for sv in solvers])),
+                              K, want, have_P)
+    opts = _diff_opts(tol, max_iters)
+    outs, want_t = [], None
+    for sv in solvers:
+        want_t, sizes = sv._want_sizes(want)
+        outs.append({k: np.zeros(sizes[k]) for k in want_t})
+    ptrs = [_host_ptrs(rows[k]) for k in ("dx", "dy", "ds")] + [[o[k].ctypes.data for o in outs] if k in want_t else None for k in ("b", "c", "A", "P")]
+    infos = _diff_batch_call(_lib.scs_hip_adjoint_batch, solvers, ptrs, opts)
+    res = []
+    for o, info in zip(outs, infos):
+        r = {"d" + k: o[k] for k in want_t}
+        r["info"] = info
+        res.append(r)
+    return res
+
+
+def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None):
+    """`derivative` of several solved backend `SCS` objects in one call: db, dc as the vectors of `adjoint_batch`.  Returns the list of
+    dicts `derivative` would return for each, with the same bits."""
+    solvers = _batch_solvers(solvers, "derivative_batch")
+    if not solvers:
+        return []
+    K = len(solvers)
+    _, rows = _many_diff_args((("db", db, [sv.m for sv in solvers]), ("dc", dc, [sv.n for sv in solvers])), K)
+    opts = _diff_opts(tol, max_iters)
+    outs = [{"dx": np.zeros(sv.n), "dy": np.zeros(sv.m), "ds": np.zeros(sv.m)} for sv in solvers]
+    ptrs = [_host_ptrs(rows[k]) for k in ("db", "dc")] + [[o[k].ctypes.data for o in outs] for k in ("dx", "dy", "ds")]
+    infos = _diff_batch_call(_lib.scs_hip_derivative_batch, solvers, ptrs, opts)
+    for o, info in zip(outs, infos):
+        o["info"] = info
+    return outs
+
+
+def _batch_device(solvers, who):
+    solvers = _batch_solvers(solvers, who)
+    devs = set(sv._device_index() for sv in solvers)
+    if len(devs) > 1:
+        raise ValueError("%s: the solvers live on different GPUs" % who)
+    return solvers, (devs.pop() if devs else 0)
+
+
+def adjoint_batch_device(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+    """`adjoint_batch` over float64 torch tensors on the solvers' GPU (taken and returned); same bits."""
+    solvers, dev = _batch_device(solvers, "adjoint_batch_device")
+    if not solvers:
+        return []
+    K = len(solvers)
+    have_P = all(sv._pattern["P"] is not None for sv in solvers)
+    _, rows = _many_diff_args((("dx", dx, [sv.n for sv in solvers]), ("dy", dy, [sv.m for sv in solvers]), ("ds", ds, [sv.m for sv in solvers])),
+                              K, want, have_P, device=dev)
+    opts = _diff_opts(tol, max_iters)
+    import torch
+    tdev = torch.device("cuda", dev)
+    outs, want_t, sizes_all = [], None, []
+    for sv in solvers:
+        want_t, sizes = sv._want_sizes(want)
+        sizes_all.append(sizes)
+        outs.append({k: torch.zeros(sizes[k], dtype=torch.float64, device=tdev) for k in want_t})
+    ins = [[t.data_ptr() if t is not None else None for t in rows[k]] if rows[k] is not None else None for k in ("dx", "dy", "ds")]
+    ptrs = ins + [[o[k].data_ptr() if sz[k] > 0 else None for o, sz in zip(outs, sizes_all)] if k in want_t else None for k in ("b", "c", "A", "P")]
+    _sync_torch_stream(dev)
+    infos = _diff_batch_call(_lib.scs_hip_adjoint_batch_device, solvers, ptrs, opts)
+    res = []
+    for o, info in zip(outs, infos):
+        r = {"d" + k: o[k] for k in want_t}
+        r["info"] = info
+        res.append(r)
+    return res
+
+
+def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None):
+    """`derivative_batch` over float64 torch tensors on the solvers' GPU."""
+    solvers, dev = _batch_device(solvers, "derivative_batch_device")
+    if not solvers:
+        return []
+    K = len(solvers)
+    _, rows = _many_diff_args((("db", db, [sv.m for sv in solvers]), ("dc", dc, [sv.n for sv in solvers])), K, device=dev)
+    opts = _diff_opts(tol, max_iters)
+    import torch
+    tdev = torch.device("cuda", dev)
+    outs = [{"dx": torch.zeros(sv.n, dtype=torch.float64, device=tdev), "dy": torch.zeros(sv.m, dtype=torch.float64, device=tdev),
+             "ds": torch.zeros(sv.m, dtype=torch.float64, device=tdev)} for sv in solvers]
+    ins = [[t.data_ptr() if t is not None else None for t in rows[k]] if rows[k] is not None else None for k in ("db", "dc")]
+    ptrs = ins + [[o[k].data_ptr() for o in outs] for k in ("dx", "dy", "ds")]
+    _sync_torch_stream(dev)
+    infos = _diff_batch_call(_lib.scs_hip_derivative_batch_device, solvers, ptrs, opts)
+    for o, info in zip(outs, infos):
+        o["info"] = info
+    return outs
+
+
+def diff_batch_plan(solvers, want=("b", "c")):
+    """The grouping `adjoint_batch(solvers, want=want)` / `derivative_batch(solvers)` would use (include/scs_hip.h:
+    scs_hip_diff_batch_plan): for each solver the index of the group it would share launches with, -1 where it is served alone."""
+    solvers = _batch_solvers(solvers, "diff_batch_plan")
+    if not solvers:
+        return []
+    want = _diff_want(want, True)
+    K = len(solvers)
+    ordered = sorted(solvers, key=id)
+    for sv in ordered:
+        sv._lock.acquire()
+    try:
+        for sv in solvers:
+            if not sv._work:
+                raise ValueError("Workspace not initialized!")
+        works = (C.c_void_p * K)(*[sv._work for sv in solvers])
+        out = (c_int * K)()
+        rc = _lib.scs_hip_diff_batch_plan(works, K, 1 if "A" in want else 0, 1 if "P" in want else 0, out)
+    finally:
+        for sv in ordered:
+            sv._lock.release()
+    if rc < 0:
+        raise RuntimeError("libscs_hip: " + last_error())
+    return [int(v) for v in out]
+
+
+def diff_group_launches():
+    """Grouped launches the batch derivative entries have issued in this process (tests, tools/adjoint_batch_bench.py)."""
+    return int(_lib.scs_hip_diff_group_launches())
 
 
 # ---------------------------------------------------------------- kernel-level entry points (tests, bench)
