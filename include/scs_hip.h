@@ -237,6 +237,30 @@ SCS_HIP_API scs_int scs_hip_derivative_device(ScsWork *w, const scs_float *db_de
                                               scs_float *dy_dev, scs_float *ds_dev, const ScsHipDiffOpts *opts, ScsHipDiffInfo *info);
 SCS_HIP_API scs_int scs_hip_derivative(ScsWork *w, const scs_float *db, const scs_float *dc, scs_float *dx, scs_float *dy, scs_float *ds,
                                        const ScsHipDiffOpts *opts, ScsHipDiffInfo *info);
+/* The forward derivative with perturbations of the matrix VALUES as well (csrc/perturb.hpp): dAx = nnz(A) values in the order of the CSC
+ * arrays scs_init got, dPx = nnz(P) values of the stored upper triangle (an off-diagonal value stands for both of its mirror images, as
+ * in dL/dP: the full perturbation is T + T' - diag(T)); NULL counts as 0.  From F1 = P x + A' y + c, F2 = A x + s - b the system is
+ *     J (dx ; dv) = (-(dc + dP x + dA' y) ; db - dA x)
+ * with x, y the resident solution: three row products on the caller's pattern (values read through the index maps scs_hip_update_matrix
+ * uses; one lane group per row, fixed summation order, no floating-point atomics) form the effective (dc ; db), and the path of
+ * scs_hip_derivative runs unchanged.  scs_hip_derivative[_device] ARE these entries with NULL dAx and dPx: such a call allocates and
+ * launches nothing of this and returns the bits it always did.  The first call that passes dAx or dPx takes n + m doubles of scratch
+ * from the block pool (kept until scs_finish) and, when scs_hip_update_matrix has not built them, the int32 maps of CSR(A) (nnz(A), for
+ * dAx) and of the full CSR(P) (its nnz, for dPx), kept with the matrix set — no layout map is built.  Two calls give the same bits, and
+ * so do the host and device entries.  Clones and both linear solvers are served.
+ * Refusals (as above: -1, the reason in scs_hip_last_error, before any device work, the workspace usable) in addition to those of
+ * scs_hip_derivative: dPx for a workspace created without P, or with a P whose values scs_hip_update_matrix would refuse (entries below
+ * the diagonal, row indices that do not ascend inside a column); (device entries) dAx / dPx that is not memory of the workspace's device. */
+SCS_HIP_API scs_int scs_hip_derivative_full_device(ScsWork *w, const scs_float *db_dev, const scs_float *dc_dev, const scs_float *dAx_dev,
+                                                   const scs_float *dPx_dev, scs_float *dx_dev, scs_float *dy_dev, scs_float *ds_dev,
+                                                   const ScsHipDiffOpts *opts, ScsHipDiffInfo *info);
+SCS_HIP_API scs_int scs_hip_derivative_full(ScsWork *w, const scs_float *db, const scs_float *dc, const scs_float *dAx, const scs_float *dPx,
+                                            scs_float *dx, scs_float *dy, scs_float *ds, const ScsHipDiffOpts *opts, ScsHipDiffInfo *info);
+/* The perturbation products of those entries on their own (tests, parity with a host product): out_c (n) = dP x + dA' y and
+ * out_b (m) = dA x at the resident solution; a NULL input counts as 0, a NULL output is skipped.  Refusals as scs_hip_derivative_full. */
+SCS_HIP_API scs_int scs_hip_data_perturbation_device(ScsWork *w, const scs_float *dAx_dev, const scs_float *dPx_dev, scs_float *out_c_dev,
+                                                     scs_float *out_b_dev);
+SCS_HIP_API scs_int scs_hip_data_perturbation(ScsWork *w, const scs_float *dAx, const scs_float *dPx, scs_float *out_c, scs_float *out_b);
 
 /* The same for a batch of `count` solved workspaces (csrc/diff_batch.hpp).  Members that agree in device, n, m, has-P, normalisation,
  * the z / l / q / s cone structure and in whether dAx / dPx are requested, whose matrices use the CSR-stream layout and whose PSD blocks
@@ -262,6 +286,17 @@ SCS_HIP_API scs_int scs_hip_derivative_batch_device(ScsWork **w, const scs_float
                                                     scs_int count);
 SCS_HIP_API scs_int scs_hip_derivative_batch(ScsWork **w, const scs_float **db, const scs_float **dc, scs_float **dx, scs_float **dy,
                                              scs_float **ds, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count);
+/* scs_hip_derivative_full for a batch: dAx / dPx hold `count` entries like the other arrays (NULL array or NULL entry = no perturbation
+ * of that matrix for that member).  Members are grouped as above, and by whether they pass dAx / dPx (as the adjoint groups by the
+ * request for dAx / dPx); the launch count of a group does not depend on its size.  scs_hip_derivative_batch[_device] are these entries
+ * with NULL dAx and dPx. */
+SCS_HIP_API scs_int scs_hip_derivative_full_batch_device(ScsWork **w, const scs_float **db_dev, const scs_float **dc_dev,
+                                                         const scs_float **dAx_dev, const scs_float **dPx_dev, scs_float **dx_dev,
+                                                         scs_float **dy_dev, scs_float **ds_dev, const ScsHipDiffOpts *opts,
+                                                         ScsHipDiffInfo **info, scs_int count);
+SCS_HIP_API scs_int scs_hip_derivative_full_batch(ScsWork **w, const scs_float **db, const scs_float **dc, const scs_float **dAx,
+                                                  const scs_float **dPx, scs_float **dx, scs_float **dy, scs_float **ds,
+                                                  const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count);
 /* The grouping those entries would use for members that all request (want_dA, want_dP), as scs_hip_batch_plan: group_of[i] = the index
  * of member i's group, -1 = served alone.  Returns the number of groups, -1 on error. */
 SCS_HIP_API int scs_hip_diff_batch_plan(ScsWork **w, scs_int count, int want_dA, int want_dP, scs_int *group_of);

@@ -5,6 +5,7 @@
 // adjoint:   g = (gx ; W gs + (W - I) gy),  J' lambda = g,  dL/dc = -lambda1,  dL/db = lambda2,
 //            dL/dA_ij = -(y_i lambda1_j + lambda2_i x_j),  dL/dP_ij = -(lambda1_i x_j + lambda1_j x_i) (i < j),  dL/dP_ii = -lambda1_i x_i
 // forward:   J (dx ; dv) = (-dc ; db),  ds = W dv,  dy = (W - I) dv
+//            (with perturbations dA, dP of the matrix values: dc + dP x + dA' y and db - dA x in place of dc and db — perturb.hpp)
 // The systems are solved by LSQR (lsqr.hpp) on the RESIDENT, equilibrated matrices A^ = D A E, P^ = E P E at v^ = sigma (D s - y / D):
 // the hatted problem has the same F, and D is constant on every SOC block and on every PSD block (normalize_dev.hpp k_enforce_blocks), so
 // Pi commutes with the scaling there and the derivation carries over to the s cones unchanged (dproj_psd.hpp).
@@ -141,6 +142,8 @@ struct DiffCall {
   bool adjoint = true;
   const double *in[3] = {nullptr, nullptr, nullptr};          // adjoint: gx, gy, gs;  forward: db, dc
   double *out[4] = {nullptr, nullptr, nullptr, nullptr};      // adjoint: db, dc, dAx, dPx;  forward: dx, dy, ds
+  const double *pert[2] = {nullptr, nullptr};                 // forward: dAx, dPx — perturbations of the matrix values (perturb.hpp)
+  bool perturbs() const { return !adjoint && (pert[0] || pert[1]); }
 };
 
 static void diff_alloc(ScsHipWork *w) {
@@ -194,6 +197,7 @@ static void diff_impl(ScsHipWork *w, const DiffCall &a, const ScsHipDiffOpts *o,
   const long cap = o && o->max_iters > 0 ? (long)o->max_iters : 4 * N;
   diff_alloc(w);
   if (a.adjoint && a.out[3]) diff_build_tri(w);
+  if (a.perturbs()) pert_alloc(w, a.pert[0] != nullptr, a.pert[1] != nullptr, "scs_hip_derivative_full");
   DiffScratch &d = w->diff;
   const double *D = w->normalized ? w->D.p : nullptr, *E = w->normalized ? w->E.p : nullptr;
   const double sigma = w->normalized ? w->scal.sigma : 1.0;
@@ -220,7 +224,13 @@ static void diff_impl(ScsHipWork *w, const DiffCall &a, const ScsHipDiffOpts *o,
     hipLaunchKernelGGL(k_lsqr_start, gN, bV, 0, s, d.uh.p, (const double *)d.dW.p, (const double *)d.dWmI.p, n, N, d.x.p, d.w.p, d.partU.p, d.st.p,
                        d.fl.p);
   } else {
-    hipLaunchKernelGGL(k_fwd_in, gN, bV, 0, s, a.in[0], a.in[1], D, E, sigma, n, m, d.uh.p);
+    const double *db = a.in[0], *dc = a.in[1];
+    if (a.perturbs()) {  // (dc_eff ; db_eff) = (dc + dP x + dA' y ; db - dA x) in place of (dc ; db): tAt, tP, tA are free until the products
+      pert_launch(w, a.pert[0], a.pert[1], dc, db, -1.0, d.eff.p, d.eff.p + n, s);
+      dc = d.eff.p;
+      db = d.eff.p + n;
+    }
+    hipLaunchKernelGGL(k_fwd_in, gN, bV, 0, s, db, dc, D, E, sigma, n, m, d.uh.p);
     hipLaunchKernelGGL(k_lsqr_start, gN, bV, 0, s, d.uh.p, (const double *)nullptr, (const double *)nullptr, n, N, d.x.p, d.w.p, d.partU.p, d.st.p,
                        d.fl.p);
   }

@@ -79,6 +79,8 @@ struct GroupDiff {
   SCS_GTABLE(kDprojPsdThreads, d_dproj_psd_gather) t_psd_gather;
   SCS_GTABLE(kVecThreads, d_adj_in) t_adj_in;
   SCS_GTABLE(kVecThreads, d_fwd_in) t_fwd_in;
+  SCS_GTABLE(kPertThreads, d_pert_rows) t_pert[3];  // forward with dA / dP (perturb.hpp): dA' y, dA x, dP x — in the order of pert_products
+  SCS_GTABLE(kVecThreads, d_pert_eff) t_pert_eff;
   SCS_GTABLE(kVecThreads, d_lsqr_start) t_start;
   SCS_GTABLE_K(kVecThreads, d_lsqr_v) t_lsqr_v;
   SCS_GTABLE_K(kVecThreads, d_lsqr_u) t_lsqr_u;
@@ -129,7 +131,7 @@ struct GroupDiff {
   template <class F> void for_dproj(DprojTabs &d, F &&f) { f(d.zl); f(d.psd); f(d.soc); f(d.soc_big); }
   template <class F> void for_tables(F &&f) {
     f(t_vhat); f(t_prep_wave); f(t_prep_block); f(t_psd_copy); f(t_copy_out0); f(t_copy_out1); f(t_gather_st); f(t_psd_eig);
-    f(t_psd_gather); f(t_adj_in); f(t_fwd_in); f(t_start); f(t_lsqr_v); f(t_lsqr_u); f(t_adj_out); f(t_fwd_out); f(t_grad_a);
+    f(t_psd_gather); f(t_adj_in); f(t_fwd_in); f(t_pert[0]); f(t_pert[1]); f(t_pert[2]); f(t_pert_eff); f(t_start); f(t_lsqr_v); f(t_lsqr_u); f(t_adj_out); f(t_fwd_out); f(t_grad_a);
     f(t_grad_p); f(t_gather_fl);
     for (DprojTabs *d : {&rhs1, &rhs2, &pv.dp, &pu.dp}) for_dproj(*d, f);
     for (ProdTabs *p : {&pv, &pu}) { f(p->ar); f(p->at); f(p->pf); }
@@ -252,6 +254,10 @@ struct GroupDiff {
       if (want_dP) t_grad_p.resize(SG);
     } else {
       t_fwd_in.resize(SG); t_fwd_in.gx = nbN;
+      if (calls[0].perturbs()) {  // (the members of a group agree in which of dA / dP they pass: plan_diff_batch)
+        for (int k = 0; k < (calls[0].pert[0] ? 2 : 0) + (calls[0].pert[1] ? 1 : 0); ++k) { t_pert[k].resize(SG); t_pert[k].gx = 0; }
+        t_pert_eff.resize(SG); t_pert_eff.gx = nbN;
+      }
       rhs1.size(p0, SG);
       t_fwd_out.resize(SG); t_fwd_out.gx = nbN;
     }
@@ -316,7 +322,20 @@ struct GroupDiff {
           gx_gp = std::max(gx_gp, vec_blocks((long)w->Pf.nnz));
         }
       } else {
-        t_fwd_in.set(g, a.in[0], a.in[1], D, E, sigma, n, m, d.uh.p);
+        const double *db = a.in[0], *dc = a.in[1];
+        if (a.perturbs()) {  // (as diff_impl: the effective right-hand side in place of the caller's)
+          PertProduct pr[3];
+          const int cnt = pert_products(w, a.pert[0], a.pert[1], pr);
+          for (int k = 0; k < cnt; ++k) {
+            t_pert[k].set(g, pr[k].rp, pr[k].ci, pr[k].map, pr[k].val, pr[k].vec, pr[k].rows, pr[k].lg, pr[k].out);
+            t_pert[k].gx = std::max(t_pert[k].gx, pr[k].blocks());
+          }
+          t_pert_eff.set(g, dc, db, a.pert[1] ? (const double *)d.tP.p : nullptr, a.pert[0] ? (const double *)d.tAt.p : nullptr,
+                         a.pert[0] ? (const double *)d.tA.p : nullptr, -1.0, n, m, d.eff.p, d.eff.p + n);
+          dc = d.eff.p;
+          db = d.eff.p + n;
+        }
+        t_fwd_in.set(g, db, dc, D, E, sigma, n, m, d.uh.p);
         t_start.set(g, d.uh.p, (const double *)nullptr, (const double *)nullptr, n, N, d.x.p, d.w.p, d.partU.p, d.st.p, d.fl.p);
         // M = J: step_v consumes J' uh, step_u consumes J vh
         set_prod(pv, g, /*jt=*/true, d.uh.p);
@@ -358,6 +377,8 @@ struct GroupDiff {
       go_dproj(rhs1, all_d, G);
       go_dproj(rhs2, all_d, G);
     } else {
+      for (auto &t : t_pert) go(t, all_d, G);
+      go(t_pert_eff, all_d, G);
       go(t_fwd_in, all_d, G);
     }
     go(t_start, all_d, G);

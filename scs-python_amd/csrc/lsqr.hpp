@@ -195,6 +195,7 @@ struct DiffScratch {
   DevBuf<double> uh, vh, w, x, tA, dW, dWmI, vhat, tAt, tP, cinfo, partU, partV, partX, st;
   DprojPsdTables psd;
   DevBuf<int> fl, tri_up;  // tri_up: column pointers of the caller's triangle of P (the gather of dL/dP), built at the first request
+  DevBuf<double> eff;      // (dc_eff ; db_eff) of a forward call that perturbs A or P (perturb.hpp): n + m, taken at the first such call
 };
 
 }  // namespace scship

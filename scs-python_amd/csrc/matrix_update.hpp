@@ -176,6 +176,69 @@ struct VmLayout {
   DevBuf<int> *cs_map, *slab_map;
 };
 
+// The value maps of the two CSR forms, in the caller's order: ar (CSR(A) slot -> position in the caller's CSC values) and pf (full
+// CSR(P) slot -> position in the caller's triangle).  Each is built once per matrix set, by whichever comes first: the first
+// scs_hip_update_matrix (both) or the first derivative that perturbs A or P (perturb.hpp: the one it needs).  The caller has selected
+// the device and keeps the arena out of the way.  Throws — with the map released — when a map cannot be derived.
+static void build_csr_value_maps(ScsHipWork *w, bool want_a, bool want_p, const char *who) {
+  MatrixSet &ms = *w->mats;
+  MatrixSet::ValueMaps &vm = ms.vmaps;
+  std::lock_guard<std::mutex> lock(ms.maps_mu);  // (clones share the set)
+  want_a = want_a && !vm.ar.p;
+  want_p = want_p && !vm.pf.p;
+  if (!want_a && !want_p) return;
+  hipStream_t s = w->stream;
+  DevBuf<int> bad;
+  bad.alloc_zero(1, s);
+  auto verdict = [&](const char *what) {
+    int b = 0;
+    HIP_CHECK(hipMemcpyAsync(&b, bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (b) throw std::runtime_error(std::string(who) + ": the value map of " + what + " does not reproduce the resident layout");
+  };
+  DeviceCsr &At = ms.At, &Ar = ms.Ar, &Pf = ms.Pf;
+  if (want_a) {
+    try {
+      if (At.nnz != ms.a_nnz_in || Ar.nnz != At.nnz) throw std::runtime_error(std::string(who) + ": the resident forms of A do not hold nnz(A) values");
+      vm.ar.alloc((size_t)std::max(Ar.nnz, 1L));
+      if (Ar.nnz > 0)
+        hipLaunchKernelGGL(k_map_transpose, dim3(vec_blocks(Ar.nnz)), dim3(kVecThreads), 0, s, (const int *)Ar.rowptr.p, (const int *)Ar.col.p, Ar.rows,
+                           (long)Ar.nnz, (const int *)At.rowptr.p, (const int *)At.col.p, vm.ar.p, bad.p);
+      verdict("A (CSR)");
+    } catch (...) {
+      (void)hipStreamSynchronize(s);
+      vm.ar.release();
+      throw;
+    }
+  }
+  if (want_p) {
+    try {
+      const int n = Pf.rows;
+      DevBuf<int> cnt, up, tmp;
+      cnt.alloc((size_t)n);
+      up.alloc((size_t)n + 1);
+      tmp.alloc_zero((size_t)(n / kScanTile + 4), s);
+      hipLaunchKernelGGL(k_pf_lowcount, dim3(vec_blocks(n)), dim3(kVecThreads), 0, s, (const int *)Pf.rowptr.p, (const int *)Pf.col.p, n, cnt.p);
+      device_exclusive_scan(cnt.p, up.p, n, tmp.p, s);
+      int total = 0;
+      HIP_CHECK(hipMemcpyAsync(&total, up.p + n, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      if ((long)total != ms.p_nnz_in)  // (cannot happen for a P the entry lets through: the host check of scs_init counted the same)
+        throw std::runtime_error(std::string(who) + ": P was given with " + std::to_string(ms.p_nnz_in) + " entries of which " +
+                                 std::to_string(total) + " lie in the upper triangle: its values cannot be updated in place");
+      vm.pf.alloc((size_t)std::max(Pf.nnz, 1L));
+      if (Pf.nnz > 0)
+        hipLaunchKernelGGL(k_map_pf, dim3(vec_blocks(Pf.nnz)), dim3(kVecThreads), 0, s, (const int *)Pf.rowptr.p, (const int *)Pf.col.p, n, (long)Pf.nnz,
+                           (const int *)up.p, vm.pf.p, bad.p);
+      verdict("P (full CSR)");  // (synchronises: cnt / up / tmp are locals)
+    } catch (...) {
+      (void)hipStreamSynchronize(s);
+      vm.pf.release();
+      throw;
+    }
+  }
+}
+
 // The value maps of the set (first call).  Throws — with nothing of the matrices touched — when a map cannot be derived or does not
 // reproduce what the layout holds.
 static void build_value_maps(ScsHipWork *w) {
@@ -192,32 +255,7 @@ static void build_value_maps(ScsHipWork *w) {
   };
   try {
     DeviceCsr &At = ms.At, &Ar = ms.Ar, &Pf = ms.Pf;
-    if (At.nnz != ms.a_nnz_in || Ar.nnz != At.nnz) throw std::runtime_error("scs_hip_update_matrix: the resident forms of A do not hold nnz(A) values");
-    vm.ar.alloc((size_t)std::max(Ar.nnz, 1L));
-    if (Ar.nnz > 0)
-      hipLaunchKernelGGL(k_map_transpose, dim3(vec_blocks(Ar.nnz)), dim3(kVecThreads), 0, s, (const int *)Ar.rowptr.p, (const int *)Ar.col.p, Ar.rows,
-                         (long)Ar.nnz, (const int *)At.rowptr.p, (const int *)At.col.p, vm.ar.p, bad.p);
-    verdict("A (CSR)");
-    if (w->has_P) {
-      const int n = Pf.rows;
-      DevBuf<int> cnt, up, tmp;
-      cnt.alloc((size_t)n);
-      up.alloc((size_t)n + 1);
-      tmp.alloc_zero((size_t)(n / kScanTile + 4), s);
-      hipLaunchKernelGGL(k_pf_lowcount, dim3(vec_blocks(n)), dim3(kVecThreads), 0, s, (const int *)Pf.rowptr.p, (const int *)Pf.col.p, n, cnt.p);
-      device_exclusive_scan(cnt.p, up.p, n, tmp.p, s);
-      int total = 0;
-      HIP_CHECK(hipMemcpyAsync(&total, up.p + n, sizeof(int), hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      if ((long)total != ms.p_nnz_in)  // (cannot happen for a P the entry lets through: the host check of scs_init counted the same)
-        throw std::runtime_error("scs_hip_update_matrix: P was given with " + std::to_string(ms.p_nnz_in) + " entries of which " +
-                                 std::to_string(total) + " lie in the upper triangle: its values cannot be updated in place");
-      vm.pf.alloc((size_t)std::max(Pf.nnz, 1L));
-      if (Pf.nnz > 0)
-        hipLaunchKernelGGL(k_map_pf, dim3(vec_blocks(Pf.nnz)), dim3(kVecThreads), 0, s, (const int *)Pf.rowptr.p, (const int *)Pf.col.p, n, (long)Pf.nnz,
-                           (const int *)up.p, vm.pf.p, bad.p);
-      verdict("P (full CSR)");  // (synchronises: cnt / up / tmp are locals)
-    }
+    build_csr_value_maps(w, true, w->has_P, "scs_hip_update_matrix");  // (a derivative with dA / dP may have built them: kept)
     const VmLayout lay[3] = {{&At, &Ar, &vm.at_cs, &vm.at_slab}, {&Ar, &At, &vm.ar_cs, &vm.ar_slab}, {&Pf, &Pf, &vm.pf_cs, &vm.pf_slab}};
     for (int k = 0; k < (w->has_P ? 3 : 2); ++k) {
       DeviceCsr &M = *lay[k].M;

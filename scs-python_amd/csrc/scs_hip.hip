@@ -48,6 +48,7 @@
 #include "loop.hpp"
 #include "batch.hpp"
 #include "matrix_update.hpp"
+#include "perturb.hpp"
 #include "diff.hpp"
 #include "diff_batch.hpp"
 
@@ -458,6 +459,16 @@ scs_int scs_hip_update_matrix_device(ScsWork *w, const scs_float *Ax_dev, const 
 // ---- derivatives of the last solve (include/scs_hip.h; csrc/diff.hpp) ----
 // every refusal comes before device work and leaves the workspace as it was.  dev: the pointers are device pointers; else host
 // pointers, staged into device buffers around the same path.
+// why the matrix perturbations of a forward call cannot be taken ("" = they can)
+static std::string pert_refusal(const ScsHipWork *w, const DiffCall &call) {
+  if (call.adjoint) return "";
+  if (call.pert[0] && w->At.nnz != w->mats->a_nnz_in) return "the resident A' does not hold nnz(A) values: dAx cannot be applied";
+  if (call.pert[1]) {
+    if (!w->has_P) return "dPx for a workspace created without P";
+    if (!w->mats->p_update_refusal.empty()) return w->mats->p_update_refusal;
+  }
+  return "";
+}
 static scs_int diff_entry(ScsWork *w, DiffCall call, const ScsHipDiffOpts *o, ScsHipDiffInfo *info, bool dev, const char *who) {
   if (!w) {
     set_last_error(std::string(who) + ": null workspace");
@@ -482,7 +493,13 @@ static scs_int diff_entry(ScsWork *w, DiffCall call, const ScsHipDiffOpts *o, Sc
       if (!w->has_P) throw std::runtime_error(std::string(who) + ": dPx for a workspace created without P");
       if (!w->mats->p_update_refusal.empty()) throw std::runtime_error(std::string(who) + ": " + w->mats->p_update_refusal);
     }
+    {
+      const std::string why = pert_refusal(w, call);
+      if (!why.empty()) throw std::runtime_error(std::string(who) + ": " + why);
+    }
     if (dev) {
+      for (int k = 0; k < 2; ++k)
+        if (call.pert[k]) check_device_vector(call.pert[k], w->device, who, k == 0 ? "dAx_dev" : "dPx_dev");
       for (int k = 0; k < 3; ++k)
         if (call.in[k]) check_device_vector(call.in[k], w->device, who, (std::string(call.adjoint ? in_adj[k] : in_fwd[k]) + "_dev").c_str());
       for (int k = 0; k < 4; ++k)
@@ -496,12 +513,17 @@ static scs_int diff_entry(ScsWork *w, DiffCall call, const ScsHipDiffOpts *o, Sc
     }
     // host twin: stage, run the device path, bring the results back
     ArenaScope no_arena(nullptr);
-    DevBuf<double> bin[3], bout[4];
+    DevBuf<double> bin[3], bout[4], bpert[2];
     DiffCall dc = call;
     for (int k = 0; k < 3; ++k)
       if (call.in[k]) {
         bin[k].upload(call.in[k], (size_t)in_len[k], w->stream);
         dc.in[k] = bin[k].p;
+      }
+    for (int k = 0; k < 2; ++k)
+      if (call.pert[k]) {
+        bpert[k].upload(call.pert[k], (size_t)std::max(k == 0 ? w->mats->a_nnz_in : w->mats->p_nnz_in, 1L), w->stream);
+        dc.pert[k] = bpert[k].p;
       }
     for (int k = 0; k < 4; ++k)
       if (call.out[k]) {
@@ -527,10 +549,12 @@ static DiffCall adjoint_call(const scs_float *gx, const scs_float *gy, const scs
   c.out[0] = db; c.out[1] = dc; c.out[2] = dAx; c.out[3] = dPx;
   return c;
 }
-static DiffCall derivative_call(const scs_float *db, const scs_float *dc, scs_float *dx, scs_float *dy, scs_float *ds) {
+static DiffCall derivative_call(const scs_float *db, const scs_float *dc, const scs_float *dAx, const scs_float *dPx, scs_float *dx,
+                                scs_float *dy, scs_float *ds) {
   DiffCall c;
   c.adjoint = false;
   c.in[0] = db; c.in[1] = dc;
+  c.pert[0] = dAx; c.pert[1] = dPx;
   c.out[0] = dx; c.out[1] = dy; c.out[2] = ds;
   return c;
 }
@@ -542,13 +566,82 @@ scs_int scs_hip_adjoint(ScsWork *w, const scs_float *gx, const scs_float *gy, co
                         scs_float *dPx, const ScsHipDiffOpts *opts, ScsHipDiffInfo *info) {
   return diff_entry(w, adjoint_call(gx, gy, gs, db, dc, dAx, dPx), opts, info, /*dev=*/false, "scs_hip_adjoint");
 }
+scs_int scs_hip_derivative_full_device(ScsWork *w, const scs_float *db_dev, const scs_float *dc_dev, const scs_float *dAx_dev,
+                                       const scs_float *dPx_dev, scs_float *dx_dev, scs_float *dy_dev, scs_float *ds_dev,
+                                       const ScsHipDiffOpts *opts, ScsHipDiffInfo *info) {
+  return diff_entry(w, derivative_call(db_dev, dc_dev, dAx_dev, dPx_dev, dx_dev, dy_dev, ds_dev), opts, info, /*dev=*/true,
+                    "scs_hip_derivative_full_device");
+}
+scs_int scs_hip_derivative_full(ScsWork *w, const scs_float *db, const scs_float *dc, const scs_float *dAx, const scs_float *dPx, scs_float *dx,
+                                scs_float *dy, scs_float *ds, const ScsHipDiffOpts *opts, ScsHipDiffInfo *info) {
+  return diff_entry(w, derivative_call(db, dc, dAx, dPx, dx, dy, ds), opts, info, /*dev=*/false, "scs_hip_derivative_full");
+}
+// (one path: the entries without matrix perturbations are the full ones with NULL dAx / dPx, under their own name in a refusal)
 scs_int scs_hip_derivative_device(ScsWork *w, const scs_float *db_dev, const scs_float *dc_dev, scs_float *dx_dev, scs_float *dy_dev,
                                   scs_float *ds_dev, const ScsHipDiffOpts *opts, ScsHipDiffInfo *info) {
-  return diff_entry(w, derivative_call(db_dev, dc_dev, dx_dev, dy_dev, ds_dev), opts, info, /*dev=*/true, "scs_hip_derivative_device");
+  return diff_entry(w, derivative_call(db_dev, dc_dev, nullptr, nullptr, dx_dev, dy_dev, ds_dev), opts, info, /*dev=*/true, "scs_hip_derivative_device");
 }
 scs_int scs_hip_derivative(ScsWork *w, const scs_float *db, const scs_float *dc, scs_float *dx, scs_float *dy, scs_float *ds,
                            const ScsHipDiffOpts *opts, ScsHipDiffInfo *info) {
-  return diff_entry(w, derivative_call(db, dc, dx, dy, ds), opts, info, /*dev=*/false, "scs_hip_derivative");
+  return diff_entry(w, derivative_call(db, dc, nullptr, nullptr, dx, dy, ds), opts, info, /*dev=*/false, "scs_hip_derivative");
+}
+
+// dP x + dA' y (n) and dA x (m) at the resident solution: the perturbation products of the full derivative on their own (perturb.hpp)
+static scs_int data_perturbation_entry(ScsWork *w, const scs_float *dAx, const scs_float *dPx, scs_float *out_c, scs_float *out_b, bool dev,
+                                       const char *who) {
+  if (!w) {
+    set_last_error(std::string(who) + ": null workspace");
+    return -1;
+  }
+  try {
+    set_last_error("");
+    const DiffCall call = derivative_call(nullptr, nullptr, dAx, dPx, nullptr, nullptr, nullptr);
+    std::lock_guard<std::mutex> lock(w->mtx);
+    std::string why = diff_refusal(w);
+    if (why.empty()) why = pert_refusal(w, call);
+    if (!why.empty()) throw std::runtime_error(std::string(who) + ": " + why);
+    if (dev) {
+      if (dAx) check_device_vector(dAx, w->device, who, "dAx_dev");
+      if (dPx) check_device_vector(dPx, w->device, who, "dPx_dev");
+      if (out_c) check_device_vector(out_c, w->device, who, "out_c_dev");
+      if (out_b) check_device_vector(out_b, w->device, who, "out_b_dev");
+    }
+    HIP_CHECK(hipSetDevice(w->device));
+    ScsHipWork::ScratchTurn turn(w);
+    hipStream_t s = w->stream;
+    const size_t n = (size_t)w->n, m = (size_t)w->m;
+    ArenaScope no_arena(nullptr);
+    DevBuf<double> ba, bp, bc, bb;
+    const double *da = dAx, *dp = dPx;
+    double *oc = out_c, *ob = out_b;
+    if (!dev) {
+      if (dAx) { ba.upload(dAx, (size_t)std::max(w->mats->a_nnz_in, 1L), s); da = ba.p; }
+      if (dPx) { bp.upload(dPx, (size_t)std::max(w->mats->p_nnz_in, 1L), s); dp = bp.p; }
+      if (out_c) { bc.alloc(n); oc = bc.p; }
+      if (out_b) { bb.alloc(m); ob = bb.p; }
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+    diff_alloc(w);
+    pert_alloc(w, da != nullptr, dp != nullptr, who);
+    pert_launch(w, da, dp, nullptr, nullptr, 1.0, oc, ob, s);
+    HIP_CHECK(hipGetLastError());
+    if (!dev) {
+      if (out_c) bc.download(out_c, n, s);
+      if (out_b) bb.download(out_b, m, s);
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return -1;
+  }
+}
+scs_int scs_hip_data_perturbation_device(ScsWork *w, const scs_float *dAx_dev, const scs_float *dPx_dev, scs_float *out_c_dev,
+                                         scs_float *out_b_dev) {
+  return data_perturbation_entry(w, dAx_dev, dPx_dev, out_c_dev, out_b_dev, /*dev=*/true, "scs_hip_data_perturbation_device");
+}
+scs_int scs_hip_data_perturbation(ScsWork *w, const scs_float *dAx, const scs_float *dPx, scs_float *out_c, scs_float *out_b) {
+  return data_perturbation_entry(w, dAx, dPx, out_c, out_b, /*dev=*/false, "scs_hip_data_perturbation");
 }
 
 // ---- grouped derivatives (include/scs_hip.h; csrc/diff_batch.hpp) ----
@@ -632,19 +725,25 @@ static scs_int diff_batch_entry(ScsWork **works, std::vector<DiffCall> calls, co
         if (!w->has_P) throw std::runtime_error(at + "dPx for a workspace created without P");
         if (!w->mats->p_update_refusal.empty()) throw std::runtime_error(at + w->mats->p_update_refusal);
       }
+      {
+        const std::string why_pert = pert_refusal(w, call);
+        if (!why_pert.empty()) throw std::runtime_error(at + why_pert);
+      }
       if (dev) {
+        for (int k = 0; k < 2; ++k)
+          if (call.pert[k]) check_device_vector(call.pert[k], w->device, mem.c_str(), k == 0 ? "dAx_dev" : "dPx_dev");
         for (int k = 0; k < 3; ++k)
           if (call.in[k]) check_device_vector(call.in[k], w->device, mem.c_str(), (std::string(adjoint ? in_adj[k] : in_fwd[k]) + "_dev").c_str());
         for (int k = 0; k < 4; ++k)
           if (call.out[k]) check_device_vector(call.out[k], w->device, mem.c_str(), (std::string(adjoint ? out_adj[k] : out_fwd[k]) + "_dev").c_str());
       }
-      want[(size_t)i] = adjoint ? ((call.out[2] ? 1 : 0) | (call.out[3] ? 2 : 0)) : 0;
+      want[(size_t)i] = adjoint ? ((call.out[2] ? 1 : 0) | (call.out[3] ? 2 : 0)) : ((call.pert[0] ? 1 : 0) | (call.pert[1] ? 2 : 0));
     }
     HIP_CHECK(hipSetDevice(works[0]->device));
     hipStream_t s = works[0]->stream;
     // host twins: stage every member's vectors
     ArenaScope no_arena(nullptr);
-    std::vector<DevBuf<double>> bin, bout;
+    std::vector<DevBuf<double>> bin, bout, bpert;
     std::vector<DiffCall> host_calls;
     auto in_len = [&](const ScsHipWork *w, int k) -> long { return adjoint ? (k == 0 ? w->n : w->m) : (k == 0 ? w->m : k == 1 ? w->n : 0); };
     auto out_len = [&](const ScsHipWork *w, int k) -> long {
@@ -655,7 +754,14 @@ static scs_int diff_batch_entry(ScsWork **works, std::vector<DiffCall> calls, co
       host_calls = calls;
       bin = std::vector<DevBuf<double>>((size_t)count * 3);
       bout = std::vector<DevBuf<double>>((size_t)count * 4);
+      bpert = std::vector<DevBuf<double>>((size_t)count * 2);
       for (int i = 0; i < count; ++i) {
+        for (int k = 0; k < 2; ++k)
+          if (host_calls[(size_t)i].pert[k]) {
+            bpert[(size_t)i * 2 + k].upload(host_calls[(size_t)i].pert[k],
+                                            (size_t)std::max(k == 0 ? works[i]->mats->a_nnz_in : works[i]->mats->p_nnz_in, 1L), s);
+            calls[(size_t)i].pert[k] = bpert[(size_t)i * 2 + k].p;
+          }
         for (int k = 0; k < 3; ++k)
           if (host_calls[(size_t)i].in[k]) {
             bin[(size_t)i * 3 + k].upload(host_calls[(size_t)i].in[k], (size_t)in_len(works[i], k), s);
@@ -687,6 +793,7 @@ static scs_int diff_batch_entry(ScsWork **works, std::vector<DiffCall> calls, co
       for (int j : job) {
         diff_alloc(works[j]);
         if (adjoint && calls[(size_t)j].out[3]) diff_build_tri(works[j]);
+        if (calls[(size_t)j].perturbs()) pert_alloc(works[j], calls[(size_t)j].pert[0] != nullptr, calls[(size_t)j].pert[1] != nullptr, who);
         gd.W.push_back(works[j]);
         gd.calls.push_back(calls[(size_t)j]);
         gd.infos.push_back(infos ? infos[j] : nullptr);
@@ -720,11 +827,13 @@ static scs_int adjoint_batch_entry(ScsWork **w, const scs_float **gx, const scs_
                                  at_or_null(dAx, i), at_or_null(dPx, i)));
   return diff_batch_entry(w, calls, opts, info, count, dev, who);
 }
-static scs_int derivative_batch_entry(ScsWork **w, const scs_float **db, const scs_float **dc, scs_float **dx, scs_float **dy, scs_float **ds,
-                                      const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count, bool dev, const char *who) {
+static scs_int derivative_batch_entry(ScsWork **w, const scs_float **db, const scs_float **dc, const scs_float **dAx, const scs_float **dPx,
+                                      scs_float **dx, scs_float **dy, scs_float **ds, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info,
+                                      scs_int count, bool dev, const char *who) {
   std::vector<DiffCall> calls;
   for (int i = 0; i < count; ++i)
-    calls.push_back(derivative_call(at_or_null(db, i), at_or_null(dc, i), at_or_null(dx, i), at_or_null(dy, i), at_or_null(ds, i)));
+    calls.push_back(derivative_call(at_or_null(db, i), at_or_null(dc, i), at_or_null(dAx, i), at_or_null(dPx, i), at_or_null(dx, i),
+                                    at_or_null(dy, i), at_or_null(ds, i)));
   return diff_batch_entry(w, calls, opts, info, count, dev, who);
 }
 scs_int scs_hip_adjoint_batch_device(ScsWork **w, const scs_float **gx_dev, const scs_float **gy_dev, const scs_float **gs_dev, scs_float **db_dev,
@@ -738,11 +847,23 @@ scs_int scs_hip_adjoint_batch(ScsWork **w, const scs_float **gx, const scs_float
 }
 scs_int scs_hip_derivative_batch_device(ScsWork **w, const scs_float **db_dev, const scs_float **dc_dev, scs_float **dx_dev, scs_float **dy_dev,
                                         scs_float **ds_dev, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count) {
-  return derivative_batch_entry(w, db_dev, dc_dev, dx_dev, dy_dev, ds_dev, opts, info, count, /*dev=*/true, "scs_hip_derivative_batch_device");
+  return derivative_batch_entry(w, db_dev, dc_dev, nullptr, nullptr, dx_dev, dy_dev, ds_dev, opts, info, count, /*dev=*/true,
+                                "scs_hip_derivative_batch_device");
+}
+scs_int scs_hip_derivative_full_batch_device(ScsWork **w, const scs_float **db_dev, const scs_float **dc_dev, const scs_float **dAx_dev,
+                                             const scs_float **dPx_dev, scs_float **dx_dev, scs_float **dy_dev, scs_float **ds_dev,
+                                             const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count) {
+  return derivative_batch_entry(w, db_dev, dc_dev, dAx_dev, dPx_dev, dx_dev, dy_dev, ds_dev, opts, info, count, /*dev=*/true,
+                                "scs_hip_derivative_full_batch_device");
+}
+scs_int scs_hip_derivative_full_batch(ScsWork **w, const scs_float **db, const scs_float **dc, const scs_float **dAx, const scs_float **dPx,
+                                      scs_float **dx, scs_float **dy, scs_float **ds, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info,
+                                      scs_int count) {
+  return derivative_batch_entry(w, db, dc, dAx, dPx, dx, dy, ds, opts, info, count, /*dev=*/false, "scs_hip_derivative_full_batch");
 }
 scs_int scs_hip_derivative_batch(ScsWork **w, const scs_float **db, const scs_float **dc, scs_float **dx, scs_float **dy, scs_float **ds,
                                  const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count) {
-  return derivative_batch_entry(w, db, dc, dx, dy, ds, opts, info, count, /*dev=*/false, "scs_hip_derivative_batch");
+  return derivative_batch_entry(w, db, dc, nullptr, nullptr, dx, dy, ds, opts, info, count, /*dev=*/false, "scs_hip_derivative_batch");
 }
 
 void scs_finish(ScsWork *w) {

@@ -45,7 +45,8 @@ struct MatrixSet {
   // what scs_hip_clone rebuilds the state of scs_init from: the data and settings scs_init was called with (scs_update moves b_orig / c_orig)
   std::vector<double> b0, c0, bl0, bu0;
   ScsSettings stgs0{};
-  // scs_hip_update_matrix (matrix_update.hpp): nothing of this exists until the first call.  One int32 source index per stored value
+  // scs_hip_update_matrix (matrix_update.hpp): nothing of this exists until the first call (ar / pf: or until the first derivative that
+  // perturbs A / P, perturb.hpp, which builds the one it needs and no layout map; `built` = ALL maps of the set exist).  One int32 source index per stored value
   // slot of every resident form but A' (whose values ARE the caller's CSC order): -1 marks a padding slot.  ar / pf index the caller's
   // arrays, the layout maps the equilibrated CSR they were built from (cs of A': CSR(A); cs of A: CSR(A'); cs of P and every slab: own CSR).
   struct ValueMaps {
@@ -70,6 +71,7 @@ struct MatrixSet {
   // The column-sorted layouts keep scratch of a product inside the layout (partial row sums of split chunks, piece sums of virtual rows,
   // combine tickets).  Workspaces that share such a set take turns: one solve / update at a time (small problems — CSR-stream — have none).
   std::mutex scratch_mu;
+  std::mutex maps_mu;  // around the one-time build of vmaps.ar / vmaps.pf (matrix_update.hpp build_csr_value_maps: clones may race for it)
   bool has_scratch() const { return At.cs.ok || Ar.cs.ok || Pf.cs.ok; }
 };
 

@@ -278,13 +278,15 @@ class SCS(object):
     """`adjoint` over float64 torch tensors on the solver's GPU (taken and returned); same bits."""
     return self._solver.adjoint_device(dx, dy, ds, want, tol, max_iters)
 
-  def derivative(self, db=None, dc=None, tol=1e-8, max_iters=None):
-    """The change {"dx", "dy", "ds", "info"} of the last solution for a change db, dc of the data (numpy vectors, None = 0)."""
-    return self._solver.derivative(db, dc, tol, max_iters)
+  def derivative(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
+    """The change {"dx", "dy", "ds", "info"} of the last solution for a change db, dc of the data (numpy vectors, None = 0) and dA, dP of
+    the matrices: each a scipy sparse matrix of the constructor's pattern (brought to its form as `update_matrix` does) or a 1-D float
+    array of the stored values in that order; an off-diagonal value of dP stands for both of its mirror images."""
+    return self._solver.derivative(db, dc, tol, max_iters, dA=_update_arg(dA, "dA", False), dP=_update_arg(dP, "dP", True))
 
-  def derivative_device(self, db=None, dc=None, tol=1e-8, max_iters=None):
-    """`derivative` over float64 torch tensors on the solver's GPU."""
-    return self._solver.derivative_device(db, dc, tol, max_iters)
+  def derivative_device(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
+    """`derivative` over float64 torch tensors on the solver's GPU (dA, dP: 1-D tensors of the stored values)."""
+    return self._solver.derivative_device(db, dc, tol, max_iters, dA=dA, dP=dP)
 
 
   def adjoint_many(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
@@ -296,13 +298,14 @@ class SCS(object):
     """`adjoint_many` over (K, .) float64 torch tensors on the solver's GPU: {"db": (K, m), "dc": (K, n), ["dA"], ["dP"], "info": [K]}."""
     return self._solver.adjoint_many_device(dx, dy, ds, want, tol, max_iters)
 
-  def derivative_many(self, db=None, dc=None, tol=1e-8, max_iters=None):
-    """`derivative` of the K problems the last `solve_many` solved, in lock step: db (K, m), dc (K, n), None = 0."""
-    return self._solver.derivative_many(db, dc, tol, max_iters)
+  def derivative_many(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
+    """`derivative` of the K problems the last `solve_many` solved, in lock step: db (K, m), dc (K, n), dA (K, nnz(A)), dP (K, nnz(P)),
+    None = 0."""
+    return self._solver.derivative_many(db, dc, tol, max_iters, dA=dA, dP=dP)
 
-  def derivative_many_device(self, db=None, dc=None, tol=1e-8, max_iters=None):
+  def derivative_many_device(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
     """`derivative_many` over (K, .) float64 torch tensors on the solver's GPU."""
-    return self._solver.derivative_many_device(db, dc, tol, max_iters)
+    return self._solver.derivative_many_device(db, dc, tol, max_iters, dA=dA, dP=dP)
 
 
 def solve(data, cone, **settings):
@@ -350,9 +353,9 @@ def adjoint_batch(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8,
   return _scs_hip.adjoint_batch(_raw_solvers(solvers, "adjoint_batch"), dx, dy, ds, want, tol, max_iters)
 
 
-def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None):
-  """`SCS.derivative` of several solved `SCS` objects as one batch (see `adjoint_batch`)."""
-  return _scs_hip.derivative_batch(_raw_solvers(solvers, "derivative_batch"), db, dc, tol, max_iters)
+def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
+  """`SCS.derivative` of several solved `SCS` objects as one batch (see `adjoint_batch`); dA, dP: one value array per solver."""
+  return _scs_hip.derivative_batch(_raw_solvers(solvers, "derivative_batch"), db, dc, tol, max_iters, dA=dA, dP=dP)
 
 
 def adjoint_batch_device(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
@@ -360,9 +363,9 @@ def adjoint_batch_device(solvers, dx=None, dy=None, ds=None, want=("b", "c"), to
   return _scs_hip.adjoint_batch_device(_raw_solvers(solvers, "adjoint_batch_device"), dx, dy, ds, want, tol, max_iters)
 
 
-def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None):
+def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
   """`derivative_batch` over float64 torch tensors on the solvers' GPU."""
-  return _scs_hip.derivative_batch_device(_raw_solvers(solvers, "derivative_batch_device"), db, dc, tol, max_iters)
+  return _scs_hip.derivative_batch_device(_raw_solvers(solvers, "derivative_batch_device"), db, dc, tol, max_iters, dA=dA, dP=dP)
 
 
 def diff_batch_plan(solvers, want=("b", "c")):

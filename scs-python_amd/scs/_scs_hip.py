@@ -232,7 +232,18 @@ def _load():
         fn = getattr(lib, name)
         fn.restype = c_int
         fn.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.POINTER(_ScsHipDiffOpts), C.POINTER(_ScsHipDiffInfo)]
+    for name in ("scs_hip_derivative_full", "scs_hip_derivative_full_device"):
+        fn = getattr(lib, name)
+        fn.restype = c_int
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 7 + [C.POINTER(_ScsHipDiffOpts), C.POINTER(_ScsHipDiffInfo)]
+    for name in ("scs_hip_data_perturbation", "scs_hip_data_perturbation_device"):
+        fn = getattr(lib, name)
+        fn.restype = c_int
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 4
     _PV = C.POINTER(C.c_void_p)
+    for fn in (lib.scs_hip_derivative_full_batch, lib.scs_hip_derivative_full_batch_device):
+        fn.restype = c_int
+        fn.argtypes = [_PV] + [_PV] * 7 + [C.POINTER(_ScsHipDiffOpts), C.POINTER(C.POINTER(_ScsHipDiffInfo)), c_int]
     for fn in (lib.scs_hip_adjoint_batch, lib.scs_hip_adjoint_batch_device):
         fn.restype = c_int
         fn.argtypes = [_PV] + [_PV] * 7 + [C.POINTER(_ScsHipDiffOpts), C.POINTER(C.POINTER(_ScsHipDiffInfo)), c_int]
@@ -978,33 +989,87 @@ class SCS(object):
         res["info"] = info
         return res
 
-    def derivative(self, db=None, dc=None, tol=1e-8, max_iters=None):
+    def _pert_sizes(self, dA, dP):
+        """nnz(A), nnz(P) of the constructor's pattern; a dP for a solver without P is refused here, before the library is called"""
+        if dP is not None and self._pattern["P"] is None:
+            raise ValueError("dP given, but the solver was created without P")
+        return int(self._pattern["A"][1].shape[0]), int(self._pattern["P"][1].shape[0]) if self._pattern["P"] is not None else 0
+
+    def derivative(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
         """The forward derivative of the last solve: the change {"dx", "dy", "ds", "info"} of the solution for a change db (m), dc (n)
-        of the data (None = 0); LSQR as in `adjoint`."""
+        of the data and dA, dP of the stored VALUES of A and of the upper triangle of P (None = 0); LSQR as in `adjoint`.  dA / dP: a 1-D
+        float array of nnz values in the constructor's CSC order (an off-diagonal value of dP stands for both mirror images, as in
+        `adjoint`'s dP), or a (data, indices, indptr) triple of a canonical CSC matrix of the constructor's pattern (`update_matrix`)."""
         if not self._work:
             raise ValueError("Workspace not initialized!")
         d = [_diff_vec("db", db, self.m), _diff_vec("dc", dc, self.n)]
+        nnz_a, nnz_p = self._pert_sizes(dA, dP)
+        d += [_diff_mat("dA", dA, self._pattern["A"]), _diff_mat("dP", dP, self._pattern["P"])]
         opts = _diff_opts(tol, max_iters)
         out = {"dx": np.zeros(self.n), "dy": np.zeros(self.m), "ds": np.zeros(self.m)}
         ptrs = [_pd(v) if v is not None else None for v in d] + [_pd(out[k]) for k in ("dx", "dy", "ds")]
-        out["info"] = self._diff_call(_lib.scs_hip_derivative, ptrs, opts)
+        if dA is None and dP is None:  # (the same path in the library; a refusal then names the entry it always named)
+            out["info"] = self._diff_call(_lib.scs_hip_derivative, ptrs[:2] + ptrs[4:], opts)
+        else:
+            out["info"] = self._diff_call(_lib.scs_hip_derivative_full, ptrs, opts)
         return out
 
-    def derivative_device(self, db=None, dc=None, tol=1e-8, max_iters=None):
-        """`derivative` over float64 torch tensors on the solver's GPU."""
+    def derivative_device(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
+        """`derivative` over float64 torch tensors on the solver's GPU (dA, dP: 1-D value tensors of nnz(A) / nnz(P) elements)."""
         if not self._work:
             raise ValueError("Workspace not initialized!")
         opts = _diff_opts(tol, max_iters)
+        nnz_a, nnz_p = self._pert_sizes(dA, dP)
         dev = self._device_index()
-        d = [_device_vec(nm, t, ln, dev) if t is not None else None for nm, t, ln in (("db", db, self.m), ("dc", dc, self.n))]
+        d = [_device_vec(nm, t, ln, dev) if t is not None else None
+             for nm, t, ln in (("db", db, self.m), ("dc", dc, self.n), ("dA", dA, nnz_a), ("dP", dP, nnz_p))]
         import torch
         tdev = torch.device("cuda", dev)
         out = {"dx": torch.zeros(self.n, dtype=torch.float64, device=tdev), "dy": torch.zeros(self.m, dtype=torch.float64, device=tdev),
                "ds": torch.zeros(self.m, dtype=torch.float64, device=tdev)}
         _sync_torch_stream(dev)
         ptrs = d + [out[k].data_ptr() for k in ("dx", "dy", "ds")]
-        out["info"] = self._diff_call(_lib.scs_hip_derivative_device, ptrs, opts)
+        if dA is None and dP is None:
+            out["info"] = self._diff_call(_lib.scs_hip_derivative_device, ptrs[:2] + ptrs[4:], opts)
+        else:
+            out["info"] = self._diff_call(_lib.scs_hip_derivative_full_device, ptrs, opts)
         return out
+
+    def data_perturbation(self, dA=None, dP=None):
+        """(dP x + dA' y, dA x) at the resident solution of the last solve: the perturbation products of `derivative(dA=, dP=)` on
+        their own (include/scs_hip.h: scs_hip_data_perturbation; tests)."""
+        if not self._work:
+            raise ValueError("Workspace not initialized!")
+        self._pert_sizes(dA, dP)
+        av, pv = _diff_mat("dA", dA, self._pattern["A"]), _diff_mat("dP", dP, self._pattern["P"])
+        out_c, out_b = np.zeros(self.n), np.zeros(self.m)
+        with self._lock:
+            rc = _lib.scs_hip_data_perturbation(self._work, _pd(av) if av is not None else None, _pd(pv) if pv is not None else None,
+                                                _pd(out_c), _pd(out_b))
+            err = last_error() if rc != 0 else ""
+        if rc != 0:
+            raise ValueError("libscs_hip: " + err)
+        return out_c, out_b
+
+    def data_perturbation_device(self, dA=None, dP=None):
+        """`data_perturbation` over float64 torch tensors on the solver's GPU (taken and returned); same bits."""
+        if not self._work:
+            raise ValueError("Workspace not initialized!")
+        nnz_a, nnz_p = self._pert_sizes(dA, dP)
+        dev = self._device_index()
+        ap = _device_vec("dA", dA, nnz_a, dev) if dA is not None else None
+        pp = _device_vec("dP", dP, nnz_p, dev) if dP is not None else None
+        import torch
+        tdev = torch.device("cuda", dev)
+        out_c = torch.zeros(self.n, dtype=torch.float64, device=tdev)
+        out_b = torch.zeros(self.m, dtype=torch.float64, device=tdev)
+        _sync_torch_stream(dev)
+        with self._lock:
+            rc = _lib.scs_hip_data_perturbation_device(self._work, ap, pp, out_c.data_ptr(), out_b.data_ptr())
+            err = last_error() if rc != 0 else ""
+        if rc != 0:
+            raise ValueError("libscs_hip: " + err)
+        return out_c, out_b
 
     # ------------------------------------- derivatives of solve_many's members in lock step (adjoint_batch below)
     def _many_members(self, K):
@@ -1025,11 +1090,14 @@ class SCS(object):
         members = self._many_members(K)
         return adjoint_batch(members, rows["dx"], rows["dy"], rows["ds"], want, tol, max_iters)
 
-    def derivative_many(self, db=None, dc=None, tol=1e-8, max_iters=None):
-        """`derivative` of the K members the last `solve_many` solved, in lock step: db (K, m), dc (K, n), None = 0."""
-        K, rows = _many_diff_args((("db", db, self.m), ("dc", dc, self.n)), None)
+    def derivative_many(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
+        """`derivative` of the K members the last `solve_many` solved, in lock step: db (K, m), dc (K, n), dA (K, nnz(A)),
+        dP (K, nnz(P)), None = 0."""
+        nnz_a, nnz_p = self._pert_sizes(dA, dP)
+        K, rows = _many_diff_args((("db", db, self.m), ("dc", dc, self.n), ("dA", dA, nnz_a), ("dP", dP, nnz_p)), None,
+                                  have_P=self._pattern["P"] is not None)
         members = self._many_members(K)
-        return derivative_batch(members, rows["db"], rows["dc"], tol, max_iters)
+        return derivative_batch(members, rows["db"], rows["dc"], tol, max_iters, dA=rows["dA"], dP=rows["dP"])
 
     def adjoint_many_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
         """`adjoint_many` over float64 torch tensors (K, .) on the solver's GPU: one grouped call that writes straight into the rows of
@@ -1052,10 +1120,12 @@ class SCS(object):
         res["info"] = infos
         return res
 
-    def derivative_many_device(self, db=None, dc=None, tol=1e-8, max_iters=None):
+    def derivative_many_device(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
         """`derivative_many` over float64 torch tensors (K, .) on the solver's GPU: {"dx": (K, n), "dy": (K, m), "ds": (K, m), "info"}."""
+        nnz_a, nnz_p = self._pert_sizes(dA, dP)
         dev = self._device_index()
-        K, rows = _many_diff_args((("db", db, self.m), ("dc", dc, self.n)), None, device=dev)
+        K, rows = _many_diff_args((("db", db, self.m), ("dc", dc, self.n), ("dA", dA, nnz_a), ("dP", dP, nnz_p)), None,
+                                  have_P=self._pattern["P"] is not None, device=dev)
         members = self._many_members(K)
         K = len(members)
         opts = _diff_opts(tol, max_iters)
@@ -1063,10 +1133,13 @@ class SCS(object):
         tdev = torch.device("cuda", dev)
         out = {"dx": torch.zeros((K, self.n), dtype=torch.float64, device=tdev), "dy": torch.zeros((K, self.m), dtype=torch.float64, device=tdev),
                "ds": torch.zeros((K, self.m), dtype=torch.float64, device=tdev)}
-        ins = [[t[i].data_ptr() for i in range(K)] if t is not None else None for t in (rows["db"], rows["dc"])]
+        ins = [[t[i].data_ptr() for i in range(K)] if t is not None else None for t in (rows["db"], rows["dc"], rows["dA"], rows["dP"])]
         outs = [[out[k][i].data_ptr() for i in range(K)] for k in ("dx", "dy", "ds")]
         _sync_torch_stream(dev)
-        out["info"] = _diff_batch_call(_lib.scs_hip_derivative_batch_device, members, ins + outs, opts)
+        if dA is None and dP is None:
+            out["info"] = _diff_batch_call(_lib.scs_hip_derivative_batch_device, members, ins[:2] + outs, opts)
+        else:
+            out["info"] = _diff_batch_call(_lib.scs_hip_derivative_full_batch_device, members, ins + outs, opts)
         return out
 
     # -------------------------------------------------- bench hooks (not part of the reference surface)
@@ -1173,6 +1246,19 @@ def _diff_vec(name, a, length):
     if a.shape[0] != length:
         raise ValueError("%s has incompatible dimension with A" % name)
     return np.array(a, dtype=np.float64, order="C", copy=True)
+
+
+def _diff_mat(name, M, pattern):
+    """dA / dP of `derivative`, checked before the library is called (no GPU needed): None, a 1-D numpy float array of nnz values
+    (`_diff_vec`), or a (data, indices, indptr) triple of the constructor's pattern (`_matrix_values`); `pattern` = the (indptr, indices)
+    the constructor was given, None for a solver without that matrix.  Returns a fresh contiguous float64 array."""
+    if M is None:
+        return None
+    if pattern is None:
+        raise ValueError("%s given, but the solver was created without %s" % (name, name[1:]))
+    if isinstance(M, tuple):
+        return _matrix_values(name, M, pattern)
+    return _diff_vec(name, M, int(pattern[1].shape[0]))
 
 
 def _diff_want(want, have_P):
@@ -1378,6 +1464,8 @@ def _many_diff_args(spec, K, want=None, have_P=True, device=None):
         rows[name] = None
         if val is None:
             continue
+        if name == "dP" and not have_P:
+            raise ValueError("dP given, but the solver was created without P")
         two_d = not isinstance(val, (list, tuple)) and getattr(val, "ndim", None) == 2
         if not two_d and not isinstance(val, (list, tuple)):
             if device is None and not isinstance(val, np.ndarray):
@@ -1485,18 +1573,31 @@ def adjoint_batch(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8,
     return res
 
 
-def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None):
-    """`derivative` of several solved backend `SCS` objects in one call: db, dc as the vectors of `adjoint_batch`.  Returns the list of
-    dicts `derivative` would return for each, with the same bits."""
+def _batch_pert_spec(solvers, db, dc, dA, dP):
+    """the spec of `_many_diff_args` for a forward batch, and whether every member has a P"""
+    nnz_a = [int(sv._pattern["A"][1].shape[0]) for sv in solvers]
+    nnz_p = [int(sv._pattern["P"][1].shape[0]) if sv._pattern["P"] is not None else 0 for sv in solvers]
+    have_P = all(sv._pattern["P"] is not None for sv in solvers)
+    return (("db", db, [sv.m for sv in solvers]), ("dc", dc, [sv.n for sv in solvers]), ("dA", dA, nnz_a), ("dP", dP, nnz_p)), have_P
+
+
+def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
+    """`derivative` of several solved backend `SCS` objects in one call: db, dc, dA, dP as the vectors of `adjoint_batch` (dA / dP: one
+    value array of nnz(A) / nnz(P) elements per solver).  Returns the list of dicts `derivative` would return for each, with the same
+    bits."""
     solvers = _batch_solvers(solvers, "derivative_batch")
     if not solvers:
         return []
     K = len(solvers)
-    _, rows = _many_diff_args((("db", db, [sv.m for sv in solvers]), ("dc", dc, [sv.n for sv in solvers])), K)
+    spec, have_P = _batch_pert_spec(solvers, db, dc, dA, dP)
+    _, rows = _many_diff_args(spec, K, have_P=have_P)
     opts = _diff_opts(tol, max_iters)
     outs = [{"dx": np.zeros(sv.n), "dy": np.zeros(sv.m), "ds": np.zeros(sv.m)} for sv in solvers]
-    ptrs = [_host_ptrs(rows[k]) for k in ("db", "dc")] + [[o[k].ctypes.data for o in outs] for k in ("dx", "dy", "ds")]
-    infos = _diff_batch_call(_lib.scs_hip_derivative_batch, solvers, ptrs, opts)
+    ptrs = [_host_ptrs(rows[k]) for k in ("db", "dc", "dA", "dP")] + [[o[k].ctypes.data for o in outs] for k in ("dx", "dy", "ds")]
+    if dA is None and dP is None:
+        infos = _diff_batch_call(_lib.scs_hip_derivative_batch, solvers, ptrs[:2] + ptrs[4:], opts)
+    else:
+        infos = _diff_batch_call(_lib.scs_hip_derivative_full_batch, solvers, ptrs, opts)
     for o, info in zip(outs, infos):
         o["info"] = info
     return outs
@@ -1539,22 +1640,26 @@ def adjoint_batch_device(solvers, dx=None, dy=None, ds=None, want=("b", "c"), to
     return res
 
 
-def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None):
+def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
     """`derivative_batch` over float64 torch tensors on the solvers' GPU."""
     solvers, dev = _batch_device(solvers, "derivative_batch_device")
     if not solvers:
         return []
     K = len(solvers)
-    _, rows = _many_diff_args((("db", db, [sv.m for sv in solvers]), ("dc", dc, [sv.n for sv in solvers])), K, device=dev)
+    spec, have_P = _batch_pert_spec(solvers, db, dc, dA, dP)
+    _, rows = _many_diff_args(spec, K, have_P=have_P, device=dev)
     opts = _diff_opts(tol, max_iters)
     import torch
     tdev = torch.device("cuda", dev)
     outs = [{"dx": torch.zeros(sv.n, dtype=torch.float64, device=tdev), "dy": torch.zeros(sv.m, dtype=torch.float64, device=tdev),
              "ds": torch.zeros(sv.m, dtype=torch.float64, device=tdev)} for sv in solvers]
-    ins = [[t.data_ptr() if t is not None else None for t in rows[k]] if rows[k] is not None else None for k in ("db", "dc")]
+    ins = [[t.data_ptr() if t is not None else None for t in rows[k]] if rows[k] is not None else None for k in ("db", "dc", "dA", "dP")]
     ptrs = ins + [[o[k].data_ptr() for o in outs] for k in ("dx", "dy", "ds")]
     _sync_torch_stream(dev)
-    infos = _diff_batch_call(_lib.scs_hip_derivative_batch_device, solvers, ptrs, opts)
+    if dA is None and dP is None:
+        infos = _diff_batch_call(_lib.scs_hip_derivative_batch_device, solvers, ptrs[:2] + ptrs[4:], opts)
+    else:
+        infos = _diff_batch_call(_lib.scs_hip_derivative_full_batch_device, solvers, ptrs, opts)
     for o, info in zip(outs, infos):
         o["info"] = info
     return outs
@@ -1584,6 +1689,14 @@ def diff_batch_plan(solvers, want=("b", "c")):
     if rc < 0:
         raise RuntimeError("libscs_hip: " + last_error())
     return [int(v) for v in out]
+
+
+def data_perturbation(solver, dA=None, dP=None):
+    """(dP x + dA' y, dA x) at the resident solution of a solved backend `SCS` (include/scs_hip.h: scs_hip_data_perturbation): the
+    perturbation products of `derivative(dA=, dP=)` on their own, on host arrays (tests)."""
+    if not isinstance(solver, SCS):
+        raise TypeError("data_perturbation expects a scs._scs_hip.SCS object")
+    return solver.data_perturbation(dA, dP)
 
 
 def diff_group_launches():

@@ -20,16 +20,16 @@ def adjoint_batch(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8,
     return _scs_hip.adjoint_batch(solvers, dx, dy, ds, want, tol, max_iters)
 
 
-def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None):
-    return _scs_hip.derivative_batch(solvers, db, dc, tol, max_iters)
+def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
+    return _scs_hip.derivative_batch(solvers, db, dc, tol, max_iters, dA=dA, dP=dP)
 
 
 def adjoint_batch_device(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
     return _scs_hip.adjoint_batch_device(solvers, dx, dy, ds, want, tol, max_iters)
 
 
-def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None):
-    return _scs_hip.derivative_batch_device(solvers, db, dc, tol, max_iters)
+def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
+    return _scs_hip.derivative_batch_device(solvers, db, dc, tol, max_iters, dA=dA, dP=dP)
 
 
 def diff_batch_plan(solvers, want=("b", "c")):

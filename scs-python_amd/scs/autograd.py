@@ -2,15 +2,25 @@
 import torch.
 
     x, y, s = scs.autograd.solve(solver, b, c)
+    x, y, s = scs.autograd.solve(solver, b, c, A=Ax, P=Px)
 
 `solver` is an `scs.SCS` of the HIP backend; b (m) and c (n) are float64 tensors on its GPU.  Forward is `update_device` +
 `solve_device` (the first call starts cold, later calls warm-start from the solver's previous solution); backward is ONE
 `adjoint_device` call for the gradients of b and c, with the LSQR tolerance `solver.autograd_tol` (default 1e-8).  The info dicts of
 the last forward and backward are left in `solver.autograd_info` / `solver.autograd_adjoint_info`.
 
+A and P, when given, are float64 1-D tensors on the solver's GPU holding the stored VALUES of the matrices in the constructor's
+canonical order (sorted CSC; P: its upper triangle, an off-diagonal value standing for both mirror images) — the learnable parameters
+of a layer usually sit there.  Forward then is `update_matrix_device` with what is given, `update_device(b, c)` and the solve;
+`update_matrix` leaves a cold iterate, so from the second call on the layer passes the previous solution explicitly
+(`solve_device(warm_start=True, x=, y=, s=)`, from the tensors it returned last).  Backward is still ONE `adjoint_device` call whose
+`want` holds exactly the inputs that need a gradient; the gradients of A and P are value tensors in the same order.  A solver whose
+matrix has live clones cannot update it: the ValueError of `update_matrix` comes through.  With A = P = None the layer does what it
+always did, call for call.
+
 The adjoint differentiates the solution that is resident on the device, so backward must run before the same solver is solved or
-updated again (RuntimeError otherwise).  A and P as differentiable inputs and double backward are not covered: call
-`SCS.adjoint_device(want=("b", "c", "A", "P"))` for the matrix gradients.
+updated again (RuntimeError otherwise).  Double backward and torch forward mode (`jvp`) are not covered; for directional derivatives
+call `SCS.derivative_device(db, dc, dA=, dP=)`.
 
     X, Y, S = scs.autograd.solve_many(solver, B, C)
 
@@ -28,6 +38,8 @@ class _Solve(torch.autograd.Function):
     out = solver.solve_device(warm_start=warm)
     solver._autograd_generation = getattr(solver, "_autograd_generation", 0) + 1
     solver.autograd_info = out["info"]
+    # (detached views: the returned tensors get a grad_fn that holds ctx and with it the solver — the solver must not hold them back)
+    solver._autograd_last = (out["x"].detach(), out["y"].detach(), out["s"].detach())
     ctx.solver = solver
     ctx.generation = solver._autograd_generation
     return out["x"], out["y"], out["s"]
@@ -46,9 +58,47 @@ class _Solve(torch.autograd.Function):
     return None, res["db"] if ctx.needs_input_grad[1] else None, res["dc"] if ctx.needs_input_grad[2] else None
 
 
-def solve(solver, b, c):
-  """(x, y, s) of the solver's problem with the data b, c, differentiable with respect to both."""
-  return _Solve.apply(solver, b, c)
+class _SolveMatrix(torch.autograd.Function):
+  """`_Solve` with the values of A and / or P as inputs (None = the solver's own)"""
+
+  @staticmethod
+  def forward(ctx, solver, b, c, A, P):
+    solver.update_matrix_device(A.detach().contiguous() if A is not None else None, P.detach().contiguous() if P is not None else None)
+    solver.update_device(b.detach().contiguous(), c.detach().contiguous())
+    last = getattr(solver, "_autograd_last", None)  # (the new matrix left a cold iterate: the previous solution goes in explicitly)
+    if last is not None:
+      out = solver.solve_device(warm_start=True, x=last[0], y=last[1], s=last[2])
+    else:
+      out = solver.solve_device(warm_start=False)
+    solver._autograd_generation = getattr(solver, "_autograd_generation", 0) + 1
+    solver.autograd_info = out["info"]
+    # (detached views: the returned tensors get a grad_fn that holds ctx and with it the solver — the solver must not hold them back)
+    solver._autograd_last = (out["x"].detach(), out["y"].detach(), out["s"].detach())
+    ctx.solver = solver
+    ctx.generation = solver._autograd_generation
+    return out["x"], out["y"], out["s"]
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable
+  def backward(ctx, gx, gy, gs):
+    solver = ctx.solver
+    if getattr(solver, "_autograd_generation", 0) != ctx.generation:
+      raise RuntimeError("scs.autograd.solve: the solver was solved again before this backward; its resident solution is another one")
+    want = tuple(k for k, need in zip(("b", "c", "A", "P"), ctx.needs_input_grad[1:5]) if need)
+    if not want:
+      return None, None, None, None, None
+    res = solver.adjoint_device(dx=gx.contiguous(), dy=gy.contiguous(), ds=gs.contiguous(), want=want,
+                                tol=getattr(solver, "autograd_tol", 1e-8))
+    solver.autograd_adjoint_info = res["info"]
+    return (None,) + tuple(res.get("d" + k) for k in ("b", "c", "A", "P"))
+
+
+def solve(solver, b, c, A=None, P=None):
+  """(x, y, s) of the solver's problem with the data b, c and — when given — the matrix values A, P (1-D tensors in the constructor's
+  canonical order), differentiable with respect to each tensor passed."""
+  if A is None and P is None:
+    return _Solve.apply(solver, b, c)
+  return _SolveMatrix.apply(solver, b, c, A, P)
 
 
 class _SolveMany(torch.autograd.Function):

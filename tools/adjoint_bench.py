@@ -15,6 +15,15 @@ fixed = t(k1) - k1 ms/LSQR it (preparation + right-hand side + results), and an 
 CG steps and the vector passes, so  W apply <= (ms/LSQR it - 2 ms/CG step) / 2  — an upper estimate that still holds the vector passes.
 
   python tools/adjoint_bench.py [--workloads target_lp_soc,target_qp,config5_member,config5_sdp,config4_psd] [--reps 3] [--out profiles/adjoint.txt]
+
+--matrix is another leg: what the perturbation products of `derivative(db, dc, dA=, dP=)` (csrc/perturb.hpp) cost.  A workload is solved
+as above; derivative_device then runs with a FIXED number of LSQR iterations (tol 1e-300, --lsqr-cap), without and with dA / dP, the two
+interleaved and repeated: the difference of the medians is the cost of the three products and the vector kernel, and it stands next to
+one LSQR iteration of the same run (the time of a call at the cap over the cap).  With --parent-root DIR (a built checkout of the
+parent commit) the call WITHOUT dA / dP is also timed there, in child processes interleaved with child processes of this checkout:
+it must not have become slower, the margin being the parent's own spread (max - min of its child medians) in that run.
+
+  python tools/adjoint_bench.py --matrix [--workloads target_lp_soc,target_qp,config5_member] [--reps 5] [--parent-root DIR] [--out profiles/derivative_matrix.txt]
 """
 import argparse
 import os
@@ -24,9 +33,121 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "scs-python_amd")):
+# (child processes of --matrix: --root DIR imports the package of another checkout)
+IMPORT_ROOT = os.path.abspath(sys.argv[sys.argv.index("--root") + 1]) if "--root" in sys.argv[:-1] else ROOT
+for p in (IMPORT_ROOT, os.path.join(IMPORT_ROOT, "scs-python_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
+
+
+def make_workload(name, pg, proj):
+    if name == "config5_member":
+        K, n, k, seed = pg.workload("config5_small")
+        K = {"l": K["l"], "q": K["q"]}
+    elif name == "config5_sdp":
+        K, n, k, seed = pg.workload("config5_small")
+    else:
+        K, n, k, seed = pg.workload(name)
+    if pg.workload_qp(name):
+        data, _, _ = pg.gen_feasible_qp(K, n, k, seed, proj, b_per_col=pg.workload_qp(name))
+    else:
+        data, _, _ = pg.gen_feasible(K, n, k, seed, proj)
+    return data, K, n
+
+
+def timed(fn, torch):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, r
+
+
+def matrix_child(args):
+    """one process: solve `--child-derivative`, print the median ms of --reps capped derivative_device(db, dc) calls (no dA / dP)"""
+    import torch
+    import scs
+    from scs import _scs_hip
+    import problem_gen as pg
+    data, K, n = make_workload(args.child_derivative, pg, lambda z, K: _scs_hip.proj_cone(z, K, dual=True))
+    m = data["A"].shape[0]
+    sv = scs.SCS(data, K, linear_solver=scs.LinearSolver.HIP_INDIRECT, verbose=False, eps_abs=1e-6, eps_rel=1e-6, max_iters=args.solve_iters)
+    sv.solve_device(warm_start=False)
+    rng = np.random.default_rng(1)
+    db, dc = torch.as_tensor(rng.standard_normal(m)).cuda(), torch.as_tensor(rng.standard_normal(n)).cuda()
+    ts = [timed(lambda: sv.derivative_device(db=db, dc=dc, tol=1e-300, max_iters=args.lsqr_cap), torch)[0] for _ in range(args.reps + 1)][1:]
+    print("CHILD_MS %.6f" % float(np.median(ts)))
+
+
+def matrix_leg(args):
+    import subprocess
+    import torch
+    import scs
+    from scs import _scs_hip
+    import problem_gen as pg
+    if _scs_hip.device_count() < 1:
+        raise SystemExit("adjoint_bench: no HIP device (there is nothing to measure without one)")
+    proj = lambda z, K: _scs_hip.proj_cone(z, K, dual=True)
+    lines = ["adjoint_bench --matrix: SCS.derivative_device after a solve, %d LSQR iterations per call (tol 1e-300), ADMM cap %d, %d interleaved "
+             "repetitions; ms: median [min .. max]" % (args.lsqr_cap, args.solve_iters, args.reps),
+             "%-15s %9s %9s %10s %10s | %-26s %-26s %-26s %-26s | %10s | %10s %10s %10s" % (
+                 "workload", "m", "n", "nnz(A)", "nnz(P)", "(db, dc) ms", "+ dA ms", "+ dP ms", "+ dA, dP ms", "ms/LSQR it", "dA cost", "dP cost",
+                 "both cost")]
+    fmt = lambda v: "%.3f [%.3f .. %.3f]" % (float(np.median(v)), min(v), max(v))
+    for name in args.workloads.split(","):
+        data, K, n = make_workload(name, pg, proj)
+        m = data["A"].shape[0]
+        has_P = data.get("P") is not None
+        sv = scs.SCS(data, K, linear_solver=scs.LinearSolver.HIP_INDIRECT, verbose=False, eps_abs=1e-6, eps_rel=1e-6, max_iters=args.solve_iters)
+        info = sv.solve_device(warm_start=False)["info"]
+        rng = np.random.default_rng(1)
+        db, dc = torch.as_tensor(rng.standard_normal(m)).cuda(), torch.as_tensor(rng.standard_normal(n)).cuda()
+        nnz_a = int(sv._solver._pattern["A"][1].shape[0])
+        nnz_p = int(sv._solver._pattern["P"][1].shape[0]) if has_P else 0
+        dA = torch.as_tensor(rng.standard_normal(nnz_a)).cuda()
+        dP = torch.as_tensor(rng.standard_normal(nnz_p)).cuda() if has_P else None
+        legs = {"plain": {}, "dA": {"dA": dA}}
+        if has_P:
+            legs["dP"] = {"dP": dP}
+            legs["both"] = {"dA": dA, "dP": dP}
+        call = lambda kw: sv.derivative_device(db=db, dc=dc, tol=1e-300, max_iters=args.lsqr_cap, **kw)
+        for kw in legs.values():  # (the first call of each kind allocates: scratch, maps)
+            call(kw)
+        ms = {k: [] for k in legs}
+        iters = 0
+        for _ in range(args.reps):
+            for k, kw in legs.items():
+                t, r = timed(lambda: call(kw), torch)
+                ms[k].append(t)
+                iters = r["info"]["iters"]
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        per_it = med["plain"] / max(iters, 1)
+        cost = lambda k: "%.4f" % (med[k] - med["plain"]) if k in med else "-"
+        lines.append("%-15s %9d %9d %10d %10d | %-26s %-26s %-26s %-26s | %10.4f | %10s %10s %10s" % (
+            name, m, n, nnz_a, nnz_p, fmt(ms["plain"]), fmt(ms["dA"]), fmt(ms["dP"]) if has_P else "-", fmt(ms["both"]) if has_P else "-",
+            per_it, cost("dA"), cost("dP"), cost("both")))
+        lines.append("%-15s   solve: %s, %d ADMM iterations; LSQR iterations per call %d; lin_sys_solver: %s" % (
+            name, info["status"], info["iter"], iters, info["lin_sys_solver"]))
+        del sv, db, dc, dA, dP
+        if args.parent_root:
+            here, there = [], []
+            for _ in range(args.reps):
+                for root, acc in ((args.parent_root, there), (ROOT, here)):
+                    cmd = [sys.executable, os.path.abspath(__file__), "--root", root, "--child-derivative", name, "--reps", str(args.reps),
+                           "--solve-iters", str(args.solve_iters), "--lsqr-cap", str(args.lsqr_cap)]
+                    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+                    if r.returncode != 0:
+                        sys.exit("child at %s failed:\n%s" % (root, r.stderr[-3000:]))
+                    acc.append(float([l for l in r.stdout.splitlines() if l.startswith("CHILD_MS")][-1].split()[1]))
+            spread = max(there) - min(there)
+            verdict = "not slower" if float(np.median(here)) <= float(np.median(there)) + spread else "SLOWER"
+            lines.append("%-15s   derivative(db, dc) in child processes, parent commit / this commit interleaved: parent %s ms, this %s ms; "
+                         "margin = the parent's spread %.3f ms: %s" % (name, fmt(there), fmt(here), spread, verdict))
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
 
 
 def main():
@@ -37,7 +158,15 @@ def main():
     ap.add_argument("--lsqr-cap", type=int, default=400)
     ap.add_argument("--tol", type=float, default=1e-8)
     ap.add_argument("--out", default=None, help="also write the table to this file")
+    ap.add_argument("--matrix", action="store_true", help="the leg that times derivative_device with and without dA / dP")
+    ap.add_argument("--parent-root", default=None, help="--matrix: a built checkout of the parent commit for the comparison of derivative(db, dc)")
+    ap.add_argument("--child-derivative", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--root", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.child_derivative:
+        return matrix_child(args)
+    if args.matrix:
+        return matrix_leg(args)
 
     import torch
     import scs
