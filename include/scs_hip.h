@@ -406,6 +406,10 @@ SCS_HIP_API const char *scs_hip_last_error(void);
 SCS_HIP_API ScsWork *scs_init_spectral(const ScsData *d, const ScsCone *k, const ScsSettings *stgs);
 SCS_HIP_API ScsWork *scs_hip_init_linsys_spectral(const ScsData *d, const ScsCone *k, const ScsSettings *stgs, int linsys);
 SCS_HIP_API int scs_hip_proj_cone_spectral(scs_float *x, const ScsCone *k, scs_int m, int dual);
+/* scs_hip_normalize for a cone with spectral rows: each log-det, nuclear, ell1 and sum-of-largest cone is one block with one
+ * row scale (tests).  Not remapped below: the plain name stays the short-struct entry. */
+SCS_HIP_API int scs_hip_normalize_spectral(ScsMatrix *A, ScsMatrix *P, scs_float *b, scs_float *c, const ScsCone *k,
+                      scs_float *D, scs_float *E, scs_float *sigma);
 #if !defined(SCS_HIP_BUILDING_LIBRARY)
 #define scs_init scs_init_spectral
 #define scs_hip_init_linsys scs_hip_init_linsys_spectral

@@ -441,14 +441,13 @@ static int kkt_solve_entry(const ScsMatrix *A, const ScsMatrix *P, const scs_flo
   }
 }
 
-int scs_hip_normalize(ScsMatrix *A, ScsMatrix *P, scs_float *b, scs_float *c, const ScsCone *k, scs_float *D, scs_float *E,
-                      scs_float *sigma) {
+static int normalize_impl(ScsMatrix *A, ScsMatrix *P, scs_float *b, scs_float *c, const ScsCone *k, scs_float *D, scs_float *E,
+                          scs_float *sigma) {
   try {
     set_last_error("");
     refresh_options();
     HostCone cone;
-    const ScsCone kk = short_cone(k);
-    if (!k || !build_cone(&kk, cone) || cone.m != A->m) throw std::runtime_error("invalid cone");
+    if (!k || !build_cone(k, cone) || cone.m != A->m) throw std::runtime_error("invalid cone");
     if (!validate_matrix(A, A->m, A->n)) throw std::runtime_error("invalid A");
     TmpStream ts;
     hipStream_t s = ts.s;
@@ -488,6 +487,17 @@ int scs_hip_normalize(ScsMatrix *A, ScsMatrix *P, scs_float *b, scs_float *c, co
     set_last_error(e.what());
     return -1;
   }
+}
+
+int scs_hip_normalize(ScsMatrix *A, ScsMatrix *P, scs_float *b, scs_float *c, const ScsCone *k, scs_float *D, scs_float *E,
+                      scs_float *sigma) {
+  const ScsCone kk = short_cone(k);
+  return normalize_impl(A, P, b, c, k ? &kk : nullptr, D, E, sigma);
+}
+// the same with the spectral fields of ScsCone read: one block (one row scale) per log-det, nuclear, ell1 and sum-of-largest cone
+int scs_hip_normalize_spectral(ScsMatrix *A, ScsMatrix *P, scs_float *b, scs_float *c, const ScsCone *k, scs_float *D, scs_float *E,
+                               scs_float *sigma) {
+  return normalize_impl(A, P, b, c, k, D, E, sigma);
 }
 
 // ---- Anderson acceleration as a standalone object (row a6): the interface of scs_source/src/aa.c

@@ -207,6 +207,8 @@ def _load():
     lib.scs_hip_normalize.restype = c_int
     lib.scs_hip_normalize.argtypes = [C.POINTER(_ScsMatrix), C.POINTER(_ScsMatrix), _PD, _PD,
                                       C.POINTER(_ScsCone), _PD, _PD, _PD]
+    lib.scs_hip_normalize_spectral.restype = c_int
+    lib.scs_hip_normalize_spectral.argtypes = lib.scs_hip_normalize.argtypes
     lib.scs_hip_set_profiling.restype = None
     lib.scs_hip_set_profiling.argtypes = [C.c_void_p, c_int]
     lib.scs_hip_kernel_times.restype = None
@@ -1862,19 +1864,29 @@ def kkt_solve_dense(A, P, diag_r, rhs):
     return r
 
 
-def normalize(A, P, b, c, cone):
-    """Returns (A_data_hat, P_data_hat, b_hat, c_hat, D, E, sigma) as scs_init computes them."""
+def _normalize(entry, k, A, P, b, c):
     M, keepA = _matrix(A.copy())
     Pm, keepP = (None, None)
     if P is not None:
         Pm, keepP = _matrix(P.copy())
     bb = np.array(b, dtype=np.float64, copy=True)
     cc = np.array(c, dtype=np.float64, copy=True)
-    k, keep = _no_spectral(cone, "normalize")
     D, E, sig = np.zeros(A.shape[0]), np.zeros(A.shape[1]), np.zeros(1)
-    _check(_lib.scs_hip_normalize(C.byref(M), C.byref(Pm) if Pm is not None else None, _pd(bb), _pd(cc),
-                                  C.byref(k), _pd(D), _pd(E), _pd(sig)))
+    _check(entry(C.byref(M), C.byref(Pm) if Pm is not None else None, _pd(bb), _pd(cc), C.byref(k), _pd(D), _pd(E), _pd(sig)))
     return keepA[0], (keepP[0] if keepP else None), bb, cc, D, E, float(sig[0])
+
+
+def normalize(A, P, b, c, cone):
+    """Returns (A_data_hat, P_data_hat, b_hat, c_hat, D, E, sigma) as scs_init computes them."""
+    k, keep = _no_spectral(cone, "normalize")
+    return _normalize(_lib.scs_hip_normalize, k, A, P, b, c)
+
+
+def normalize_spectral(A, P, b, c, cone):
+    """`normalize` for a cone that may carry spectral keys (d, nuc_m/nuc_n, ell1, sl_n/sl_k): each such cone is one block of rows
+    with one scale (include/scs_hip.h scs_hip_normalize_spectral)."""
+    k, keep = _cone_struct(cone)
+    return _normalize(_lib.scs_hip_normalize_spectral, k, A, P, b, c)
 
 
 def copy_bandwidth(nbytes=1 << 30, reps=10):

@@ -198,5 +198,6 @@ def C_sizeof(t):
 def test_spectral_entry_points_are_exported():
     import ctypes
     lib = ctypes.CDLL(os.path.join(ROOT, "scs-python_amd", "scs", "libscs_hip.so"))
-    for name in ("scs_init_spectral", "scs_hip_init_linsys_spectral", "scs_hip_proj_cone_spectral", "scs_init", "scs_hip_proj_cone"):
+    for name in ("scs_init_spectral", "scs_hip_init_linsys_spectral", "scs_hip_proj_cone_spectral", "scs_hip_normalize_spectral", "scs_init",
+                 "scs_hip_proj_cone"):
         assert hasattr(lib, name), name
