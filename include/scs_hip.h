@@ -97,7 +97,8 @@ SCS_HIP_API double scs_hip_spmv_bench(const ScsMatrix *A, int transpose, int rep
 SCS_HIP_API int scs_hip_proj_cone(scs_float *x, const ScsCone *k, scs_int m, int dual);
 
 /* The derivative of that projection (csrc/dproj.hpp) at v, applied to u: out_Wu = W u and out_WmIu = (W - I) u with W = D Pi_K(v)
- * (v, u, the outputs: `len` doubles, host pointers; an output may be NULL).  Zero, nonnegative, second-order and real PSD (s) cones only.  (parity tests) */
+ * (v, u, the outputs: `len` doubles, host pointers; an output may be NULL).  Zero, nonnegative, box, second-order, real PSD (s) and power (p)
+ * cones; the others are refused by name.  (parity tests) */
 SCS_HIP_API int scs_hip_dproj_cone(const scs_float *v, const scs_float *u, const ScsCone *cone, scs_int len, scs_float *out_Wu, scs_float *out_WmIu);
 
 /* The same projection applied to `count` vectors one after the other (xs: count x m, row-major, in place) through ONE set of cone
@@ -215,7 +216,7 @@ SCS_HIP_API scs_int scs_hip_update_matrix_device(ScsWork *w, const scs_float *Ax
  *
  * Returns 0, or -1 with the reason in scs_hip_last_error — refused before any device work, the workspace unchanged and usable: a NULL
  * workspace; no solve yet, or the last solve did not end SCS_SOLVED / SCS_SOLVED_INACCURATE; scs_update, scs_hip_update_device or
- * scs_hip_update_matrix[_device] ran since the last solve (the resident solution is stale); a cone other than z, l, q, s (named in the
+ * scs_hip_update_matrix[_device] ran since the last solve (the resident solution is stale); a cone other than z, l, box, q, s, p (named in the
  * message); (device entries) a pointer that is not device memory of the workspace's device; dPx for a workspace created without P, or
  * with a P whose values scs_hip_update_matrix would refuse (entries below the diagonal, unsorted rows). */
 typedef struct {
@@ -366,6 +367,14 @@ SCS_HIP_API void scs_hip_aa_finish(ScsHipAa *a);
  * the ADMM loop) on the solver's stream; out[4] = {ms per projection, matrices, largest order, reference flop count
  * ((16/3 + 2) n^3 per matrix)}.  0 on success, 1 when the problem has no PSD cone. */
 SCS_HIP_API int scs_hip_time_psd(ScsWork *w, int reps, double *out);
+
+/* tools/adjoint_bench.py --cones: after a solve, the kernels of the box and power derivative (csrc/dproj_box_pow.hpp) at the solution's
+ * fixed point, timed with events on the workspace's stream, `reps` launches each.  out[8] = {ms per box W apply in the one-workgroup
+ * form, ms in the two-launch form (both at this cone's size, whatever form a call would pick), ms per projection of the same cone in
+ * the form a solve uses (on scratch: the solve's warm start is not touched), bsize, ms per W apply of the power cones, ms per
+ * preparation of their W, ms per projection of them, their count}; the entries of a cone the problem does not have are 0.
+ * 0 on success, -1 with a reason where scs_hip_adjoint would refuse the workspace. */
+SCS_HIP_API int scs_hip_time_dproj(ScsWork *w, int reps, double *out);
 
 /* Hands the device blocks this library caches for reuse (dead workspaces' buffers, at most SCS_HIP_POOL_MB = 1024 MiB by default) back
  * to the driver: for a process that shares its GPUs with allocators this library does not see (torch, RCCL, other processes). */

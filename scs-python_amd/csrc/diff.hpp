@@ -8,7 +8,10 @@
 //            (with perturbations dA, dP of the matrix values: dc + dP x + dA' y and db - dA x in place of dc and db — perturb.hpp)
 // The systems are solved by LSQR (lsqr.hpp) on the RESIDENT, equilibrated matrices A^ = D A E, P^ = E P E at v^ = sigma (D s - y / D):
 // the hatted problem has the same F, and D is constant on every SOC block and on every PSD block (normalize_dev.hpp k_enforce_blocks), so
-// Pi commutes with the scaling there and the derivation carries over to the s cones unchanged (dproj_psd.hpp).
+// Pi commutes with the scaling there and the derivation carries over to the s cones unchanged (dproj_psd.hpp).  The same holds for the
+// power cones: each is a 3-row boundary of HostCone::boundaries, so D is constant on it.  The box cone in hatted coordinates is again
+// a box cone, with the bounds bl_j D_{j+1} / D_0 — the workspace's working copies box_bl / box_bu (setup.hpp), not the _orig ones —
+// so its W is that of the hatted cone at v^ (dproj_box_pow.hpp) and nothing else changes.
 // In: gx^ = E gx / sigma, gy^ = D gy / sigma,
 // gs^ = gs / (D sigma), dc^ = sigma E dc, db^ = sigma D db.  Out: dL/dc = sigma E dL/dc^, dL/db = sigma D dL/db^,
 // dL/dA_ij = D_i E_j dL/dA^_ij, dL/dP_ij = E_i E_j dL/dP^_ij; dx = E dx^ / sigma, dy = D dy^ / sigma, ds = ds^ / (D sigma).  With
@@ -131,11 +134,28 @@ static std::string diff_refusal(const ScsHipWork *w) {
   if (w->diff_state == 2) return "the last solve did not end solved (status " + std::to_string(w->last_status_val) + "): there is no solution to differentiate";
   if (w->diff_state == 3) return "the resident solution is stale: b, c or the matrix changed since the last solve; solve again first";
   const HostCone &c = w->cone;
-  const char *other = c.bsize > 1 ? "box" : !c.cs.empty() ? "complex PSD (cs)" : c.ep > 0 ? "exponential (ep)" :
-                      c.ed > 0 ? "dual exponential (ed)" : !c.p.empty() ? "power (p)" : !c.d.empty() ? "log-det (d)" :
-                      !c.nuc_m.empty() ? "nuclear norm (nuc)" : !c.ell1.empty() ? "ell1" : !c.sl_n.empty() ? "sum-of-largest (sl)" : nullptr;
-  if (other) return std::string("the derivative of the ") + other + " cone projection is not implemented (z, l, q and s cones only)";
+  const char *other = !c.cs.empty() ? "complex PSD (cs)" : c.ep > 0 ? "exponential (ep)" : c.ed > 0 ? "dual exponential (ed)" :
+                      !c.d.empty() ? "log-det (d)" : !c.nuc_m.empty() ? "nuclear norm (nuc)" : !c.ell1.empty() ? "ell1" :
+                      !c.sl_n.empty() ? "sum-of-largest (sl)" : nullptr;
+  if (other)
+    return std::string("the derivative of the ") + other + " cone projection is not implemented (z, l, q and s cones only, plus box and p)";
   return "";
+}
+
+// the box and power tables of a cone plan: the workspace's WORKING bounds (they follow the row scaling) and exponents, the caller's
+// scratch (dbox_scratch_doubles(bsize) doubles, one ticket for a box above kDboxMultiMin, 6 doubles per power cone) and m doubles
+// nobody reads during the preparation
+static void dproj_plan_box_pow(DprojPlan &plan, const ScsHipWork *w, double *box_st, unsigned *ticket, double *sym3, double *tmp_m) {
+  const HostCone &c = w->cone;
+  if (c.bsize > 0) {
+    plan.box.bsize = c.bsize; plan.box.off = c.off_box;
+    plan.box.bl = w->box_bl.p; plan.box.bu = w->box_bu.p;
+    plan.box.st = box_st; plan.box.ticket = ticket; plan.box.tmp = tmp_m + c.off_box;
+  }
+  if (!c.p.empty()) {
+    plan.sym3.count = (int)c.p.size(); plan.sym3.off = c.off_p;
+    plan.sym3.a = w->pow_a.p; plan.sym3.W = sym3;
+  }
 }
 
 struct DiffCall {
@@ -156,6 +176,9 @@ static void diff_alloc(ScsHipWork *w) {
   for (DevBuf<double> *b : {&d.tAt, &d.tP}) b->alloc(n);
   d.cinfo.alloc((size_t)3 * std::max(w->n_soc, 1));
   d.psd.build(w->psd_order_h, w->psd_off.p, w->psd_order.p, w->psd_woff.p, w->stream);
+  if (w->cone.bsize > 0) d.box.alloc(dbox_scratch_doubles(w->cone.bsize));
+  if (w->cone.bsize > kDboxMultiMin) d.box_ticket.alloc_zero(1, w->stream);
+  if (!w->cone.p.empty()) d.sym3.alloc((size_t)6 * w->cone.p.size());
   const size_t nb = (size_t)vec_blocks((long)N);
   for (DevBuf<double> *b : {&d.partU, &d.partV, &d.partX}) b->alloc(nb);
   d.st.alloc(L_COUNT);
@@ -213,6 +236,7 @@ static void diff_impl(ScsHipWork *w, const DiffCall &a, const ScsHipDiffOpts *o,
   plan.vh = d.vhat.p; plan.cinfo = d.cinfo.p; plan.m = m;
   plan.psd = d.psd.plan;
   plan.psd.tmp_m = d.dW.p;  // (free until the right-hand side is formed)
+  dproj_plan_box_pow(plan, w, d.box.p, d.box_ticket.p, d.sym3.p, d.dW.p);
   launch_dproj_prep(plan, s);
 
   // ---- right-hand side into uh, x = w = 0 ----

@@ -51,17 +51,23 @@ struct GroupDiff {
     SCS_GTABLE(kDprojPsdThreads, d_dproj_psd_fused) psd;
     SCS_GTABLE(kConeThreads, d_dproj_soc_wave) soc;
     SCS_GTABLE(kConeThreads, d_dproj_soc_block) soc_big;
+    SCS_GTABLE(kBoxThreads, d_dbox) box;  // (one workgroup: a box above kDboxMultiMin keeps its member solo, member_ok)
+    SCS_GTABLE(kConeThreads, d_dproj_sym3) sym3;
     void size(const DprojPlan &p, size_t G) {
       if (p.z + p.l > 0) { zl.resize(G); zl.gx = vec_blocks(p.z + p.l); }
       if (p.psd.n_small > 0) { psd.resize(G); psd.gx = ceil_div(p.psd.n_small, kDprojPsdThreads / 64); psd.lds = kDprojPsdFusedLds; }
       if (p.n_soc > 0) { soc.resize(G); soc.gx = soc_wave_blocks(p.n_soc, p.G); }
       if (p.n_soc > 0 && p.n_soc_big > 0) { soc_big.resize(G); soc_big.gx = p.n_soc_big; }
+      if (p.box.bsize > 0) { box.resize(G); box.gx = 1; }
+      if (p.sym3.count > 0) { sym3.resize(G); sym3.gx = ceil_div(p.sym3.count, kConeThreads); }
     }
     void set(int g, const DprojPlan &p, const DprojIo &io, const int *done) {
       if (zl.used) zl.set(g, io, p.vh, p.z, p.l, done);
       if (psd.used) psd.set(g, io, p.psd, done);
       if (soc.used) soc.set(g, io, p.vh, (const double *)p.cinfo, p.off, p.dim, p.n_soc, p.G, done);
       if (soc_big.used) soc_big.set(g, io, p.vh, (const double *)p.cinfo, p.off, p.dim, p.big, done);
+      if (box.used) box.set(g, io, p.vh + p.box.off, p.box.bl, p.box.bu, p.box.bsize, p.box.off, (const double *)p.box.st, done);
+      if (sym3.used) sym3.set(g, io, (const double *)p.sym3.W, p.sym3.count, p.sym3.off, done);
     }
   };
   // one product J q or J' l (diff.hpp prod_J / prod_Jt) over the group
@@ -74,6 +80,8 @@ struct GroupDiff {
   SCS_GTABLE(kVecThreads, d_dproj_vhat) t_vhat;
   SCS_GTABLE(kConeThreads, d_dproj_prep_wave) t_prep_wave;
   SCS_GTABLE(kConeThreads, d_dproj_prep_block) t_prep_block;
+  SCS_GTABLE(kBoxThreads, d_dbox_prep) t_box_prep;
+  SCS_GTABLE(kConeThreads, d_dpow_prep) t_pow_prep;
   SCS_GTABLE(kVecThreads, d_copy_f64) t_psd_copy, t_copy_out0, t_copy_out1, t_gather_st;
   SCS_GTABLE(kPsdThreads, d_proj_psd<0>) t_psd_eig;
   SCS_GTABLE(kDprojPsdThreads, d_dproj_psd_gather) t_psd_gather;
@@ -119,18 +127,19 @@ struct GroupDiff {
     if (w->has_P && (w->Pf.cs.ok || w->Pf.has_slab)) return false;
     for (int o : w->psd_order_h)
       if (o > kDprojPsdFusedMax) return false;
+    if (w->cone.bsize > kDboxMultiMin) return false;  // the multi-launch box apply (and the 25 rounds of its preparation)
     return true;
   }
   // the part of GroupSolve::same_shape the derivative depends on
   static bool same_shape(const ScsHipWork *a, const ScsHipWork *b) {
     const HostCone &x = a->cone, &y = b->cone;
     return a->device == b->device && a->n == b->n && a->m == b->m && a->has_P == b->has_P && a->normalized == b->normalized &&
-           x.z == y.z && x.l == y.l && x.q == y.q && x.s == y.s;
+           x.z == y.z && x.l == y.l && x.bsize == y.bsize && x.q == y.q && x.s == y.s && x.p.size() == y.p.size();
   }
 
-  template <class F> void for_dproj(DprojTabs &d, F &&f) { f(d.zl); f(d.psd); f(d.soc); f(d.soc_big); }
+  template <class F> void for_dproj(DprojTabs &d, F &&f) { f(d.zl); f(d.psd); f(d.box); f(d.sym3); f(d.soc); f(d.soc_big); }
   template <class F> void for_tables(F &&f) {
-    f(t_vhat); f(t_prep_wave); f(t_prep_block); f(t_psd_copy); f(t_copy_out0); f(t_copy_out1); f(t_gather_st); f(t_psd_eig);
+    f(t_vhat); f(t_prep_wave); f(t_prep_block); f(t_box_prep); f(t_pow_prep); f(t_psd_copy); f(t_copy_out0); f(t_copy_out1); f(t_gather_st); f(t_psd_eig);
     f(t_psd_gather); f(t_adj_in); f(t_fwd_in); f(t_pert[0]); f(t_pert[1]); f(t_pert[2]); f(t_pert_eff); f(t_start); f(t_lsqr_v); f(t_lsqr_u); f(t_adj_out); f(t_fwd_out); f(t_grad_a);
     f(t_grad_p); f(t_gather_fl);
     for (DprojTabs *d : {&rhs1, &rhs2, &pv.dp, &pu.dp}) for_dproj(*d, f);
@@ -147,6 +156,8 @@ struct GroupDiff {
   void go_dproj(const DprojTabs &d, const int *list, int count) {  // (the order of launch_dproj)
     go(d.zl, list, count);
     go(d.psd, list, count);
+    go(d.box, list, count);
+    go(d.sym3, list, count);
     go(d.soc, list, count);
     go(d.soc_big, list, count);
   }
@@ -226,6 +237,7 @@ struct GroupDiff {
       plan.vh = d.vhat.p; plan.cinfo = d.cinfo.p; plan.m = m;
       plan.psd = d.psd.plan;
       plan.psd.tmp_m = d.dW.p;
+      dproj_plan_box_pow(plan, w, d.box.p, d.box_ticket.p, d.sym3.p, d.dW.p);
     }
     const DprojPlan &p0 = plans[0];
     const size_t SG = (size_t)G;
@@ -234,6 +246,8 @@ struct GroupDiff {
     t_vhat.resize(SG); t_vhat.gx = vec_blocks(m);
     if (p0.n_soc > 0) { t_prep_wave.resize(SG); t_prep_wave.gx = soc_wave_blocks(p0.n_soc, p0.G); }
     if (p0.n_soc > 0 && p0.n_soc_big > 0) { t_prep_block.resize(SG); t_prep_block.gx = p0.n_soc_big; }
+    if (p0.box.bsize > 0) { t_box_prep.resize(SG); t_box_prep.gx = 1; }
+    if (p0.sym3.count > 0) { t_pow_prep.resize(SG); t_pow_prep.gx = ceil_div(p0.sym3.count, kConeThreads); }
     // the decomposition borrows K9-layout scratch for a slice of the members at a time (stream order protects its reuse)
     const size_t per_member = (size_t)std::max(p0.psd.scratch_doubles, 1L);
     const int slice = (int)std::max<size_t>(1, std::min<size_t>(SG, kDiffPsdBorrowMax / (per_member * sizeof(double))));
@@ -286,6 +300,8 @@ struct GroupDiff {
       t_vhat.set(g, (const double *)w->sols.p, (const double *)w->soly.p, D, sigma, m, d.vhat.p);
       if (t_prep_wave.used) t_prep_wave.set(g, plan.vh, plan.off, plan.dim, plan.n_soc, plan.G, plan.cinfo);
       if (t_prep_block.used) t_prep_block.set(g, plan.vh, plan.off, plan.dim, plan.big, plan.cinfo);
+      if (t_box_prep.used) t_box_prep.set(g, plan.vh + plan.box.off, plan.box.bl, plan.box.bu, plan.box.bsize, plan.box.tmp, plan.box.st);
+      if (t_pow_prep.used) t_pow_prep.set(g, plan.vh + plan.sym3.off, plan.sym3.a, plan.sym3.count, plan.sym3.W);
       if (t_psd_eig.used) {
         double *scr = psd_scratch.p + per_member * (size_t)(g % slice);
         t_psd_copy.set(g, plan.vh, plan.psd.tmp_m, (long)m);
@@ -368,6 +384,8 @@ struct GroupDiff {
       psd_scratch.release();
       --t_pool_release;
     }
+    go(t_box_prep, all_d, G);  // (the order of launch_dproj_prep: after the PSD blocks, whose tmp_m holds box.tmp)
+    go(t_pow_prep, all_d, G);
     go(t_prep_wave, all_d, G);
     go(t_prep_block, all_d, G);
 

@@ -1,4 +1,5 @@
-// dproj.hpp — W = D Pi_K(v), the derivative of the cone projection, applied to a vector: zero, nonnegative, second-order and real PSD cones.
+// dproj.hpp — W = D Pi_K(v), the derivative of the cone projection, applied to a vector: zero, nonnegative, box, second-order, real PSD
+// and power cones.
 //
 // The adjoint and the forward derivative of a solve (lsqr.hpp, diff.hpp) need W u and (W - I) u at the fixed point v = s - y of the
 // last solve.  W is symmetric and block diagonal by cone:
@@ -7,6 +8,7 @@
 //   SOC, v = (t, z), r = |z|:   W = I if r <= t;   W = 0 if r <= -t;   else
 //                      W = 1/(2r) [[r, z'], [z, (t + r) I - t z z'/r^2]]
 //   PSD blocks         dproj_psd.hpp
+//   box cone, power cones (a symmetric 3 x 3 block each)   dproj_box_pow.hpp
 //
 // Mapping to the machine follows the projections (cones.hpp): the off / dim tables, one lane group of soc_group() = 8/16/32/64 lanes per
 // cone up to kSocBig entries, one workgroup per longer cone, q == 1 treated as a nonnegative row.  A preparation pass runs once per
@@ -32,7 +34,8 @@ struct DprojIo {
 
 }  // namespace scship
 
-#include "dproj_psd.hpp"  // the PSD blocks (needs DprojIo)
+#include "dproj_psd.hpp"      // the PSD blocks (needs DprojIo)
+#include "dproj_box_pow.hpp"  // the box cone and the three-row cones (needs DprojIo)
 
 namespace scship {
 
@@ -203,9 +206,13 @@ struct DprojPlan {
   double *cinfo = nullptr;     // 3 doubles per SOC
   long m = 0;                  // length of vh
   DprojPsdPlan psd;            // the PSD blocks (dproj_psd.hpp); count == 0: none
+  DprojBoxPlan box;            // the box cone (dproj_box_pow.hpp); bsize == 0: none
+  DprojSym3Plan sym3;          // the power cones (dproj_box_pow.hpp); count == 0: none
 };
 inline void launch_dproj_prep(const DprojPlan &p, hipStream_t s) {
   launch_dproj_psd_prep(p.psd, p.vh, p.m, s);
+  launch_dbox_prep(p.box, p.vh, s);  // (after the PSD blocks: box.tmp may lie inside psd.tmp_m)
+  launch_dsym3_prep(p.sym3, p.vh, s);
   if (p.n_soc <= 0) return;
   hipLaunchKernelGGL(k_dproj_prep_wave, dim3(soc_wave_blocks(p.n_soc, p.G)), dim3(kConeThreads), 0, s, p.vh, p.off, p.dim, p.n_soc, p.G, p.cinfo);
   if (p.n_soc_big > 0) hipLaunchKernelGGL(k_dproj_prep_block, dim3(p.n_soc_big), dim3(kConeThreads), 0, s, p.vh, p.off, p.dim, p.big, p.cinfo);
@@ -213,6 +220,8 @@ inline void launch_dproj_prep(const DprojPlan &p, hipStream_t s) {
 inline void launch_dproj(const DprojPlan &p, const DprojIo &io, const int *done, hipStream_t s) {
   if (p.z + p.l > 0) hipLaunchKernelGGL(k_dproj_zl, dim3(vec_blocks(p.z + p.l)), dim3(kVecThreads), 0, s, io, p.vh, p.z, p.l, done);
   launch_dproj_psd(p.psd, io, done, s);
+  launch_dbox(p.box, p.vh, io, done, s);
+  launch_dsym3(p.sym3, io, done, s);
   if (p.n_soc <= 0) return;
   hipLaunchKernelGGL(k_dproj_soc_wave, dim3(soc_wave_blocks(p.n_soc, p.G)), dim3(kConeThreads), 0, s, io, p.vh, (const double *)p.cinfo, p.off, p.dim,
                      p.n_soc, p.G, done);

@@ -273,7 +273,7 @@ int scs_hip_proj_cone(scs_float *x, const ScsCone *k, scs_int m, int dual) {
 }
 int scs_hip_proj_cone_spectral(scs_float *x, const ScsCone *k, scs_int m, int dual) { return proj_cone_impl(x, k, m, dual); }
 
-// W u and (W - I) u at v for the z, l, q, s cones (csrc/dproj.hpp, dproj_psd.hpp): the kernels of the derivative entry points on host vectors
+// W u and (W - I) u at v for the z, l, box, q, s and p cones (csrc/dproj.hpp, dproj_psd.hpp, dproj_box_pow.hpp): the kernels of the derivative entry points on host vectors
 int scs_hip_dproj_cone(const scs_float *v, const scs_float *u, const ScsCone *cone, scs_int len, scs_float *out_Wu, scs_float *out_WmIu) {
   try {
     set_last_error("");
@@ -301,6 +301,12 @@ int scs_hip_dproj_cone(const scs_float *v, const scs_float *u, const ScsCone *co
     psd.build(w.psd_order_h, w.psd_off.p, w.psd_order.p, w.psd_woff.p, ts.s);
     plan.psd = psd.plan;
     plan.psd.tmp_m = dWu.p;  // (overwritten by the apply)
+    DevBuf<double> box_st, sym3;
+    DevBuf<unsigned> ticket;
+    if (w.cone.bsize > 0) box_st.alloc(dbox_scratch_doubles(w.cone.bsize));
+    if (w.cone.bsize > kDboxMultiMin) ticket.alloc_zero(1, ts.s);
+    if (!w.cone.p.empty()) sym3.alloc((size_t)6 * w.cone.p.size());
+    dproj_plan_box_pow(plan, &w, box_st.p, ticket.p, sym3.p, dWu.p);
     launch_dproj_prep(plan, ts.s);
     launch_dproj(plan, DprojIo{du.p, nullptr, dWu.p, dWmI.p}, nullptr, ts.s);
     HIP_CHECK(hipGetLastError());

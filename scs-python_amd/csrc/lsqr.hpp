@@ -194,6 +194,8 @@ struct DiffScratch {
   bool ready = false, tri_ready = false;
   DevBuf<double> uh, vh, w, x, tA, dW, dWmI, vhat, tAt, tP, cinfo, partU, partV, partX, st;
   DprojPsdTables psd;
+  DevBuf<double> box, sym3;     // the box cone's state (dbox_scratch_doubles) and the power cones' W (6 per cone); none of either: not allocated
+  DevBuf<unsigned> box_ticket;  // (k_proj_box_round, box cones above kDboxMultiMin only)
   DevBuf<int> fl, tri_up;  // tri_up: column pointers of the caller's triangle of P (the gather of dL/dP), built at the first request
   DevBuf<double> eff;      // (dc_eff ; db_eff) of a forward call that perturbs A or P (perturb.hpp): n + m, taken at the first such call
 };

@@ -1085,6 +1085,97 @@ int scs_hip_time_psd(ScsWork *w, int reps, double *out) {
   }
 }
 
+int scs_hip_time_dproj(ScsWork *w, int reps, double *out) {
+  if (!w || !out || reps <= 0) return -1;
+  try {
+    set_last_error("");
+    std::lock_guard<std::mutex> lock(w->mtx);
+    const std::string why = diff_refusal(w);
+    if (!why.empty()) throw std::runtime_error("scs_hip_time_dproj: " + why);
+    HIP_CHECK(hipSetDevice(w->device));
+    ScsHipWork::ScratchTurn turn(w);
+    hipStream_t s = w->stream;
+    const int m = w->m;
+    diff_alloc(w);
+    DiffScratch &d = w->diff;
+    const double *D = w->normalized ? w->D.p : nullptr;
+    hipLaunchKernelGGL(k_dproj_vhat, dim3(vec_blocks(m)), dim3(kVecThreads), 0, s, (const double *)w->sols.p, (const double *)w->soly.p, D,
+                       w->normalized ? w->scal.sigma : 1.0, m, d.vhat.p);
+    DprojPlan plan;
+    plan.vh = d.vhat.p; plan.m = m;
+    dproj_plan_box_pow(plan, w, d.box.p, d.box_ticket.p, d.sym3.p, d.dW.p);
+    // the two-launch form needs the partial slots whatever the size: scratch of this call when the workspace holds the short state
+    ArenaScope no_arena(nullptr);
+    DevBuf<double> st_big;
+    DevBuf<unsigned> ticket;
+    DprojBoxPlan multi = plan.box;
+    if (plan.box.bsize > 0 && !plan.box.multi()) {
+      st_big.alloc((size_t)DB_STATE + 3 * kBoxMultiMaxWgs);
+      ticket.alloc_zero(1, s);
+      multi.st = st_big.p; multi.ticket = ticket.p;
+    }
+    launch_dbox_prep(plan.box, plan.vh, s);
+    launch_dsym3_prep(plan.sym3, plan.vh, s);
+    if (st_big.p) HIP_CHECK(hipMemcpyAsync(st_big.p, plan.box.st, sizeof(double) * DB_STATE, hipMemcpyDeviceToDevice, s));
+    const DprojIo io{d.uh.p + w->n, nullptr, d.dW.p, d.dWmI.p};  // (any m-vector serves as u)
+    HIP_CHECK(hipMemsetAsync(d.uh.p, 0, sizeof(double) * ((size_t)w->n + m), s));
+    auto timed = [&](auto &&body) {
+      for (int i = 0; i < 2; ++i) body();
+      HIP_CHECK(hipEventRecord(w->ev[0], s));
+      for (int i = 0; i < reps; ++i) body();
+      HIP_CHECK(hipEventRecord(w->ev[1], s));
+      HIP_CHECK(hipEventSynchronize(w->ev[1]));
+      HIP_CHECK(hipGetLastError());
+      float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+      return (double)ms / reps;
+    };
+    for (int i = 0; i < 8; ++i) out[i] = 0.;
+    const DprojBoxPlan &b = plan.box;
+    if (b.bsize > 1) {
+      const double *vb = plan.vh + b.off;
+      const int wgs = box_multi_wgs(b.bsize);
+      out[0] = timed([&] { hipLaunchKernelGGL(k_dbox, dim3(1), dim3(kBoxThreads), 0, s, io, vb, b.bl, b.bu, b.bsize, b.off, (const double *)b.st,
+                                              (const int *)nullptr); });
+      out[1] = timed([&] {
+        hipLaunchKernelGGL(k_dbox_part, dim3(wgs), dim3(kBoxMultiThreads), 0, s, io, vb, b.bl, b.bu, b.bsize, b.off, (const double *)multi.st, 0,
+                           multi.parts(), (const int *)nullptr);
+        hipLaunchKernelGGL(k_dbox_rows, dim3(wgs), dim3(kBoxMultiThreads), 0, s, io, vb, b.bl, b.bu, b.bsize, b.off, (const double *)multi.st,
+                           (const double *)multi.parts(), wgs, (const int *)nullptr);
+      });
+      // one projection of the same cone, in the form a solve uses at this size, on the scratch copy and this call's own t
+      double *tw = multi.st + DB_STOP + 1;  // (a free slot of the state)
+      const double one = 1.0;
+      HIP_CHECK(hipMemcpyAsync(tw, &one, sizeof(double), hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      if (b.bsize > kBoxMultiMin)
+        out[2] = timed([&] {
+          for (int round = 0; round < kBoxRounds; ++round)
+            hipLaunchKernelGGL(k_proj_box_round, dim3(wgs), dim3(kBoxMultiThreads), 0, s, vb, b.bl, b.bu, b.bsize, multi.st, multi.round_parts(),
+                               multi.ticket, 0, round, (const int *)nullptr);
+          hipLaunchKernelGGL(k_proj_box_apply, dim3(wgs), dim3(kBoxMultiThreads), 0, s, b.tmp, b.bl, b.bu, b.bsize, multi.st, 0, (const int *)nullptr);
+        });
+      else
+        out[2] = timed([&] { hipLaunchKernelGGL(k_proj_box, dim3(1), dim3(kBoxThreads), 0, s, b.tmp, b.bl, b.bu, b.bsize, tw, 0, (const int *)nullptr); });
+      out[3] = (double)b.bsize;
+    }
+    const DprojSym3Plan &p3 = plan.sym3;
+    if (p3.count > 0) {
+      out[4] = timed([&] { launch_dsym3(p3, io, nullptr, s); });
+      out[5] = timed([&] { launch_dsym3_prep(p3, plan.vh, s); });
+      HIP_CHECK(hipMemcpyAsync(d.dW.p + p3.off, plan.vh + p3.off, sizeof(double) * 3 * (size_t)p3.count, hipMemcpyDeviceToDevice, s));
+      out[6] = timed([&] { hipLaunchKernelGGL(k_proj_pow_primal, dim3(ceil_div(p3.count, kConeThreads)), dim3(kConeThreads), 0, s, d.dW.p + p3.off, p3.a,
+                                              p3.count, (const int *)nullptr); });
+      out[7] = (double)p3.count;
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return -1;
+  }
+}
+
 void scs_hip_set_profiling(ScsWork *w, int on) {
   if (w) w->profile = on != 0;
 }

@@ -370,7 +370,7 @@ def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None,
 
 def diff_batch_plan(solvers, want=("b", "c")):
   """How `adjoint_batch(solvers, want=want)` would split the batch: one int per solver, the index of the group it would share launches
-  with, or -1 where it is differentiated alone (a shape of its own, a pass or slab matrix layout, a PSD block above order 32)."""
+  with, or -1 where it is differentiated alone (a shape of its own, a pass or slab matrix layout, a PSD block above order 32, a box cone above 16384 rows)."""
   return _scs_hip.diff_batch_plan(_raw_solvers(solvers, "diff_batch_plan"), want)
 
 

@@ -266,6 +266,8 @@ def _load():
     lib.scs_hip_get_mark.argtypes = [C.c_void_p, _PD]
     lib.scs_hip_time_psd.restype = c_int
     lib.scs_hip_time_psd.argtypes = [C.c_void_p, c_int, _PD]
+    lib.scs_hip_time_dproj.restype = c_int
+    lib.scs_hip_time_dproj.argtypes = [C.c_void_p, c_int, _PD]
     lib.scs_hip_trim_pool.restype = None
     lib.scs_hip_trim_pool.argtypes = []
     lib.scs_hip_pool_stats.restype = None
@@ -1184,6 +1186,17 @@ class SCS(object):
         _check(rc)
         return {"ms": float(out[0]), "matrices": int(out[1]), "max_order": int(out[2]), "ref_flops": float(out[3])}
 
+    def _time_dproj(self, reps=50):
+        """after a solve: ms per launch of the box and power derivative kernels and of the projections of the same cones
+        (include/scs_hip.h scs_hip_time_dproj; tools/adjoint_bench.py --cones)"""
+        out = np.zeros(8)
+        with self._lock:
+            rc = _lib.scs_hip_time_dproj(self._work, int(reps), _pd(out))
+        if rc != 0:
+            raise ValueError("libscs_hip: " + last_error())
+        return {"box_apply_one_wg_ms": float(out[0]), "box_apply_two_launch_ms": float(out[1]), "box_proj_ms": float(out[2]), "bsize": int(out[3]),
+                "pow_apply_ms": float(out[4]), "pow_prep_ms": float(out[5]), "pow_proj_ms": float(out[6]), "pow_cones": int(out[7])}
+
     def _psd_refine_stats(self, cap=4096):
         """per PSD matrix of order > 32: [calls refined, refinements sent back to the sweeps, |K1|_F^2 at the last gate,
         mixed-sign off-norm^2 / |A|^2 after the last refinement, stage flag of the last call, then what the last call's matrix looked like
@@ -1785,7 +1798,7 @@ def proj_cone(z, cone, dual=False):
 
 
 def dproj_cone(v, u, cone):
-    """(W u, (W - I) u) with W the derivative of the projection onto the cone at v: the kernels of `SCS.adjoint` (z, l, q and s cones)"""
+    """(W u, (W - I) u) with W the derivative of the projection onto the cone at v: the kernels of `SCS.adjoint` (z, l, box, q, s and p cones)"""
     v = np.ascontiguousarray(v, dtype=np.float64)
     u = np.ascontiguousarray(u, dtype=np.float64)
     if v.ndim != 1 or v.shape != u.shape:

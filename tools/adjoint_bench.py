@@ -24,6 +24,16 @@ parent commit) the call WITHOUT dA / dP is also timed there, in child processes 
 it must not have become slower, the margin being the parent's own spread (max - min of its child medians) in that run.
 
   python tools/adjoint_bench.py --matrix [--workloads target_lp_soc,target_qp,config5_member] [--reps 5] [--parent-root DIR] [--out profiles/derivative_matrix.txt]
+
+--cones is the leg of the box and power derivative (csrc/dproj_box_pow.hpp).  Two workloads built from a chosen primal-dual pair: box_qp, a
+bounded QP in the MPC shape (--box-bounds variables, each with a lower and an upper bound: ONE box cone, t fixed to 1 by a zero row of
+A, a third of the bounds active on each side; sparse positive definite P and --box-eq equality rows), and pow, --pow-cones power cones
+(primal and dual exponents, a third each inside / polar / boundary) under a sparse square A and a diagonal P.  Each is solved, adjoint_device runs to --tol, then
+with caps k1 < k2 on the LSQR iterations (tol 1e-300) ms/LSQR it = (t(k2) - t(k1)) / (k2 - k1); scs_hip_time_dproj times, with events on
+the workspace's stream, one W apply of the cone — the box cone in BOTH forms at the same size — next to one projection of the same cone.
+--box-sizes adds the two forms of the box apply at further sizes (the crossing of the two forms: kDboxMultiMin).
+
+  python tools/adjoint_bench.py --cones [--box-bounds 60000] [--pow-cones 4000] [--box-sizes 1000,4000,16000,60000,99999] [--out profiles/adjoint_box_pow.txt]
 """
 import argparse
 import os
@@ -150,6 +160,115 @@ def matrix_leg(args):
             f.write(text + "\n")
 
 
+def box_qp_workload(k, neq, seed=7):
+    """(data, cone, pair): n = k variables, rows = neq equalities | t | k bounds; a third of the bounds active on each side"""
+    from scipy import sparse
+    rng = np.random.default_rng(seed)
+    bl, bu = -rng.uniform(0.5, 2.0, k), rng.uniform(0.5, 2.0, k)
+    kind = rng.integers(0, 20, k)
+    bu[kind == 0] = np.inf
+    bl[kind == 1] = 0.0
+    sets = rng.integers(0, 3, k)
+    sets[(sets == 0) & ~np.isfinite(bu)] = 2
+    d = rng.uniform(0.3, 1.0, k)
+    hi = np.where(np.isfinite(bu), bu, bl + 2.0)
+    w = bl + rng.uniform(0.2, 0.8, k) * (hi - bl)
+    U, L = sets == 0, sets == 1
+    w[U], w[L] = bu[U] + d[U], bl[L] - d[L]
+    v_box = np.concatenate([[1.0 - np.sum(d[U] * bu[U]) + np.sum(d[L] * bl[L])], w])
+    s_box = np.concatenate([[1.0], np.where(U, bu, np.where(L, bl, w))])
+    vz = rng.uniform(0.5, 1.5, neq) * rng.choice([-1.0, 1.0], neq)
+    s = np.concatenate([np.zeros(neq), s_box])
+    y = s - np.concatenate([vz, v_box])
+    x = s_box[1:].copy()  # bound rows of A are -I with b = 0: s = x
+    free = np.flatnonzero(sets == 2)  # (the equality rows couple free variables only: no row is decided by the active bounds alone)
+    Aeq = sparse.csc_matrix((rng.standard_normal(8 * neq), (np.repeat(np.arange(neq), 8), rng.choice(free, 8 * neq))), shape=(neq, k))
+    A = sparse.vstack([Aeq, sparse.csc_matrix((1, k)), -sparse.identity(k)]).tocsc()
+    A.sort_indices()
+    off = sparse.csc_matrix((rng.standard_normal(2 * k), (rng.integers(0, k, 2 * k), rng.integers(0, k, 2 * k))), shape=(k, k))
+    P = sparse.csc_matrix(sparse.diags(1.0 + rng.random(k)) + 0.1 * (off + off.T))
+    b = A @ x + s
+    c = -(P @ x) - A.T @ y
+    Pu = sparse.triu(P, format="csc")
+    Pu.sort_indices()
+    return {"A": A, "P": Pu, "b": b, "c": c}, {"z": neq, "bl": bl, "bu": bu}, (x, y, s)
+
+
+def pow_workload(npow, n, seed=8):
+    from scipy import sparse
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dproj_cones_ref as dr
+    rng = np.random.default_rng(seed)
+    a = rng.uniform(0.1, 0.9, npow) * rng.choice([-1.0, 1.0], npow)
+    v = np.concatenate([dr.pow_point(rng, a[i], ("in", "polar", "bd")[i % 3]) for i in range(npow)])
+    s = np.concatenate([dr.pow_project(v[3 * i:3 * i + 3], a[i]) for i in range(npow)])
+    y = s - v
+    m = 3 * npow
+    A = sparse.csc_matrix((rng.standard_normal(6 * m), (np.repeat(np.arange(m), 6), rng.integers(0, n, 6 * m))), shape=(m, n))
+    A.sort_indices()
+    x = rng.standard_normal(n)
+    P = sparse.diags(1.0 + rng.random(n)).tocsc()
+    return {"A": A, "P": P, "b": A @ x + s, "c": -(P @ x) - A.T @ y}, {"p": a}, (x, y, s)
+
+
+def cones_leg(args):
+    import torch
+    import scs
+    from scs import _scs_hip
+    if _scs_hip.device_count() < 1:
+        raise SystemExit("adjoint_bench: no HIP device (there is nothing to measure without one)")
+    lines = ["adjoint_bench --cones: SCS.adjoint_device (want b, c) after a solve; tol %g, ADMM cap %d, %d repetitions (median); "
+             "kernel times: %d launches between two events" % (args.tol, args.solve_iters, args.reps, args.kernel_reps)]
+    works = (("box_qp", lambda: box_qp_workload(args.box_bounds, args.box_eq)), ("pow", lambda: pow_workload(args.pow_cones, 3 * args.pow_cones)))
+    for name, make in works:
+        data, K, (x0, _, _) = make()
+        m, n = data["A"].shape
+        sv = scs.SCS(data, K, linear_solver=scs.LinearSolver.HIP_INDIRECT, verbose=False, eps_abs=1e-8, eps_rel=1e-8, max_iters=args.solve_iters)
+        sol = sv.solve_device(warm_start=False)
+        info = sol["info"]
+        rng = np.random.default_rng(1)
+        g = [torch.as_tensor(rng.standard_normal(k_)).cuda() for k_ in (n, m, m)]
+        call = lambda tol, cap: sv.adjoint_device(dx=g[0], dy=g[1], ds=g[2], tol=tol, max_iters=cap)
+        call(args.tol, args.lsqr_cap)  # (the first call allocates the scratch)
+        runs = [timed(lambda: call(args.tol, args.lsqr_cap), torch) for _ in range(args.reps)]
+        li = runs[-1][1]["info"]
+
+        def capped(cap):
+            rs = [timed(lambda: call(1e-300, cap), torch) for _ in range(args.reps)]
+            return float(np.median([r[0] for r in rs])), rs[-1][1]["info"]["iters"]
+        (t1, k1), (t2, k2) = capped(8), capped(48)
+        per_it = (t2 - t1) / max(k2 - k1, 1)
+        tk = sv._solver._time_dproj(reps=args.kernel_reps)
+        lines.append("%-7s m %d, n %d, nnz(A) %d | solve: %s, %d ADMM it, |x - x_built|_inf %.1e | adjoint to tol: %d LSQR it, stop %d, residual "
+                     "%.2e, %.2f ms | ms/LSQR it %.4f (caps %d, %d), fixed part %.3f ms" % (
+                         name, m, n, data["A"].nnz, info["status"], info["iter"], float(np.abs(sol["x"].cpu().numpy() - x0).max()), li["iters"],
+                         li["stop"], li["residual"], float(np.median([r[0] for r in runs])), per_it, k1, k2, t1 - k1 * per_it))
+        if tk["bsize"]:
+            lines.append("%-7s box cone of %d bounds: W apply one workgroup %.4f ms | two launches %.4f ms | a call uses the %s form | one "
+                         "projection (warm) %.4f ms" % (name, tk["bsize"] - 1, tk["box_apply_one_wg_ms"], tk["box_apply_two_launch_ms"],
+                                                        "two-launch" if tk["bsize"] > 16384 else "one-workgroup", tk["box_proj_ms"]))
+        if tk["pow_cones"]:
+            lines.append("%-7s %d power cones: W apply %.4f ms | preparation of W (once per call) %.4f ms | one projection %.4f ms" % (
+                name, tk["pow_cones"], tk["pow_apply_ms"], tk["pow_prep_ms"], tk["pow_proj_ms"]))
+        del sv, sol, g
+    if args.box_sizes:
+        lines.append("box W apply by size (same generator, %d equality rows; ADMM cap 50: the kernels' time does not depend on the iterate):"
+                     % args.box_eq)
+        for k in [int(v) for v in args.box_sizes.split(",")]:
+            data, K, _ = box_qp_workload(k, args.box_eq)
+            sv = scs.SCS(data, K, linear_solver=scs.LinearSolver.HIP_INDIRECT, verbose=False, eps_abs=1e-6, eps_rel=1e-6, max_iters=50)
+            sv.solve_device(warm_start=False)
+            tk = sv._solver._time_dproj(reps=args.kernel_reps)
+            lines.append("  %7d bounds: one workgroup %.4f ms | two launches %.4f ms | projection %.4f ms" % (
+                k, tk["box_apply_one_wg_ms"], tk["box_apply_two_launch_ms"], tk["box_proj_ms"]))
+            del sv
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="target_lp_soc,target_qp,config5_member,config5_sdp,config4_psd")
@@ -160,6 +279,12 @@ def main():
     ap.add_argument("--out", default=None, help="also write the table to this file")
     ap.add_argument("--matrix", action="store_true", help="the leg that times derivative_device with and without dA / dP")
     ap.add_argument("--parent-root", default=None, help="--matrix: a built checkout of the parent commit for the comparison of derivative(db, dc)")
+    ap.add_argument("--cones", action="store_true", help="the leg of the box and power derivative")
+    ap.add_argument("--box-bounds", type=int, default=60000)
+    ap.add_argument("--box-eq", type=int, default=200)
+    ap.add_argument("--pow-cones", type=int, default=4000)
+    ap.add_argument("--box-sizes", default="1000,4000,16000,60000,99999")
+    ap.add_argument("--kernel-reps", type=int, default=200)
     ap.add_argument("--child-derivative", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--root", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -167,6 +292,8 @@ def main():
         return matrix_child(args)
     if args.matrix:
         return matrix_leg(args)
+    if args.cones:
+        return cones_leg(args)
 
     import torch
     import scs
