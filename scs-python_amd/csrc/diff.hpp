@@ -23,7 +23,11 @@
 // The products go through launch_spmv with EpiStore (every layout finishes it: the split pass layout through k_epi_finish).
 //
 // Every kernel here, in lsqr.hpp, dproj.hpp and dproj_psd.hpp is a __device__ body d_X with its one-problem entry k_X; a batch of
-// workspaces is differentiated in lock step through the grouped entries of the same bodies (diff_batch.hpp).
+// workspaces is differentiated in lock step through the grouped entries of the same bodies (diff_batch.hpp).  Everything the two
+// paths must agree on to give the same bits is defined once, below the kernels: DiffLimits and diff_fill_info (options in, figures
+// out), diff_plan (the cone plan), DiffWiring (which scratch slot holds what, the operands and order of each product, which product
+// each LSQR half step consumes) and lsqr_drive (the chunk schedule and the extra half step at the cap).  diff_impl launches from
+// them; GroupDiff::run fills its tables from them.
 //
 // A call reads solx / soly / sols and the matrices, and writes the workspace's DiffScratch only (the eigen-decomposition of the PSD
 // blocks borrows a block of the pool for the call; the solve's psd_scratch is not touched).
@@ -164,7 +168,40 @@ struct DiffCall {
   double *out[4] = {nullptr, nullptr, nullptr, nullptr};      // adjoint: db, dc, dAx, dPx;  forward: dx, dy, ds
   const double *pert[2] = {nullptr, nullptr};                 // forward: dAx, dPx — perturbations of the matrix values (perturb.hpp)
   bool perturbs() const { return !adjoint && (pert[0] || pert[1]); }
+  // the arguments' names in a refusal and their lengths in doubles (what a host twin stages)
+  const char *in_name(int k) const {
+    static const char *const adj[3] = {"gx", "gy", "gs"}, *const fwd[3] = {"db", "dc", ""};
+    return (adjoint ? adj : fwd)[k];
+  }
+  const char *out_name(int k) const {
+    static const char *const adj[4] = {"db", "dc", "dAx", "dPx"}, *const fwd[4] = {"dx", "dy", "ds", ""};
+    return (adjoint ? adj : fwd)[k];
+  }
+  static const char *pert_name(int k) { return k == 0 ? "dAx" : "dPx"; }
+  long in_len(const ScsHipWork *w, int k) const { return adjoint ? (k == 0 ? w->n : w->m) : (k == 0 ? w->m : k == 1 ? w->n : 0); }
+  long out_len(const ScsHipWork *w, int k) const {
+    if (adjoint) return k == 0 ? w->m : k == 1 ? w->n : pert_len(w, k - 2);
+    return k == 0 ? w->n : k < 3 ? w->m : 0;
+  }
+  static long pert_len(const ScsHipWork *w, int k) { return k == 0 ? w->mats->a_nnz_in : w->mats->p_nnz_in; }
 };
+
+// the LSQR tolerance and iteration cap of a call over N = n + m unknowns
+struct DiffLimits {
+  double tol;
+  long cap;
+  DiffLimits(const ScsHipDiffOpts *o, long N) : tol(o && o->tol > 0. ? o->tol : 1e-8), cap(o && o->max_iters > 0 ? (long)o->max_iters : 4 * N) {}
+};
+// what a call reports, from the flag and state blocks LSQR left (info == nullptr: nothing)
+static void diff_fill_info(ScsHipDiffInfo *info, const int *hfl, const double *hst, long cap, double ms) {
+  if (!info) return;
+  info->iters = (scs_int)std::min((long)hfl[LF_ITERS], cap);
+  info->stop = hfl[LF_STOP] ? hfl[LF_STOP] : 3;
+  info->residual = hst[L_BNORM] > 0. ? hst[L_RNORM] / hst[L_BNORM] : 0.;
+  const double den = hst[L_ANORM] * hst[L_RNORM];
+  info->normal_residual = den > 0. ? hst[L_ARNORM] / den : 0.;
+  info->time_ms = ms;
+}
 
 static void diff_alloc(ScsHipWork *w) {
   DiffScratch &d = w->diff;
@@ -210,14 +247,117 @@ static void diff_build_tri(ScsHipWork *w) {
   d.tri_ready = true;
 }
 
-// The caller holds w->mtx and the scratch turn, has selected the device and refused bad arguments.  All pointers are device pointers.
+// the cone plan of a call: the workspace's cone tables over its scratch.  psd.tmp_m and the box tmp inside it lie in dW, which is free
+// until the right-hand side is formed.
+static DprojPlan diff_plan(ScsHipWork *w) {
+  DiffScratch &d = w->diff;
+  DprojPlan plan;
+  plan.z = w->cone.z; plan.l = w->cone.l; plan.n_soc = w->n_soc; plan.n_soc_big = w->n_soc_big; plan.G = w->soc_G;
+  plan.off = w->soc_off.p; plan.dim = w->soc_dim.p; plan.big = w->soc_big.p;
+  plan.vh = d.vhat.p; plan.cinfo = d.cinfo.p; plan.m = w->m;
+  plan.psd = d.psd.plan;
+  plan.psd.tmp_m = d.dW.p;
+  dproj_plan_box_pow(plan, w, d.box.p, d.box_ticket.p, d.sym3.p, d.dW.p);
+  return plan;
+}
+
+// One product of the operator on one workspace, J q or J' l: the apply of W, the three SpMVs (each with its input and where it stores)
+// and the combination the LSQR kernel that consumes the product reads.  The pieces go in the order
+//     J q:   apply, A (Ar), A' (At), P (Pf)             J' l:  A (Ar), apply (it reads A l1), A' (At), P (Pf)
+// (transposed says which); a workspace without P skips pf.
+struct DiffProduct {
+  struct Spmv {
+    const double *in;
+    EpiStore out;
+  };
+  bool transposed;
+  DprojIo io;
+  Spmv ar, at, pf;
+  LsqrProd read;
+};
+
+// Which buffer of a workspace's DiffScratch holds what during one call: the one place where slots are aliased and products are wired.
+// Both call paths read it: diff_impl launches from it, GroupDiff::run (diff_batch.hpp) fills its tables from it.
+struct DiffWiring {
+  // adjoint right-hand side: k_adj_in leaves gx^ in uh[0..n), gy^ in gyh = x[n..) and gs^ in gsh = tA (both free until LSQR starts);
+  // the two applies leave W gs^ in dW and (W - I) gy^ in dWmI, which k_lsqr_start adds into uh[n..) (start_add)
+  double *gyh = nullptr, *gsh = nullptr;
+  DprojIo rhs_gs{}, rhs_gy{};
+  const double *start_add[2] = {nullptr, nullptr};
+  // forward right-hand side: the caller's (dc ; db), or the effective pair in eff when the call perturbs A or P (eff_c != nullptr:
+  // (dc + dP x + dA' y ; db - dA x), perturb.hpp, whose products pass through tAt, tP, tA — free until the LSQR products)
+  const double *dc_in = nullptr, *db_in = nullptr;
+  double *eff_c = nullptr, *eff_b = nullptr;
+  // M = J' (adjoint) or J (forward).  pv = M' uh, which step_v consumes;  pu = M vh, which step_u consumes
+  DiffProduct pv{}, pu{};
+  // after the loop.  adjoint: dL/dc and dL/db in tP and tA (free now);  forward: the apply that turns dv^ = x[n..) into dW, dWmI
+  double *dc = nullptr, *db = nullptr;
+  DprojIo fin{};
+};
+static DiffWiring diff_wiring(ScsHipWork *w, const DiffCall &a) {
+  DiffScratch &d = w->diff;
+  const int n = w->n;
+  const double *tP = w->has_P ? d.tP.p : nullptr;
+  auto J = [&](const double *q) {
+    return DiffProduct{false, DprojIo{q + n, nullptr, d.dW.p, d.dWmI.p}, {q, EpiStore{d.tA.p, 0}}, {d.dWmI.p, EpiStore{d.tAt.p, 0}},
+                       {q, EpiStore{d.tP.p, 0}}, LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 0}};
+  };
+  auto Jt = [&](const double *l) {
+    return DiffProduct{true, DprojIo{d.tA.p, l + n, d.dW.p, nullptr}, {l, EpiStore{d.tA.p, 0}}, {l + n, EpiStore{d.tAt.p, 0}},
+                       {l, EpiStore{d.tP.p, 0}}, LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 1}};
+  };
+  DiffWiring wr;
+  if (a.adjoint) {
+    wr.gyh = d.x.p + n; wr.gsh = d.tA.p;
+    wr.rhs_gs = DprojIo{wr.gsh, nullptr, d.dW.p, nullptr};
+    wr.rhs_gy = DprojIo{wr.gyh, nullptr, nullptr, d.dWmI.p};
+    wr.start_add[0] = d.dW.p; wr.start_add[1] = d.dWmI.p;
+    wr.pv = J(d.uh.p); wr.pu = Jt(d.vh.p);
+    wr.dc = d.tP.p; wr.db = d.tA.p;
+  } else {
+    wr.db_in = a.in[0]; wr.dc_in = a.in[1];
+    if (a.perturbs()) {
+      wr.dc_in = wr.eff_c = d.eff.p;
+      wr.db_in = wr.eff_b = d.eff.p + n;
+    }
+    wr.pv = Jt(d.uh.p); wr.pu = J(d.vh.p);
+    wr.fin = DprojIo{d.x.p + n, nullptr, d.dW.p, d.dWmI.p};
+  }
+  return wr;
+}
+
+// The host control of LSQR (lsqr.hpp): queue chunks of iterations between looks at the flags.  step_u(k) / step_v(k) queue the product
+// and the kernel of that half step; finished() reads the flags back and says whether nothing is left to iterate.
+template <class StepU, class StepV, class Finished> static void lsqr_drive(long cap, StepU &&step_u, StepV &&step_v, Finished &&finished) {
+  step_v(0);
+  long k = 0;  // iterations enqueued
+  long chunk = 8;
+  bool done;
+  while (true) {
+    const long upto = std::min(cap, k + chunk);
+    while (k < upto) {
+      ++k;
+      step_u((int)k);
+      step_v((int)k);
+    }
+    done = finished();
+    if (done || k >= cap) break;
+    chunk = std::max(4L, std::min(k / 2, 64L));
+  }
+  if (!done) {  // the cap: the tests (and the figures of info) for x_cap need alpha_{cap+1}
+    step_u((int)(k + 1));
+    finished();
+  }
+}
+
+// One workspace.  The caller holds w->mtx and the scratch turn, has selected the device and refused bad arguments (diff_check).  All
+// pointers are device pointers.
 static void diff_impl(ScsHipWork *w, const DiffCall &a, const ScsHipDiffOpts *o, ScsHipDiffInfo *info) {
   const double t0 = now_ms();
   hipStream_t s = w->stream;
   const int n = w->n, m = w->m;
   const long N = (long)n + m;
-  const double tol = o && o->tol > 0. ? o->tol : 1e-8;
-  const long cap = o && o->max_iters > 0 ? (long)o->max_iters : 4 * N;
+  const DiffLimits lim(o, N);
   diff_alloc(w);
   if (a.adjoint && a.out[3]) diff_build_tri(w);
   if (a.perturbs()) pert_alloc(w, a.pert[0] != nullptr, a.pert[1] != nullptr, "scs_hip_derivative_full");
@@ -227,122 +367,70 @@ static void diff_impl(ScsHipWork *w, const DiffCall &a, const ScsHipDiffOpts *o,
   const int nbN = vec_blocks(N);
   const dim3 gN(nbN), bV(kVecThreads);
   const int *done = d.fl.p + LF_DONE;
+  const DiffWiring wr = diff_wiring(w, a);
 
   // ---- the fixed point and the cone records ----
   hipLaunchKernelGGL(k_dproj_vhat, dim3(vec_blocks(m)), bV, 0, s, (const double *)w->sols.p, (const double *)w->soly.p, D, sigma, m, d.vhat.p);
-  DprojPlan plan;
-  plan.z = w->cone.z; plan.l = w->cone.l; plan.n_soc = w->n_soc; plan.n_soc_big = w->n_soc_big; plan.G = w->soc_G;
-  plan.off = w->soc_off.p; plan.dim = w->soc_dim.p; plan.big = w->soc_big.p;
-  plan.vh = d.vhat.p; plan.cinfo = d.cinfo.p; plan.m = m;
-  plan.psd = d.psd.plan;
-  plan.psd.tmp_m = d.dW.p;  // (free until the right-hand side is formed)
-  dproj_plan_box_pow(plan, w, d.box.p, d.box_ticket.p, d.sym3.p, d.dW.p);
+  const DprojPlan plan = diff_plan(w);
   launch_dproj_prep(plan, s);
 
   // ---- right-hand side into uh, x = w = 0 ----
   if (a.adjoint) {
-    double *gyh = d.x.p + n, *gsh = d.tA.p;
-    hipLaunchKernelGGL(k_adj_in, gN, bV, 0, s, a.in[0], a.in[1], a.in[2], D, E, sigma, n, m, d.uh.p, gyh, gsh);
-    launch_dproj(plan, DprojIo{gsh, nullptr, d.dW.p, nullptr}, nullptr, s);
-    launch_dproj(plan, DprojIo{gyh, nullptr, nullptr, d.dWmI.p}, nullptr, s);
-    hipLaunchKernelGGL(k_lsqr_start, gN, bV, 0, s, d.uh.p, (const double *)d.dW.p, (const double *)d.dWmI.p, n, N, d.x.p, d.w.p, d.partU.p, d.st.p,
-                       d.fl.p);
+    hipLaunchKernelGGL(k_adj_in, gN, bV, 0, s, a.in[0], a.in[1], a.in[2], D, E, sigma, n, m, d.uh.p, wr.gyh, wr.gsh);
+    launch_dproj(plan, wr.rhs_gs, nullptr, s);
+    launch_dproj(plan, wr.rhs_gy, nullptr, s);
   } else {
-    const double *db = a.in[0], *dc = a.in[1];
-    if (a.perturbs()) {  // (dc_eff ; db_eff) = (dc + dP x + dA' y ; db - dA x) in place of (dc ; db): tAt, tP, tA are free until the products
-      pert_launch(w, a.pert[0], a.pert[1], dc, db, -1.0, d.eff.p, d.eff.p + n, s);
-      dc = d.eff.p;
-      db = d.eff.p + n;
-    }
-    hipLaunchKernelGGL(k_fwd_in, gN, bV, 0, s, db, dc, D, E, sigma, n, m, d.uh.p);
-    hipLaunchKernelGGL(k_lsqr_start, gN, bV, 0, s, d.uh.p, (const double *)nullptr, (const double *)nullptr, n, N, d.x.p, d.w.p, d.partU.p, d.st.p,
-                       d.fl.p);
+    if (wr.eff_c) pert_launch(w, a.pert[0], a.pert[1], a.in[1], a.in[0], -1.0, wr.eff_c, wr.eff_b, s);
+    hipLaunchKernelGGL(k_fwd_in, gN, bV, 0, s, wr.db_in, wr.dc_in, D, E, sigma, n, m, d.uh.p);
   }
+  hipLaunchKernelGGL(k_lsqr_start, gN, bV, 0, s, d.uh.p, wr.start_add[0], wr.start_add[1], n, N, d.x.p, d.w.p, d.partU.p, d.st.p, d.fl.p);
 
-  // ---- the two products (results in tAt, tP, tA, dW) ----
-  const double *tP = w->has_P ? d.tP.p : nullptr;
-  auto prod_J = [&](const double *q) {
-    launch_dproj(plan, DprojIo{q + n, nullptr, d.dW.p, d.dWmI.p}, done, s);
-    launch_spmv(w->Ar.view(), q, EpiStore{d.tA.p, 0}, done, s);
-    launch_spmv(w->At.view(), d.dWmI.p, EpiStore{d.tAt.p, 0}, done, s);
-    if (w->has_P) launch_spmv(w->Pf.view(), q, EpiStore{d.tP.p, 0}, done, s);
-    return LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 0};
+  // ---- LSQR: the products leave their results in tAt, tP, tA, dW ----
+  auto product = [&](const DiffProduct &p) {
+    if (!p.transposed) launch_dproj(plan, p.io, done, s);
+    launch_spmv(w->Ar.view(), p.ar.in, p.ar.out, done, s);
+    if (p.transposed) launch_dproj(plan, p.io, done, s);
+    launch_spmv(w->At.view(), p.at.in, p.at.out, done, s);
+    if (w->has_P) launch_spmv(w->Pf.view(), p.pf.in, p.pf.out, done, s);
   };
-  auto prod_Jt = [&](const double *l) {
-    launch_spmv(w->Ar.view(), l, EpiStore{d.tA.p, 0}, done, s);
-    launch_dproj(plan, DprojIo{d.tA.p, l + n, d.dW.p, nullptr}, done, s);
-    launch_spmv(w->At.view(), l + n, EpiStore{d.tAt.p, 0}, done, s);
-    if (w->has_P) launch_spmv(w->Pf.view(), l, EpiStore{d.tP.p, 0}, done, s);
-    return LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 1};
-  };
-  // M = J' (adjoint) or J (forward): M v and M' u
-  auto prod_M = [&](const double *v) { return a.adjoint ? prod_Jt(v) : prod_J(v); };
-  auto prod_Mt = [&](const double *u) { return a.adjoint ? prod_J(u) : prod_Jt(u); };
   auto step_v = [&](int k) {
-    const LsqrProd tv = prod_Mt(d.uh.p);
-    hipLaunchKernelGGL(k_lsqr_v, gN, bV, 0, s, k, tv, d.vh.p, (const double *)d.w.p, d.x.p, n, N, (const double *)d.partU.p, nbN, d.partV.p, d.partX.p,
-                       d.st.p, d.fl.p);
+    product(wr.pv);
+    hipLaunchKernelGGL(k_lsqr_v, gN, bV, 0, s, k, wr.pv.read, d.vh.p, (const double *)d.w.p, d.x.p, n, N, (const double *)d.partU.p, nbN, d.partV.p,
+                       d.partX.p, d.st.p, d.fl.p);
   };
   auto step_u = [&](int k) {
-    const LsqrProd tu = prod_M(d.vh.p);
-    hipLaunchKernelGGL(k_lsqr_u, gN, bV, 0, s, k, tu, d.uh.p, (const double *)d.vh.p, d.w.p, n, N, (const double *)d.partV.p, (const double *)d.partX.p,
-                       nbN, d.partU.p, d.st.p, d.fl.p, tol);
+    product(wr.pu);
+    hipLaunchKernelGGL(k_lsqr_u, gN, bV, 0, s, k, wr.pu.read, d.uh.p, (const double *)d.vh.p, d.w.p, n, N, (const double *)d.partV.p,
+                       (const double *)d.partX.p, nbN, d.partU.p, d.st.p, d.fl.p, lim.tol);
   };
   int hfl[LF_COUNT] = {0, 0, 0, 0};
-  auto read_flags = [&] {
+  lsqr_drive(lim.cap, step_u, step_v, [&] {
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(hfl, d.fl.p, sizeof(hfl), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-  };
-
-  // ---- LSQR: chunks of iterations between looks at the flag block ----
-  step_v(0);
-  long k = 0;  // iterations enqueued
-  long chunk = 8;
-  while (true) {
-    const long upto = std::min(cap, k + chunk);
-    while (k < upto) {
-      ++k;
-      step_u((int)k);
-      step_v((int)k);
-    }
-    read_flags();
-    if (hfl[LF_DONE] || k >= cap) break;
-    chunk = std::max(4L, std::min(k / 2, 64L));
-  }
-  if (!hfl[LF_DONE]) {  // the cap: the tests (and the figures of info) for x_cap need alpha_{cap+1}
-    step_u((int)(k + 1));
-    read_flags();
-  }
+    return hfl[LF_DONE] != 0;
+  });
   double hst[L_COUNT];
   HIP_CHECK(hipMemcpyAsync(hst, d.st.p, sizeof(hst), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
 
   // ---- results ----
   if (a.adjoint) {
-    double *dc = d.tP.p, *db = d.tA.p;  // (free now)
-    hipLaunchKernelGGL(k_adj_out, gN, bV, 0, s, (const double *)d.x.p, D, E, sigma, n, m, dc, db);
-    if (a.out[0]) HIP_CHECK(hipMemcpyAsync(a.out[0], db, sizeof(double) * m, hipMemcpyDeviceToDevice, s));
-    if (a.out[1]) HIP_CHECK(hipMemcpyAsync(a.out[1], dc, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(k_adj_out, gN, bV, 0, s, (const double *)d.x.p, D, E, sigma, n, m, wr.dc, wr.db);
+    if (a.out[0]) HIP_CHECK(hipMemcpyAsync(a.out[0], wr.db, sizeof(double) * m, hipMemcpyDeviceToDevice, s));
+    if (a.out[1]) HIP_CHECK(hipMemcpyAsync(a.out[1], wr.dc, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
     if (a.out[2] && w->At.nnz > 0)
       hipLaunchKernelGGL(k_grad_a, dim3(vec_blocks((long)w->At.nnz)), bV, 0, s, (const int *)w->At.rowptr.p, (const int *)w->At.col.p, w->At.rows,
-                         (long)w->At.nnz, (const double *)w->solx.p, (const double *)w->soly.p, (const double *)dc, (const double *)db, a.out[2]);
+                         (long)w->At.nnz, (const double *)w->solx.p, (const double *)w->soly.p, (const double *)wr.dc, (const double *)wr.db, a.out[2]);
     if (a.out[3] && w->Pf.nnz > 0)
       hipLaunchKernelGGL(k_grad_p, dim3(vec_blocks((long)w->Pf.nnz)), bV, 0, s, (const int *)w->Pf.rowptr.p, (const int *)w->Pf.col.p, n, (long)w->Pf.nnz,
-                         (const int *)d.tri_up.p, (const double *)w->solx.p, (const double *)dc, a.out[3]);
+                         (const int *)d.tri_up.p, (const double *)w->solx.p, (const double *)wr.dc, a.out[3]);
   } else {
-    launch_dproj(plan, DprojIo{d.x.p + n, nullptr, d.dW.p, d.dWmI.p}, nullptr, s);
+    launch_dproj(plan, wr.fin, nullptr, s);
     hipLaunchKernelGGL(k_fwd_out, gN, bV, 0, s, (const double *)d.x.p, (const double *)d.dW.p, (const double *)d.dWmI.p, D, E, sigma, n, m, a.out[0],
                        a.out[1], a.out[2]);
   }
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(s));
-  if (info) {
-    info->iters = (scs_int)std::min((long)hfl[LF_ITERS], cap);
-    info->stop = hfl[LF_STOP] ? hfl[LF_STOP] : 3;
-    info->residual = hst[L_BNORM] > 0. ? hst[L_RNORM] / hst[L_BNORM] : 0.;
-    const double den = hst[L_ANORM] * hst[L_RNORM];
-    info->normal_residual = den > 0. ? hst[L_ARNORM] / den : 0.;
-    info->time_ms = now_ms() - t0;
-  }
+  diff_fill_info(info, hfl, hst, lim.cap, now_ms() - t0);
 }

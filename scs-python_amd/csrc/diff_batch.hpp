@@ -8,11 +8,14 @@
 // record).  Same code, same block decomposition, same partial sums => every member's outputs, iteration count, stopping rule and
 // residual figures are bit-identical to a call of its own (tests/test_adjoint_batch_gpu.py).
 //
-// GroupDiff::run is diff_impl applied to every member.  The members share the iteration index k (a launch-level argument of the two
-// LSQR kernels: k_grouped_k); a member that has converged drops out of the member list, and until the host has seen its flag its
-// kernels return at once on its own done flag.  Per chunk of iterations ONE gather launch and ONE copy of G x LF_COUNT ints cross the
-// host.  Each member keeps its own DiffScratch; the group owns the argument tables, the member lists and the two gathered blocks, and
-// gives its device blocks back to the block pool when the call ends.
+// GroupDiff::run and diff_impl are the two ways to issue one call, and they read the same definitions (diff.hpp): the limits
+// (DiffLimits), the cone plan (diff_plan), the buffer assignments and the order of a product's pieces (DiffWiring, DiffProduct), the
+// host control of the iteration (lsqr_drive) and the reported figures (diff_fill_info).  What differs is only that diff_impl launches
+// k_X with a member's arguments where run writes them into the member's record of the table of d_X.  The members share the iteration
+// index k (a launch-level argument of the two LSQR kernels: k_grouped_k); a member that has converged drops out of the member list,
+// and until the host has seen its flag its kernels return at once on its own done flag.  Per chunk of iterations ONE gather launch
+// and ONE copy of G x LF_COUNT ints cross the host.  Each member keeps its own DiffScratch; the group owns the argument tables, the
+// member lists and the two gathered blocks, and gives its device blocks back to the block pool when the call ends.
 #pragma once
 
 namespace scship {
@@ -70,11 +73,18 @@ struct GroupDiff {
       if (sym3.used) sym3.set(g, io, (const double *)p.sym3.W, p.sym3.count, p.sym3.off, done);
     }
   };
-  // one product J q or J' l (diff.hpp prod_J / prod_Jt) over the group
+  // one product of the operator over the group: every member's DiffProduct (diff.hpp), which also says in which order the pieces go
   struct ProdTabs {
     DprojTabs dp;
     SCS_GTABLE(kSpmvThreads, d_spmv_stream<EpiStore>) ar, at, pf;
-    bool transposed = false;  // J': A l first, then the apply
+    bool transposed = false;
+    void set(int g, const ScsHipWork *w, const DprojPlan &plan, const DiffProduct &p, const int *done) {
+      transposed = p.transposed;
+      dp.set(g, plan, p.io, done);
+      ar.set(g, csr_of(w->Ar), p.ar.in, p.ar.out, done, nullptr);
+      at.set(g, csr_of(w->At), p.at.in, p.at.out, done, nullptr);
+      if (w->has_P) pf.set(g, csr_of(w->Pf), p.pf.in, p.pf.out, done, nullptr);
+    }
   };
 
   SCS_GTABLE(kVecThreads, d_dproj_vhat) t_vhat;
@@ -161,18 +171,12 @@ struct GroupDiff {
     go(d.soc, list, count);
     go(d.soc_big, list, count);
   }
-  void go_prod(const ProdTabs &p, const int *list, int count) {  // (the orders of prod_J and prod_Jt)
-    if (!p.transposed) {
-      go_dproj(p.dp, list, count);
-      go(p.ar, list, count);
-      go(p.at, list, count);
-      go(p.pf, list, count);
-    } else {
-      go(p.ar, list, count);
-      go_dproj(p.dp, list, count);
-      go(p.at, list, count);
-      go(p.pf, list, count);
-    }
+  void go_prod(const ProdTabs &p, const int *list, int count) {  // (the order of a DiffProduct)
+    if (!p.transposed) go_dproj(p.dp, list, count);
+    go(p.ar, list, count);
+    if (p.transposed) go_dproj(p.dp, list, count);
+    go(p.at, list, count);
+    go(p.pf, list, count);
   }
   void sync() {
     HIP_CHECK(hipGetLastError());  // (launches are not checked one by one)
@@ -184,33 +188,14 @@ struct GroupDiff {
     return V;
   }
 
-  // the records of one product for member g: q (or l) is the LSQR vector it reads
-  void set_prod(ProdTabs &p, int g, bool jt, const double *q) {
-    ScsHipWork *w = W[(size_t)g];
-    DiffScratch &d = w->diff;
-    const int *done = d.fl.p + LF_DONE;
-    p.transposed = jt;
-    if (!jt) {
-      p.dp.set(g, plans[(size_t)g], DprojIo{q + n, nullptr, d.dW.p, d.dWmI.p}, done);
-      p.ar.set(g, csr_of(w->Ar), q, EpiStore{d.tA.p, 0}, done, nullptr);
-      p.at.set(g, csr_of(w->At), d.dWmI.p, EpiStore{d.tAt.p, 0}, done, nullptr);
-    } else {
-      p.ar.set(g, csr_of(w->Ar), q, EpiStore{d.tA.p, 0}, done, nullptr);
-      p.dp.set(g, plans[(size_t)g], DprojIo{d.tA.p, q + n, d.dW.p, nullptr}, done);
-      p.at.set(g, csr_of(w->At), q + n, EpiStore{d.tAt.p, 0}, done, nullptr);
-    }
-    if (has_P) p.pf.set(g, csr_of(w->Pf), q, EpiStore{d.tP.p, 0}, done, nullptr);
-  }
-
-  // The caller holds every member's mutex, has selected the device, refused bad arguments and run diff_alloc / diff_build_tri for
-  // every member.  All pointers are device pointers.
+  // The caller holds every member's mutex, has selected the device, refused bad arguments (diff_check) and run diff_alloc /
+  // diff_build_tri / pert_alloc for every member.  All pointers are device pointers.
   void run(const ScsHipDiffOpts *o) {
     const double t0 = now_ms();
     G = (int)W.size();
     ScsHipWork *w0 = W[0];
     n = w0->n; m = w0->m; N = (long)n + m; has_P = w0->has_P;
-    const double tol = o && o->tol > 0. ? o->tol : 1e-8;
-    const long cap = o && o->max_iters > 0 ? (long)o->max_iters : 4 * N;
+    const DiffLimits lim(o, N);
     const int nbN = vec_blocks(N);
     const bool want_dA = adjoint && calls[0].out[2], want_dP = adjoint && calls[0].out[3];
     ArenaScope no_arena(nullptr);
@@ -226,19 +211,9 @@ struct GroupDiff {
     const int *all_d = lists_d.p;
     int *active_d = lists_d.p + G, *active_h = lists_h + G;
 
-    // ---- the members' cone plans (as diff_impl forms them) ----
-    plans.resize((size_t)G);
-    for (int g = 0; g < G; ++g) {
-      ScsHipWork *w = W[(size_t)g];
-      DiffScratch &d = w->diff;
-      DprojPlan &plan = plans[(size_t)g];
-      plan.z = w->cone.z; plan.l = w->cone.l; plan.n_soc = w->n_soc; plan.n_soc_big = w->n_soc_big; plan.G = w->soc_G;
-      plan.off = w->soc_off.p; plan.dim = w->soc_dim.p; plan.big = w->soc_big.p;
-      plan.vh = d.vhat.p; plan.cinfo = d.cinfo.p; plan.m = m;
-      plan.psd = d.psd.plan;
-      plan.psd.tmp_m = d.dW.p;
-      dproj_plan_box_pow(plan, w, d.box.p, d.box_ticket.p, d.sym3.p, d.dW.p);
-    }
+    // ---- the members' cone plans ----
+    plans.clear();
+    for (ScsHipWork *w : W) plans.push_back(diff_plan(w));
     const DprojPlan &p0 = plans[0];
     const size_t SG = (size_t)G;
 
@@ -309,60 +284,48 @@ struct GroupDiff {
                       (const int *)nullptr, plan.psd.tol2, refine_off, 0);
         t_psd_gather.set(g, plan.psd, (const double *)scr, plan.vh);
       }
-      const double *tP = has_P ? d.tP.p : nullptr;
+      const DiffWiring wr = diff_wiring(w, a);
+      const int *done = d.fl.p + LF_DONE;
+      // right-hand side and results: the kernels of the call's direction
       if (adjoint) {
-        double *gyh = d.x.p + n, *gsh = d.tA.p;
-        t_adj_in.set(g, a.in[0], a.in[1], a.in[2], D, E, sigma, n, m, d.uh.p, gyh, gsh);
-        rhs1.set(g, plan, DprojIo{gsh, nullptr, d.dW.p, nullptr}, nullptr);
-        rhs2.set(g, plan, DprojIo{gyh, nullptr, nullptr, d.dWmI.p}, nullptr);
-        t_start.set(g, d.uh.p, (const double *)d.dW.p, (const double *)d.dWmI.p, n, N, d.x.p, d.w.p, d.partU.p, d.st.p, d.fl.p);
-        // M = J': step_v consumes M' uh = J uh, step_u consumes M vh = J' vh
-        set_prod(pv, g, /*jt=*/false, d.uh.p);
-        set_prod(pu, g, /*jt=*/true, d.vh.p);
-        t_lsqr_v.set(g, LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 0}, d.vh.p, (const double *)d.w.p, d.x.p, n, N, (const double *)d.partU.p, nbN,
-                     d.partV.p, d.partX.p, d.st.p, d.fl.p);
-        t_lsqr_u.set(g, LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 1}, d.uh.p, (const double *)d.vh.p, d.w.p, n, N, (const double *)d.partV.p,
-                     (const double *)d.partX.p, nbN, d.partU.p, d.st.p, d.fl.p, tol);
-        double *dc = d.tP.p, *db = d.tA.p;  // (free after the loop)
-        t_adj_out.set(g, (const double *)d.x.p, D, E, sigma, n, m, dc, db);
-        t_copy_out0.set(g, (const double *)db, a.out[0], a.out[0] ? (long)m : 0L);
-        t_copy_out1.set(g, (const double *)dc, a.out[1], a.out[1] ? (long)n : 0L);
+        t_adj_in.set(g, a.in[0], a.in[1], a.in[2], D, E, sigma, n, m, d.uh.p, wr.gyh, wr.gsh);
+        rhs1.set(g, plan, wr.rhs_gs, nullptr);
+        rhs2.set(g, plan, wr.rhs_gy, nullptr);
+        t_adj_out.set(g, (const double *)d.x.p, D, E, sigma, n, m, wr.dc, wr.db);
+        t_copy_out0.set(g, (const double *)wr.db, a.out[0], a.out[0] ? (long)m : 0L);
+        t_copy_out1.set(g, (const double *)wr.dc, a.out[1], a.out[1] ? (long)n : 0L);
         if (want_dA) {
           t_grad_a.set(g, (const int *)w->At.rowptr.p, (const int *)w->At.col.p, w->At.rows, (long)w->At.nnz, (const double *)w->solx.p,
-                       (const double *)w->soly.p, (const double *)dc, (const double *)db, a.out[2]);
+                       (const double *)w->soly.p, (const double *)wr.dc, (const double *)wr.db, a.out[2]);
           gx_ga = std::max(gx_ga, vec_blocks((long)w->At.nnz));
         }
         if (want_dP) {
           t_grad_p.set(g, (const int *)w->Pf.rowptr.p, (const int *)w->Pf.col.p, n, (long)w->Pf.nnz, (const int *)d.tri_up.p,
-                       (const double *)w->solx.p, (const double *)dc, a.out[3]);
+                       (const double *)w->solx.p, (const double *)wr.dc, a.out[3]);
           gx_gp = std::max(gx_gp, vec_blocks((long)w->Pf.nnz));
         }
       } else {
-        const double *db = a.in[0], *dc = a.in[1];
-        if (a.perturbs()) {  // (as diff_impl: the effective right-hand side in place of the caller's)
+        if (wr.eff_c) {  // the launches of pert_launch (perturb.hpp)
           PertProduct pr[3];
           const int cnt = pert_products(w, a.pert[0], a.pert[1], pr);
           for (int k = 0; k < cnt; ++k) {
             t_pert[k].set(g, pr[k].rp, pr[k].ci, pr[k].map, pr[k].val, pr[k].vec, pr[k].rows, pr[k].lg, pr[k].out);
             t_pert[k].gx = std::max(t_pert[k].gx, pr[k].blocks());
           }
-          t_pert_eff.set(g, dc, db, a.pert[1] ? (const double *)d.tP.p : nullptr, a.pert[0] ? (const double *)d.tAt.p : nullptr,
-                         a.pert[0] ? (const double *)d.tA.p : nullptr, -1.0, n, m, d.eff.p, d.eff.p + n);
-          dc = d.eff.p;
-          db = d.eff.p + n;
+          t_pert_eff.set(g, a.in[1], a.in[0], a.pert[1] ? (const double *)d.tP.p : nullptr, a.pert[0] ? (const double *)d.tAt.p : nullptr,
+                         a.pert[0] ? (const double *)d.tA.p : nullptr, -1.0, n, m, wr.eff_c, wr.eff_b);
         }
-        t_fwd_in.set(g, db, dc, D, E, sigma, n, m, d.uh.p);
-        t_start.set(g, d.uh.p, (const double *)nullptr, (const double *)nullptr, n, N, d.x.p, d.w.p, d.partU.p, d.st.p, d.fl.p);
-        // M = J: step_v consumes J' uh, step_u consumes J vh
-        set_prod(pv, g, /*jt=*/true, d.uh.p);
-        set_prod(pu, g, /*jt=*/false, d.vh.p);
-        t_lsqr_v.set(g, LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 1}, d.vh.p, (const double *)d.w.p, d.x.p, n, N, (const double *)d.partU.p, nbN,
-                     d.partV.p, d.partX.p, d.st.p, d.fl.p);
-        t_lsqr_u.set(g, LsqrProd{d.tAt.p, tP, d.tA.p, d.dW.p, 0}, d.uh.p, (const double *)d.vh.p, d.w.p, n, N, (const double *)d.partV.p,
-                     (const double *)d.partX.p, nbN, d.partU.p, d.st.p, d.fl.p, tol);
-        rhs1.set(g, plan, DprojIo{d.x.p + n, nullptr, d.dW.p, d.dWmI.p}, nullptr);
+        t_fwd_in.set(g, wr.db_in, wr.dc_in, D, E, sigma, n, m, d.uh.p);
+        rhs1.set(g, plan, wr.fin, nullptr);
         t_fwd_out.set(g, (const double *)d.x.p, (const double *)d.dW.p, (const double *)d.dWmI.p, D, E, sigma, n, m, a.out[0], a.out[1], a.out[2]);
       }
+      // LSQR: the same records whatever the direction, over the wiring's two products
+      t_start.set(g, d.uh.p, wr.start_add[0], wr.start_add[1], n, N, d.x.p, d.w.p, d.partU.p, d.st.p, d.fl.p);
+      pv.set(g, w, plan, wr.pv, done);
+      pu.set(g, w, plan, wr.pu, done);
+      t_lsqr_v.set(g, wr.pv.read, d.vh.p, (const double *)d.w.p, d.x.p, n, N, (const double *)d.partU.p, nbN, d.partV.p, d.partX.p, d.st.p, d.fl.p);
+      t_lsqr_u.set(g, wr.pu.read, d.uh.p, (const double *)d.vh.p, d.w.p, n, N, (const double *)d.partV.p, (const double *)d.partX.p, nbN,
+                   d.partU.p, d.st.p, d.fl.p, lim.tol);
       t_gather_fl.set(g, (const int *)d.fl.p, flags_d.p + (size_t)g * LF_COUNT, (int)LF_COUNT);
       t_gather_st.set(g, (const double *)d.st.p, st_d.p + (size_t)g * L_COUNT, (long)L_COUNT);
     }
@@ -403,40 +366,26 @@ struct GroupDiff {
 
     // ---- LSQR: chunks of iterations between looks at the gathered flags ----
     int na = G;  // members of the active list
+    bool list_changed = false;  // the pinned active list was compacted: the device's copy follows before the next step
     auto step_v = [&](int k) { go_prod(pv, active_d, na); go_k(t_lsqr_v, active_d, na, k); };
-    auto step_u = [&](int k) { go_prod(pu, active_d, na); go_k(t_lsqr_u, active_d, na, k); };
-    auto read_flags = [&] {  // every member's flags (a finished member's block no longer changes)
+    auto step_u = [&](int k) {  // (the first launches after every look at the flags)
+      if (list_changed) HIP_CHECK(hipMemcpyAsync(active_d, active_h, sizeof(int) * (size_t)na, hipMemcpyHostToDevice, s));
+      list_changed = false;
+      go_prod(pu, active_d, na);
+      go_k(t_lsqr_u, active_d, na, k);
+    };
+    lsqr_drive(lim.cap, step_u, step_v, [&] {
+      // every member's flags (a finished member's block no longer changes); finished members leave the active list
       go(t_gather_fl, all_d, G);
       HIP_CHECK(hipMemcpyAsync(flags_h, flags_d.p, sizeof(int) * LF_COUNT * G, hipMemcpyDeviceToHost, s));
-      sync();
-    };
-    auto drop_finished = [&] {  // (after a synchronisation: the pinned list may be rewritten)
+      sync();  // (the pinned list may be rewritten)
       int keep = 0;
       for (int i = 0; i < na; ++i)
         if (!flags_h[(size_t)active_h[i] * LF_COUNT + LF_DONE]) active_h[keep++] = active_h[i];
-      if (keep == na) return;
+      list_changed = list_changed || keep != na;
       na = keep;
-      if (na > 0) HIP_CHECK(hipMemcpyAsync(active_d, active_h, sizeof(int) * (size_t)na, hipMemcpyHostToDevice, s));
-    };
-    step_v(0);
-    long k = 0;
-    long chunk = 8;
-    while (true) {
-      const long upto = std::min(cap, k + chunk);
-      while (k < upto) {
-        ++k;
-        step_u((int)k);
-        step_v((int)k);
-      }
-      read_flags();
-      drop_finished();
-      if (na == 0 || k >= cap) break;
-      chunk = std::max(4L, std::min(k / 2, 64L));
-    }
-    if (na > 0) {  // the cap: the tests (and the figures of info) for x_cap need alpha_{cap+1}
-      step_u((int)(k + 1));
-      read_flags();
-    }
+      return na == 0;
+    });
     go(t_gather_st, all_d, G);
     HIP_CHECK(hipMemcpyAsync(st_h, st_d.p, sizeof(double) * L_COUNT * G, hipMemcpyDeviceToHost, s));
 
@@ -453,18 +402,7 @@ struct GroupDiff {
     }
     sync();
     const double dt = now_ms() - t0;
-    for (int g = 0; g < G; ++g) {
-      ScsHipDiffInfo *info = infos[(size_t)g];
-      if (!info) continue;
-      const int *hfl = flags_h + (size_t)g * LF_COUNT;
-      const double *hst = st_h + (size_t)g * L_COUNT;
-      info->iters = (scs_int)std::min((long)hfl[LF_ITERS], cap);
-      info->stop = hfl[LF_STOP] ? hfl[LF_STOP] : 3;
-      info->residual = hst[L_BNORM] > 0. ? hst[L_RNORM] / hst[L_BNORM] : 0.;
-      const double den = hst[L_ANORM] * hst[L_RNORM];
-      info->normal_residual = den > 0. ? hst[L_ARNORM] / den : 0.;
-      info->time_ms = dt;
-    }
+    for (int g = 0; g < G; ++g) diff_fill_info(infos[(size_t)g], flags_h + (size_t)g * LF_COUNT, st_h + (size_t)g * L_COUNT, lim.cap, dt);
   }
 };
 

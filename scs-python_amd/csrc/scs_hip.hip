@@ -469,6 +469,58 @@ static std::string pert_refusal(const ScsHipWork *w, const DiffCall &call) {
   }
   return "";
 }
+// the device-pointer checks of a call's vectors, under the names the entry's header gives them
+static void diff_check_device(const ScsHipWork *w, const DiffCall &call, const char *who) {
+  for (int k = 0; k < 2; ++k)
+    if (call.pert[k]) check_device_vector(call.pert[k], w->device, who, (std::string(DiffCall::pert_name(k)) + "_dev").c_str());
+  for (int k = 0; k < 3; ++k)
+    if (call.in[k]) check_device_vector(call.in[k], w->device, who, (std::string(call.in_name(k)) + "_dev").c_str());
+  for (int k = 0; k < 4; ++k)
+    if (call.out[k]) check_device_vector(call.out[k], w->device, who, (std::string(call.out_name(k)) + "_dev").c_str());
+}
+// The refusal ladder of one call on one workspace (the caller holds w->mtx): the first step that applies throws "<who>: <reason>".
+// who = the entry's name, or "<entry>: member i" in a batch, whose members must all live on `batch_device` (< 0: a call of its own).
+static void diff_check(const ScsHipWork *w, const DiffCall &call, bool dev, const std::string &who, int batch_device = -1) {
+  std::string why = diff_refusal(w);
+  if (why.empty() && batch_device >= 0 && w->device != batch_device) why = "the members of a batch live on one device";
+  if (why.empty() && call.adjoint && call.out[2] && w->At.nnz != w->mats->a_nnz_in)
+    why = "the resident A' does not hold nnz(A) values: dAx cannot be gathered";
+  if (why.empty() && call.adjoint && call.out[3]) why = !w->has_P ? "dPx for a workspace created without P" : w->mats->p_update_refusal;
+  if (why.empty()) why = pert_refusal(w, call);
+  if (!why.empty()) throw std::runtime_error(who + ": " + why);
+  if (dev) diff_check_device(w, call, who.c_str());
+}
+// The host twin of one call: device copies of `in` and `pert`, device blocks for `out`.  stage() queues the uploads and returns the
+// device-side call, fetch() queues the downloads; the caller synchronises the stream once after all uploads and once after all
+// downloads, and holds an ArenaScope(nullptr).
+struct DiffStage {
+  DevBuf<double> bin[3], bout[4], bpert[2];
+  DiffCall host;
+  DiffCall stage(const ScsHipWork *w, const DiffCall &call, hipStream_t s) {
+    host = call;
+    DiffCall dc = call;
+    for (int k = 0; k < 3; ++k)
+      if (call.in[k]) {
+        bin[k].upload(call.in[k], (size_t)call.in_len(w, k), s);
+        dc.in[k] = bin[k].p;
+      }
+    for (int k = 0; k < 2; ++k)
+      if (call.pert[k]) {
+        bpert[k].upload(call.pert[k], (size_t)std::max(DiffCall::pert_len(w, k), 1L), s);
+        dc.pert[k] = bpert[k].p;
+      }
+    for (int k = 0; k < 4; ++k)
+      if (call.out[k]) {
+        bout[k].alloc((size_t)std::max(call.out_len(w, k), 1L));
+        dc.out[k] = bout[k].p;
+      }
+    return dc;
+  }
+  void fetch(const ScsHipWork *w, hipStream_t s) const {
+    for (int k = 0; k < 4; ++k)
+      if (host.out[k]) bout[k].download(host.out[k], (size_t)host.out_len(w, k), s);
+  }
+};
 static scs_int diff_entry(ScsWork *w, DiffCall call, const ScsHipDiffOpts *o, ScsHipDiffInfo *info, bool dev, const char *who) {
   if (!w) {
     set_last_error(std::string(who) + ": null workspace");
@@ -476,64 +528,20 @@ static scs_int diff_entry(ScsWork *w, DiffCall call, const ScsHipDiffOpts *o, Sc
   }
   try {
     set_last_error("");
-    static const char *const in_adj[3] = {"gx", "gy", "gs"}, *const in_fwd[3] = {"db", "dc", ""};
-    static const char *const out_adj[4] = {"db", "dc", "dAx", "dPx"}, *const out_fwd[4] = {"dx", "dy", "ds", ""};
-    const int n = w->n, m = w->m;
-    const long in_len_adj[3] = {n, m, m}, in_len_fwd[3] = {m, n, 0};
-    const long out_len_adj[4] = {m, n, w->mats->a_nnz_in, w->mats->p_nnz_in}, out_len_fwd[4] = {n, m, m, 0};
-    const long *in_len = call.adjoint ? in_len_adj : in_len_fwd, *out_len = call.adjoint ? out_len_adj : out_len_fwd;
     std::lock_guard<std::mutex> lock(w->mtx);
-    {
-      const std::string why = diff_refusal(w);
-      if (!why.empty()) throw std::runtime_error(std::string(who) + ": " + why);
-    }
-    if (call.adjoint && call.out[2] && w->At.nnz != w->mats->a_nnz_in)
-      throw std::runtime_error(std::string(who) + ": the resident A' does not hold nnz(A) values: dAx cannot be gathered");
-    if (call.adjoint && call.out[3]) {
-      if (!w->has_P) throw std::runtime_error(std::string(who) + ": dPx for a workspace created without P");
-      if (!w->mats->p_update_refusal.empty()) throw std::runtime_error(std::string(who) + ": " + w->mats->p_update_refusal);
-    }
-    {
-      const std::string why = pert_refusal(w, call);
-      if (!why.empty()) throw std::runtime_error(std::string(who) + ": " + why);
-    }
-    if (dev) {
-      for (int k = 0; k < 2; ++k)
-        if (call.pert[k]) check_device_vector(call.pert[k], w->device, who, k == 0 ? "dAx_dev" : "dPx_dev");
-      for (int k = 0; k < 3; ++k)
-        if (call.in[k]) check_device_vector(call.in[k], w->device, who, (std::string(call.adjoint ? in_adj[k] : in_fwd[k]) + "_dev").c_str());
-      for (int k = 0; k < 4; ++k)
-        if (call.out[k]) check_device_vector(call.out[k], w->device, who, (std::string(call.adjoint ? out_adj[k] : out_fwd[k]) + "_dev").c_str());
-    }
+    diff_check(w, call, dev, who);
     HIP_CHECK(hipSetDevice(w->device));
     ScsHipWork::ScratchTurn turn(w);
     if (dev) {
       diff_impl(w, call, o, info);
       return 0;
     }
-    // host twin: stage, run the device path, bring the results back
     ArenaScope no_arena(nullptr);
-    DevBuf<double> bin[3], bout[4], bpert[2];
-    DiffCall dc = call;
-    for (int k = 0; k < 3; ++k)
-      if (call.in[k]) {
-        bin[k].upload(call.in[k], (size_t)in_len[k], w->stream);
-        dc.in[k] = bin[k].p;
-      }
-    for (int k = 0; k < 2; ++k)
-      if (call.pert[k]) {
-        bpert[k].upload(call.pert[k], (size_t)std::max(k == 0 ? w->mats->a_nnz_in : w->mats->p_nnz_in, 1L), w->stream);
-        dc.pert[k] = bpert[k].p;
-      }
-    for (int k = 0; k < 4; ++k)
-      if (call.out[k]) {
-        bout[k].alloc((size_t)std::max(out_len[k], 1L));
-        dc.out[k] = bout[k].p;
-      }
+    DiffStage st;
+    const DiffCall dc = st.stage(w, call, w->stream);
     HIP_CHECK(hipStreamSynchronize(w->stream));
     diff_impl(w, dc, o, info);
-    for (int k = 0; k < 4; ++k)
-      if (call.out[k]) bout[k].download(call.out[k], (size_t)out_len[k], w->stream);
+    st.fetch(w, w->stream);
     HIP_CHECK(hipStreamSynchronize(w->stream));
     return 0;
   } catch (const std::exception &e) {
@@ -601,8 +609,7 @@ static scs_int data_perturbation_entry(ScsWork *w, const scs_float *dAx, const s
     if (why.empty()) why = pert_refusal(w, call);
     if (!why.empty()) throw std::runtime_error(std::string(who) + ": " + why);
     if (dev) {
-      if (dAx) check_device_vector(dAx, w->device, who, "dAx_dev");
-      if (dPx) check_device_vector(dPx, w->device, who, "dPx_dev");
+      diff_check_device(w, call, who);  // (dAx, dPx: the call holds nothing else)
       if (out_c) check_device_vector(out_c, w->device, who, "out_c_dev");
       if (out_b) check_device_vector(out_b, w->device, who, "out_b_dev");
     }
@@ -615,8 +622,8 @@ static scs_int data_perturbation_entry(ScsWork *w, const scs_float *dAx, const s
     const double *da = dAx, *dp = dPx;
     double *oc = out_c, *ob = out_b;
     if (!dev) {
-      if (dAx) { ba.upload(dAx, (size_t)std::max(w->mats->a_nnz_in, 1L), s); da = ba.p; }
-      if (dPx) { bp.upload(dPx, (size_t)std::max(w->mats->p_nnz_in, 1L), s); dp = bp.p; }
+      if (dAx) { ba.upload(dAx, (size_t)std::max(DiffCall::pert_len(w, 0), 1L), s); da = ba.p; }
+      if (dPx) { bp.upload(dPx, (size_t)std::max(DiffCall::pert_len(w, 1), 1L), s); dp = bp.p; }
       if (out_c) { bc.alloc(n); oc = bc.p; }
       if (out_b) { bb.alloc(m); ob = bb.p; }
       HIP_CHECK(hipStreamSynchronize(s));
@@ -697,8 +704,6 @@ static scs_int diff_batch_entry(ScsWork **works, std::vector<DiffCall> calls, co
   set_last_error("");
   if (!diff_batch_members_ok(works, count, who)) return -1;
   const bool adjoint = calls[0].adjoint;  // (count >= 1: one call per member)
-  static const char *const in_adj[3] = {"gx", "gy", "gs"}, *const in_fwd[3] = {"db", "dc", ""};
-  static const char *const out_adj[4] = {"db", "dc", "dAx", "dPx"}, *const out_fwd[4] = {"dx", "dy", "ds", ""};
   std::vector<std::unique_lock<std::mutex>> locks;
   std::vector<hipStream_t> saved;
   std::vector<int> restored;
@@ -710,69 +715,19 @@ static scs_int diff_batch_entry(ScsWork **works, std::vector<DiffCall> calls, co
       std::sort(order.begin(), order.end(), [&](int a, int b) { return std::less<ScsHipWork *>()(works[a], works[b]); });
       for (int j : order) locks.emplace_back(works[j]->mtx);
     }
-    // every refusal of diff_entry, for every member, before any device work
+    // every member's refusal ladder, before any device work
     std::vector<int> want((size_t)count, 0);
     for (int i = 0; i < count; ++i) {
-      ScsHipWork *w = works[i];
       const DiffCall &call = calls[(size_t)i];
-      const std::string mem = std::string(who) + ": member " + std::to_string(i), at = mem + ": ";
-      const std::string why = diff_refusal(w);
-      if (!why.empty()) throw std::runtime_error(at + why);
-      if (w->device != works[0]->device) throw std::runtime_error(at + "the members of a batch live on one device");
-      if (adjoint && call.out[2] && w->At.nnz != w->mats->a_nnz_in)
-        throw std::runtime_error(at + "the resident A' does not hold nnz(A) values: dAx cannot be gathered");
-      if (adjoint && call.out[3]) {
-        if (!w->has_P) throw std::runtime_error(at + "dPx for a workspace created without P");
-        if (!w->mats->p_update_refusal.empty()) throw std::runtime_error(at + w->mats->p_update_refusal);
-      }
-      {
-        const std::string why_pert = pert_refusal(w, call);
-        if (!why_pert.empty()) throw std::runtime_error(at + why_pert);
-      }
-      if (dev) {
-        for (int k = 0; k < 2; ++k)
-          if (call.pert[k]) check_device_vector(call.pert[k], w->device, mem.c_str(), k == 0 ? "dAx_dev" : "dPx_dev");
-        for (int k = 0; k < 3; ++k)
-          if (call.in[k]) check_device_vector(call.in[k], w->device, mem.c_str(), (std::string(adjoint ? in_adj[k] : in_fwd[k]) + "_dev").c_str());
-        for (int k = 0; k < 4; ++k)
-          if (call.out[k]) check_device_vector(call.out[k], w->device, mem.c_str(), (std::string(adjoint ? out_adj[k] : out_fwd[k]) + "_dev").c_str());
-      }
+      diff_check(works[i], call, dev, std::string(who) + ": member " + std::to_string(i), works[0]->device);
       want[(size_t)i] = adjoint ? ((call.out[2] ? 1 : 0) | (call.out[3] ? 2 : 0)) : ((call.pert[0] ? 1 : 0) | (call.pert[1] ? 2 : 0));
     }
     HIP_CHECK(hipSetDevice(works[0]->device));
     hipStream_t s = works[0]->stream;
-    // host twins: stage every member's vectors
     ArenaScope no_arena(nullptr);
-    std::vector<DevBuf<double>> bin, bout, bpert;
-    std::vector<DiffCall> host_calls;
-    auto in_len = [&](const ScsHipWork *w, int k) -> long { return adjoint ? (k == 0 ? w->n : w->m) : (k == 0 ? w->m : k == 1 ? w->n : 0); };
-    auto out_len = [&](const ScsHipWork *w, int k) -> long {
-      if (adjoint) return k == 0 ? w->m : k == 1 ? w->n : k == 2 ? w->mats->a_nnz_in : w->mats->p_nnz_in;
-      return k == 0 ? w->n : k < 3 ? w->m : 0;
-    };
+    std::vector<DiffStage> stages(dev ? 0 : (size_t)count);  // host twins: every member's vectors
     if (!dev) {
-      host_calls = calls;
-      bin = std::vector<DevBuf<double>>((size_t)count * 3);
-      bout = std::vector<DevBuf<double>>((size_t)count * 4);
-      bpert = std::vector<DevBuf<double>>((size_t)count * 2);
-      for (int i = 0; i < count; ++i) {
-        for (int k = 0; k < 2; ++k)
-          if (host_calls[(size_t)i].pert[k]) {
-            bpert[(size_t)i * 2 + k].upload(host_calls[(size_t)i].pert[k],
-                                            (size_t)std::max(k == 0 ? works[i]->mats->a_nnz_in : works[i]->mats->p_nnz_in, 1L), s);
-            calls[(size_t)i].pert[k] = bpert[(size_t)i * 2 + k].p;
-          }
-        for (int k = 0; k < 3; ++k)
-          if (host_calls[(size_t)i].in[k]) {
-            bin[(size_t)i * 3 + k].upload(host_calls[(size_t)i].in[k], (size_t)in_len(works[i], k), s);
-            calls[(size_t)i].in[k] = bin[(size_t)i * 3 + k].p;
-          }
-        for (int k = 0; k < 4; ++k)
-          if (host_calls[(size_t)i].out[k]) {
-            bout[(size_t)i * 4 + k].alloc((size_t)std::max(out_len(works[i], k), 1L));
-            calls[(size_t)i].out[k] = bout[(size_t)i * 4 + k].p;
-          }
-      }
+      for (int i = 0; i < count; ++i) calls[(size_t)i] = stages[(size_t)i].stage(works[i], calls[(size_t)i], s);
       HIP_CHECK(hipStreamSynchronize(s));
     }
     for (const std::vector<int> &job : plan_diff_batch(works, (int)count, want)) {
@@ -804,9 +759,7 @@ static scs_int diff_batch_entry(ScsWork **works, std::vector<DiffCall> calls, co
       restored.clear();
     }
     if (!dev) {
-      for (int i = 0; i < count; ++i)
-        for (int k = 0; k < 4; ++k)
-          if (host_calls[(size_t)i].out[k]) bout[(size_t)i * 4 + k].download(host_calls[(size_t)i].out[k], (size_t)out_len(works[i], k), s);
+      for (int i = 0; i < count; ++i) stages[(size_t)i].fetch(works[i], s);
       HIP_CHECK(hipStreamSynchronize(s));
     }
   } catch (const std::exception &e) {
@@ -1101,9 +1054,7 @@ int scs_hip_time_dproj(ScsWork *w, int reps, double *out) {
     const double *D = w->normalized ? w->D.p : nullptr;
     hipLaunchKernelGGL(k_dproj_vhat, dim3(vec_blocks(m)), dim3(kVecThreads), 0, s, (const double *)w->sols.p, (const double *)w->soly.p, D,
                        w->normalized ? w->scal.sigma : 1.0, m, d.vhat.p);
-    DprojPlan plan;
-    plan.vh = d.vhat.p; plan.m = m;
-    dproj_plan_box_pow(plan, w, d.box.p, d.box_ticket.p, d.sym3.p, d.dW.p);
+    const DprojPlan plan = diff_plan(w);  // (of which vh, box and sym3 are read below)
     // the two-launch form needs the partial slots whatever the size: scratch of this call when the workspace holds the short state
     ArenaScope no_arena(nullptr);
     DevBuf<double> st_big;
