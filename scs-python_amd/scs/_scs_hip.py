@@ -20,6 +20,9 @@ There is NO CPU fallback: if the shared library or a GPU is missing this module
 raises (ImportError at import for a missing library; ValueError("ScsWork
 allocation error!") from the constructor when no device is usable).
 """
+import collections
+import contextlib
+import functools
 import ctypes as C
 import importlib.util
 import os
@@ -838,8 +841,9 @@ class SCS(object):
             if not self._work:
                 raise ValueError("Workspace not initialized!")
             rc = _lib.scs_hip_update_device(self._work, bp, cp)
+            err = last_error() if rc != 0 else ""
         if rc != 0:
-            raise RuntimeError("libscs_hip: " + last_error())
+            raise RuntimeError("libscs_hip: " + err)
         return None
 
     def _previous_to_device(self, ptrs):
@@ -904,13 +908,7 @@ class SCS(object):
         tdev = torch.device("cuda", dev)
         out = {"x": torch.empty((K, self.n), dtype=torch.float64, device=tdev), "y": torch.empty((K, self.m), dtype=torch.float64, device=tdev),
                "s": torch.empty((K, self.m), dtype=torch.float64, device=tdev)}
-        ordered = sorted(members, key=id)  # the lock order of solve_batch
-        for sv in ordered:
-            sv._lock.acquire()
-        try:
-            for sv in members:
-                if not sv._work:
-                    raise ValueError("Workspace not initialized!")
+        with _locked(members) as works:
             if warm_start:
                 missing = [name for name in ("x", "y", "s") if rows[name] is None]
                 for name in ("x", "y", "s"):
@@ -924,20 +922,18 @@ class SCS(object):
                         sv._previous_to_device({name: out[name][i].data_ptr() for name in missing})
             _sync_torch_stream(dev)
             infos = [_ScsInfo() for _ in members]
-            works = (C.c_void_p * K)(*[sv._work for sv in members])
             ptrs = {name: (C.c_void_p * K)(*[out[name][i].data_ptr() for i in range(K)]) for name in ("x", "y", "s")}
             infp = (C.POINTER(_ScsInfo) * K)(*[C.pointer(io) for io in infos])
             rc = _lib.scs_hip_solve_batch_device(works, ptrs["x"], ptrs["y"], ptrs["s"], infp, K, 1 if warm_start else 0)
             err = last_error() if rc != 0 else ""
-        finally:
-            for sv in ordered:
-                sv._lock.release()
         out["info"] = [_info_dict(io) for io in infos]
         if rc != 0 and any(o["status_val"] == 0 for o in out["info"]):  # (as solve_batch: only a call that failed as a whole raises)
             raise RuntimeError("libscs_hip: " + err)
         return out
 
     # ------------------------------------------------------ derivatives of the last solve (include/scs_hip.h)
+    # The twelve public functions (here and adjoint_batch ... below) name a kind (_ADJOINT / _DERIVATIVE), a memory (host arrays or
+    # device tensors) and their arguments; `_diff` serves one solver, `_diff_list` a list of members.
     def _diff_call(self, fn, ptrs, opts):
         info = _ScsHipDiffInfo()
         with self._lock:
@@ -947,14 +943,45 @@ class SCS(object):
             err = last_error() if rc != 0 else ""
         if rc != 0:
             raise ValueError("libscs_hip: " + err)
-        return {"iters": int(info.iters), "residual": float(info.residual), "normal_residual": float(info.normal_residual),
-                "stop": int(info.stop), "time_ms": float(info.time_ms)}
+        return _diff_info_dict(info)
 
-    def _want_sizes(self, want):
-        want = _diff_want(want, self._pattern["P"] is not None)
-        sizes = {"b": self.m, "c": self.n, "A": int(self._pattern["A"][1].shape[0]),
-                 "P": int(self._pattern["P"][1].shape[0]) if self._pattern["P"] is not None else 0}
-        return want, sizes
+    def _lens(self):
+        """the lengths of the vectors of a derivative call, by the key the kinds use: n, m and the stored values of A and of P"""
+        pa, pp = self._pattern["A"], self._pattern["P"]
+        return {"n": self.n, "m": self.m, "A": int(pa[1].shape[0]), "P": int(pp[1].shape[0]) if pp is not None else 0}
+
+    def _refuse_dP(self, kind, vals):
+        """an input of nnz(P) values (dP) for a solver without P is refused here, before the library is called"""
+        if self._pattern["P"] is None:
+            for (name, key), v in zip(kind.ins, vals):
+                if key == "P" and v is not None:
+                    raise ValueError("%s given, but the solver was created without P" % name)
+
+    def _diff(self, kind, device, vals, want, tol, max_iters):
+        """One solver's call of `kind`: vals = the inputs in the order of kind.ins, on the host or (device) on the solver's GPU; want =
+        the outputs' names, None = all of them."""
+        if not self._work:
+            raise ValueError("Workspace not initialized!")
+        if want is not None:
+            want = _diff_want(want, self._pattern["P"] is not None)
+        lens, nv = self._lens(), kind.vectors
+        if device:  # (tol, max_iters and dP need no call of the library to be refused: they come before the first one, _device_index)
+            opts = _diff_opts(tol, max_iters)
+            self._refuse_dP(kind, vals)
+            mem = _device_memory(self._device_index())
+            ins = [mem.check(self, name, v, key, lens) for (name, key), v in zip(kind.ins, vals)]
+        else:  # (as the arguments come: the vectors, then the matrix values, then tol and max_iters)
+            mem = _HOST
+            ins = [mem.check(self, name, v, key, lens) for (name, key), v in zip(kind.ins[:nv], vals)]
+            self._refuse_dP(kind, vals)
+            ins += [mem.check(self, name, v, key, lens) for (name, key), v in zip(kind.ins[nv:], vals[nv:])]
+            opts = _diff_opts(tol, max_iters)
+        out = {k: mem.zeros(lens[kind.outs[k]]) for k in _diff_chosen(kind, want)}
+        fn, ins = _diff_entry(kind, mem, False, ins)
+        ptrs = [mem.address(v) if v is not None else None for v in ins] + [mem.address(out[k]) if k in out else None for k in kind.outs]
+        mem.ready()
+        out["info"] = self._diff_call(fn, ptrs, opts)
+        return out
 
     def adjoint(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
         """The adjoint of the last solve: given dL/dx (n), dL/dy (m), dL/ds (m) — None = 0 — returns {"db", "dc", ["dA"], ["dP"],
@@ -962,118 +989,49 @@ class SCS(object):
         of P in the constructor's order.  One LSQR solve on the device with tolerance `tol` and at most `max_iters` iterations (None:
         4 (n + m)); info = {"iters", "residual", "normal_residual", "stop", "time_ms"}.  A degenerate solution is not an error: the
         minimum-norm least-squares answer comes back with stop == 2."""
-        if not self._work:
-            raise ValueError("Workspace not initialized!")
-        want, sizes = self._want_sizes(want)
-        g = [_diff_vec("dx", dx, self.n), _diff_vec("dy", dy, self.m), _diff_vec("ds", ds, self.m)]
-        opts = _diff_opts(tol, max_iters)
-        out = {k: np.zeros(sizes[k]) for k in want}
-        ptrs = [_pd(v) if v is not None else None for v in g] + [_pd(out[k]) if k in out else None for k in ("b", "c", "A", "P")]
-        info = self._diff_call(_lib.scs_hip_adjoint, ptrs, opts)
-        res = {"d" + k: out[k] for k in want}
-        res["info"] = info
-        return res
+        return self._diff(_ADJOINT, False, (dx, dy, ds), want, tol, max_iters)
 
     def adjoint_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
         """`adjoint` over float64 torch tensors on the solver's GPU: takes and returns device tensors; nothing of length n or m
         crosses the host.  Same bits as `adjoint` on the same values."""
-        if not self._work:
-            raise ValueError("Workspace not initialized!")
-        want, sizes = self._want_sizes(want)
-        opts = _diff_opts(tol, max_iters)
-        dev = self._device_index()
-        g = [_device_vec(nm, t, ln, dev) if t is not None else None for nm, t, ln in (("dx", dx, self.n), ("dy", dy, self.m), ("ds", ds, self.m))]
-        import torch
-        tdev = torch.device("cuda", dev)
-        out = {k: torch.zeros(sizes[k], dtype=torch.float64, device=tdev) for k in want}
-        _sync_torch_stream(dev)  # the stream contract: inputs complete before the library's own stream reads them
-        ptrs = g + [out[k].data_ptr() if k in out and sizes[k] > 0 else None for k in ("b", "c", "A", "P")]
-        info = self._diff_call(_lib.scs_hip_adjoint_device, ptrs, opts)
-        res = {"d" + k: out[k] for k in want}
-        res["info"] = info
-        return res
-
-    def _pert_sizes(self, dA, dP):
-        """nnz(A), nnz(P) of the constructor's pattern; a dP for a solver without P is refused here, before the library is called"""
-        if dP is not None and self._pattern["P"] is None:
-            raise ValueError("dP given, but the solver was created without P")
-        return int(self._pattern["A"][1].shape[0]), int(self._pattern["P"][1].shape[0]) if self._pattern["P"] is not None else 0
+        return self._diff(_ADJOINT, True, (dx, dy, ds), want, tol, max_iters)
 
     def derivative(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
         """The forward derivative of the last solve: the change {"dx", "dy", "ds", "info"} of the solution for a change db (m), dc (n)
         of the data and dA, dP of the stored VALUES of A and of the upper triangle of P (None = 0); LSQR as in `adjoint`.  dA / dP: a 1-D
         float array of nnz values in the constructor's CSC order (an off-diagonal value of dP stands for both mirror images, as in
         `adjoint`'s dP), or a (data, indices, indptr) triple of a canonical CSC matrix of the constructor's pattern (`update_matrix`)."""
-        if not self._work:
-            raise ValueError("Workspace not initialized!")
-        d = [_diff_vec("db", db, self.m), _diff_vec("dc", dc, self.n)]
-        nnz_a, nnz_p = self._pert_sizes(dA, dP)
-        d += [_diff_mat("dA", dA, self._pattern["A"]), _diff_mat("dP", dP, self._pattern["P"])]
-        opts = _diff_opts(tol, max_iters)
-        out = {"dx": np.zeros(self.n), "dy": np.zeros(self.m), "ds": np.zeros(self.m)}
-        ptrs = [_pd(v) if v is not None else None for v in d] + [_pd(out[k]) for k in ("dx", "dy", "ds")]
-        if dA is None and dP is None:  # (the same path in the library; a refusal then names the entry it always named)
-            out["info"] = self._diff_call(_lib.scs_hip_derivative, ptrs[:2] + ptrs[4:], opts)
-        else:
-            out["info"] = self._diff_call(_lib.scs_hip_derivative_full, ptrs, opts)
-        return out
+        return self._diff(_DERIVATIVE, False, (db, dc, dA, dP), None, tol, max_iters)
 
     def derivative_device(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
         """`derivative` over float64 torch tensors on the solver's GPU (dA, dP: 1-D value tensors of nnz(A) / nnz(P) elements)."""
+        return self._diff(_DERIVATIVE, True, (db, dc, dA, dP), None, tol, max_iters)
+
+    def _data_perturbation(self, device, dA, dP):
         if not self._work:
             raise ValueError("Workspace not initialized!")
-        opts = _diff_opts(tol, max_iters)
-        nnz_a, nnz_p = self._pert_sizes(dA, dP)
-        dev = self._device_index()
-        d = [_device_vec(nm, t, ln, dev) if t is not None else None
-             for nm, t, ln in (("db", db, self.m), ("dc", dc, self.n), ("dA", dA, nnz_a), ("dP", dP, nnz_p))]
-        import torch
-        tdev = torch.device("cuda", dev)
-        out = {"dx": torch.zeros(self.n, dtype=torch.float64, device=tdev), "dy": torch.zeros(self.m, dtype=torch.float64, device=tdev),
-               "ds": torch.zeros(self.m, dtype=torch.float64, device=tdev)}
-        _sync_torch_stream(dev)
-        ptrs = d + [out[k].data_ptr() for k in ("dx", "dy", "ds")]
-        if dA is None and dP is None:
-            out["info"] = self._diff_call(_lib.scs_hip_derivative_device, ptrs[:2] + ptrs[4:], opts)
-        else:
-            out["info"] = self._diff_call(_lib.scs_hip_derivative_full_device, ptrs, opts)
-        return out
+        self._refuse_dP(_DERIVATIVE, (None, None, dA, dP))
+        mem = _device_memory(self._device_index()) if device else _HOST
+        lens = self._lens()
+        ins = [mem.check(self, name, v, key, lens) for (name, key), v in zip(_DERIVATIVE.ins[2:], (dA, dP))]
+        out_c, out_b = mem.zeros(self.n), mem.zeros(self.m)
+        ptrs = [mem.address(v) if v is not None else None for v in ins] + [mem.address(out_c), mem.address(out_b)]
+        mem.ready()
+        with self._lock:
+            rc = getattr(_lib, "scs_hip_data_perturbation" + mem.suffix)(self._work, *ptrs)
+            err = last_error() if rc != 0 else ""
+        if rc != 0:
+            raise ValueError("libscs_hip: " + err)
+        return out_c, out_b
 
     def data_perturbation(self, dA=None, dP=None):
         """(dP x + dA' y, dA x) at the resident solution of the last solve: the perturbation products of `derivative(dA=, dP=)` on
         their own (include/scs_hip.h: scs_hip_data_perturbation; tests)."""
-        if not self._work:
-            raise ValueError("Workspace not initialized!")
-        self._pert_sizes(dA, dP)
-        av, pv = _diff_mat("dA", dA, self._pattern["A"]), _diff_mat("dP", dP, self._pattern["P"])
-        out_c, out_b = np.zeros(self.n), np.zeros(self.m)
-        with self._lock:
-            rc = _lib.scs_hip_data_perturbation(self._work, _pd(av) if av is not None else None, _pd(pv) if pv is not None else None,
-                                                _pd(out_c), _pd(out_b))
-            err = last_error() if rc != 0 else ""
-        if rc != 0:
-            raise ValueError("libscs_hip: " + err)
-        return out_c, out_b
+        return self._data_perturbation(False, dA, dP)
 
     def data_perturbation_device(self, dA=None, dP=None):
         """`data_perturbation` over float64 torch tensors on the solver's GPU (taken and returned); same bits."""
-        if not self._work:
-            raise ValueError("Workspace not initialized!")
-        nnz_a, nnz_p = self._pert_sizes(dA, dP)
-        dev = self._device_index()
-        ap = _device_vec("dA", dA, nnz_a, dev) if dA is not None else None
-        pp = _device_vec("dP", dP, nnz_p, dev) if dP is not None else None
-        import torch
-        tdev = torch.device("cuda", dev)
-        out_c = torch.zeros(self.n, dtype=torch.float64, device=tdev)
-        out_b = torch.zeros(self.m, dtype=torch.float64, device=tdev)
-        _sync_torch_stream(dev)
-        with self._lock:
-            rc = _lib.scs_hip_data_perturbation_device(self._work, ap, pp, out_c.data_ptr(), out_b.data_ptr())
-            err = last_error() if rc != 0 else ""
-        if rc != 0:
-            raise ValueError("libscs_hip: " + err)
-        return out_c, out_b
+        return self._data_perturbation(True, dA, dP)
 
     # ------------------------------------- derivatives of solve_many's members in lock step (adjoint_batch below)
     def _many_members(self, K):
@@ -1087,64 +1045,34 @@ class SCS(object):
             raise ValueError("%d rows, but solve_many has solved %d member%s of this solver" % (K, have, "" if have == 1 else "s"))
         return [self] + self._many[:K - 1]
 
+    def _diff_many(self, kind, device, vals, want, tol, max_iters):
+        """`kind` of the members the last solve_many solved: vals = (K, .) stacks in the order of kind.ins.  On the device the results
+        are stacks too, and the one grouped call writes straight into their rows."""
+        self._refuse_dP(kind, vals)
+        mem = _device_memory(self._device_index()) if device else _HOST
+        lens = self._lens()
+        K, rows = _many_diff_args(_diff_spec(kind, vals, lens), None, want, self._pattern["P"] is not None, device=mem.device)
+        members = self._many_members(K)
+        return _diff_list(kind, mem, members, rows, [lens] * len(members), want, tol, max_iters, stacked=device)
+
     def adjoint_many(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
         """`adjoint` of the K members the last `solve_many` solved, in lock step (`adjoint_batch`): dx (K, n), dy (K, m), ds (K, m),
         None = 0.  Returns the K dicts `adjoint` would return, with the same bits."""
-        K, rows = _many_diff_args((("dx", dx, self.n), ("dy", dy, self.m), ("ds", ds, self.m)), None, want, self._pattern["P"] is not None)
-        members = self._many_members(K)
-        return adjoint_batch(members, rows["dx"], rows["dy"], rows["ds"], want, tol, max_iters)
+        return self._diff_many(_ADJOINT, False, (dx, dy, ds), want, tol, max_iters)
 
     def derivative_many(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
         """`derivative` of the K members the last `solve_many` solved, in lock step: db (K, m), dc (K, n), dA (K, nnz(A)),
         dP (K, nnz(P)), None = 0."""
-        nnz_a, nnz_p = self._pert_sizes(dA, dP)
-        K, rows = _many_diff_args((("db", db, self.m), ("dc", dc, self.n), ("dA", dA, nnz_a), ("dP", dP, nnz_p)), None,
-                                  have_P=self._pattern["P"] is not None)
-        members = self._many_members(K)
-        return derivative_batch(members, rows["db"], rows["dc"], tol, max_iters, dA=rows["dA"], dP=rows["dP"])
+        return self._diff_many(_DERIVATIVE, False, (db, dc, dA, dP), None, tol, max_iters)
 
     def adjoint_many_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
         """`adjoint_many` over float64 torch tensors (K, .) on the solver's GPU: one grouped call that writes straight into the rows of
         {"db": (K, m), "dc": (K, n), ["dA": (K, nnz)], ["dP"], "info": [K dicts]}."""
-        dev = self._device_index()
-        K, rows = _many_diff_args((("dx", dx, self.n), ("dy", dy, self.m), ("ds", ds, self.m)), None, want,
-                                  self._pattern["P"] is not None, device=dev)
-        members = self._many_members(K)
-        K = len(members)
-        want, sizes = self._want_sizes(want)
-        opts = _diff_opts(tol, max_iters)
-        import torch
-        tdev = torch.device("cuda", dev)
-        out = {k: torch.zeros((K, sizes[k]), dtype=torch.float64, device=tdev) for k in want}
-        ins = [[t[i].data_ptr() for i in range(K)] if t is not None else None for t in (rows["dx"], rows["dy"], rows["ds"])]
-        outs = [[out[k][i].data_ptr() for i in range(K)] if k in out and sizes[k] > 0 else None for k in ("b", "c", "A", "P")]
-        _sync_torch_stream(dev)  # the stream contract: inputs complete before the library's own stream reads them
-        infos = _diff_batch_call(_lib.scs_hip_adjoint_batch_device, members, ins + outs, opts)
-        res = {"d" + k: out[k] for k in want}
-        res["info"] = infos
-        return res
+        return self._diff_many(_ADJOINT, True, (dx, dy, ds), want, tol, max_iters)
 
     def derivative_many_device(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
         """`derivative_many` over float64 torch tensors (K, .) on the solver's GPU: {"dx": (K, n), "dy": (K, m), "ds": (K, m), "info"}."""
-        nnz_a, nnz_p = self._pert_sizes(dA, dP)
-        dev = self._device_index()
-        K, rows = _many_diff_args((("db", db, self.m), ("dc", dc, self.n), ("dA", dA, nnz_a), ("dP", dP, nnz_p)), None,
-                                  have_P=self._pattern["P"] is not None, device=dev)
-        members = self._many_members(K)
-        K = len(members)
-        opts = _diff_opts(tol, max_iters)
-        import torch
-        tdev = torch.device("cuda", dev)
-        out = {"dx": torch.zeros((K, self.n), dtype=torch.float64, device=tdev), "dy": torch.zeros((K, self.m), dtype=torch.float64, device=tdev),
-               "ds": torch.zeros((K, self.m), dtype=torch.float64, device=tdev)}
-        ins = [[t[i].data_ptr() for i in range(K)] if t is not None else None for t in (rows["db"], rows["dc"], rows["dA"], rows["dP"])]
-        outs = [[out[k][i].data_ptr() for i in range(K)] for k in ("dx", "dy", "ds")]
-        _sync_torch_stream(dev)
-        if dA is None and dP is None:
-            out["info"] = _diff_batch_call(_lib.scs_hip_derivative_batch_device, members, ins[:2] + outs, opts)
-        else:
-            out["info"] = _diff_batch_call(_lib.scs_hip_derivative_full_batch_device, members, ins + outs, opts)
-        return out
+        return self._diff_many(_DERIVATIVE, True, (db, dc, dA, dP), None, tol, max_iters)
 
     # -------------------------------------------------- bench hooks (not part of the reference surface)
     def _set_profiling(self, on):
@@ -1392,6 +1320,33 @@ def _many_args(m, n, b, c, warm_start, x, y, s):
     return K, rows
 
 
+@contextlib.contextmanager
+def _locked(solvers):
+    """Every member's lock for the length of a grouped call, taken in `id` order — one global lock order: two overlapping batches
+    cannot deadlock.  A finished member is refused; yields the C array of the members' workspaces, in the order given."""
+    ordered = sorted(solvers, key=id)
+    for sv in ordered:
+        sv._lock.acquire()
+    try:
+        for sv in solvers:
+            if not sv._work:
+                raise ValueError("Workspace not initialized!")
+        yield (C.c_void_p * len(solvers))(*[sv._work for sv in solvers])
+    finally:
+        for sv in ordered:
+            sv._lock.release()
+
+
+def _batch_solvers(solvers, who):
+    solvers = list(solvers)
+    for sv in solvers:
+        if not isinstance(sv, SCS):
+            raise TypeError("%s expects scs._scs_hip.SCS objects" % who)
+    if len(set(id(sv) for sv in solvers)) != len(solvers):
+        raise ValueError("%s: a solver appears twice" % who)
+    return solvers
+
+
 def solve_batch(solvers, warm_start=False):
     """Grouped solve of several backend `SCS` objects (include/scs_hip.h: scs_hip_solve_batch): equally shaped
     problems share every kernel launch of the ADMM loop.  Returns the list of result dicts `solve()` would have
@@ -1408,31 +1363,32 @@ def solve_batch(solvers, warm_start=False):
     for sv in solvers:
         if not isinstance(sv, SCS):
             raise TypeError("solve_batch expects scs._scs_hip.SCS objects")
-    ordered = sorted(solvers, key=id)  # one global lock order: two overlapping batches cannot deadlock
-    for sv in ordered:
-        sv._lock.acquire()
-    try:
-        for sv in solvers:
-            if not sv._work:
-                raise ValueError("Workspace not initialized!")
+    with _locked(solvers) as works:
         cnt = len(solvers)
         sols = [_ScsSolution(_pd(sv._x), _pd(sv._y), _pd(sv._s)) for sv in solvers]
         infos = [_ScsInfo() for _ in solvers]
-        works = (C.c_void_p * cnt)(*[sv._work for sv in solvers])
         solp = (C.POINTER(_ScsSolution) * cnt)(*[C.pointer(so) for so in sols])
         infp = (C.POINTER(_ScsInfo) * cnt)(*[C.pointer(io) for io in infos])
         rc = _lib.scs_hip_solve_batch(works, solp, infp, cnt, 1 if warm_start else 0)  # GIL released by ctypes
         err = last_error() if rc != 0 else ""
         out = [{"x": sv._x.copy(), "y": sv._y.copy(), "s": sv._s.copy(), "info": _info_dict(io)}
                for sv, io in zip(solvers, infos)]
-    finally:
-        for sv in ordered:
-            sv._lock.release()
     # rc != 0 also when a single member ended SCS_FAILED: its dict says so (status_val -4, NaN vectors) exactly as .solve() would
     # report it, and the other members keep their results.  Only a call that failed as a whole raises.
     if rc != 0 and any(o["info"]["status_val"] == 0 for o in out):
         raise RuntimeError("libscs_hip: " + err)
     return out
+
+
+def _plan_call(solvers, plan):
+    """a grouping entry under every member's lock: plan(works, K, out) fills out[i] with member i's group"""
+    with _locked(solvers) as works:
+        out = (c_int * len(solvers))()
+        rc = plan(works, len(solvers), out)
+        err = last_error() if rc < 0 else ""
+    if rc < 0:
+        raise RuntimeError("libscs_hip: " + err)
+    return [int(v) for v in out]
 
 
 def batch_plan(solvers):
@@ -1446,26 +1402,77 @@ def batch_plan(solvers):
     for sv in solvers:
         if not isinstance(sv, SCS):
             raise TypeError("batch_plan expects scs._scs_hip.SCS objects")
-    ordered = sorted(solvers, key=id)  # (the lock order of solve_batch)
-    for sv in ordered:
-        sv._lock.acquire()
-    try:
-        for sv in solvers:
-            if not sv._work:
-                raise ValueError("Workspace not initialized!")
-        cnt = len(solvers)
-        works = (C.c_void_p * cnt)(*[sv._work for sv in solvers])
-        out = (c_int * cnt)()
-        rc = _lib.scs_hip_batch_plan(works, cnt, out)
-    finally:
-        for sv in ordered:
-            sv._lock.release()
-    if rc < 0:
-        raise RuntimeError("libscs_hip: " + last_error())
-    return [int(v) for v in out]
+    return _plan_call(solvers, _lib.scs_hip_batch_plan)
 
 
-# ---------------------------------------------------------------- derivatives of a batch (include/scs_hip.h: scs_hip_adjoint_batch ...)
+# ---------------------------------------------------------------- derivatives: the two kinds, the two memories, the two call shapes
+# A kind of derivative call is its vectors in the slot order of its C entries (include/scs_hip.h), each with the key of its length in
+# `SCS._lens()`: `ins` are the public arguments in their order, the first `vectors` of them data vectors and the rest values of the
+# matrices; `outs` are the results under the names they are returned by (a dict in slot order).  `entry` is the stem of its four C entries: + "_batch" for a
+# list of members, + "_device" for device pointers.  `short`: the stem for a call whose matrix values are all None, which takes the
+# slots without them (scs_hip_derivative[_batch][_device] are the full entries with NULL dAx and dPx, under their own names).
+_DiffKind = collections.namedtuple("_DiffKind", "ins vectors outs entry short")
+_ADJOINT = _DiffKind(ins=(("dx", "n"), ("dy", "m"), ("ds", "m")), vectors=3, outs={"db": "m", "dc": "n", "dA": "A", "dP": "P"},
+                     entry="scs_hip_adjoint", short=None)  # (`want` selects among the outputs: "b" is db ...)
+_DERIVATIVE = _DiffKind(ins=(("db", "m"), ("dc", "n"), ("dA", "A"), ("dP", "P")), vectors=2, outs={"dx": "n", "dy": "m", "ds": "m"},
+                        entry="scs_hip_derivative_full", short="scs_hip_derivative")
+
+# Where the vectors live.  check(solver, name, value, key, lens): one input, checked before the library is called, as it goes on;
+# zeros(shape): a result; address(vector): what C gets; ready(): right before the call; device: the GPU index, None on the host.
+_Memory = collections.namedtuple("_Memory", "suffix device check zeros address ready")
+
+
+def _host_check(sv, name, v, key, lens):
+    return _diff_mat(name, v, sv._pattern[key]) if key in ("A", "P") else _diff_vec(name, v, lens[key])
+
+
+_HOST = _Memory("", None, _host_check, np.zeros, lambda a: a.ctypes.data, lambda: None)
+
+
+@functools.lru_cache(maxsize=None)
+def _device_memory(dev):
+    """float64 torch tensors on GPU `dev` (torch is imported here, not by `import scs`)"""
+    import torch
+    tdev = torch.device("cuda", dev)
+
+    def check(sv, name, t, key, lens):
+        if t is not None:
+            _device_vec(name, t, lens[key], dev)
+        return t
+
+    # A result without an element: C takes a non-NULL output as wanted, whatever its length — the refusals for dPx fire, a batch groups
+    # its members by it (csrc/scs_hip.hip diff_check, diff_batch_entry) — so NULL and the address of an empty array are two requests.
+    # The host passes the address numpy gives an empty array; an empty tensor has none (its data_ptr() is 0), so here it is NULL.
+    return _Memory("_device", dev, check, functools.partial(torch.zeros, dtype=torch.float64, device=tdev), torch.Tensor.data_ptr,
+                   lambda: _sync_torch_stream(dev))  # the stream contract: inputs complete before the library's own stream reads them
+
+
+def _diff_chosen(kind, want):
+    """the names of the results: those `want` selects, in its order, or (None) all of the kind"""
+    return ["d" + k for k in want] if want is not None else list(kind.outs)
+
+
+def _diff_entry(kind, mem, batch, ins):
+    """the C entry of a call and the inputs that fill its slots"""
+    stem = kind.entry
+    # dA is None and dP is None: the short entry (the same path in the library; a refusal then names the entry it always named)
+    if kind.short and all(v is None for v in ins[kind.vectors:]):
+        stem, ins = kind.short, ins[:kind.vectors]
+    return getattr(_lib, stem + ("_batch" if batch else "") + mem.suffix), ins
+
+
+def _diff_info_dict(info):
+    return {"iters": int(info.iters), "residual": float(info.residual), "normal_residual": float(info.normal_residual),
+            "stop": int(info.stop), "time_ms": float(info.time_ms)}
+
+
+def _diff_spec(kind, vals, lens):
+    """the (name, value, length) triples `_many_diff_args` takes; lens: the `_lens()` of all members, or a list of each member's"""
+    if isinstance(lens, dict):
+        return tuple((name, v, lens[key]) for (name, key), v in zip(kind.ins, vals))
+    return tuple((name, v, [ln[key] for ln in lens]) for (name, key), v in zip(kind.ins, vals))
+
+
 def _many_diff_args(spec, K, want=None, have_P=True, device=None):
     """Argument checks of the batch derivative entries, before the library is called (pure Python; torch is touched only for device
     arguments).  spec: (name, value, length) triples; `length` is an int or a list of one int per member.  A value is None (0 for every
@@ -1517,16 +1524,6 @@ def _many_diff_args(spec, K, want=None, have_P=True, device=None):
     return K, rows
 
 
-def _batch_solvers(solvers, who):
-    solvers = list(solvers)
-    for sv in solvers:
-        if not isinstance(sv, SCS):
-            raise TypeError("%s expects scs._scs_hip.SCS objects" % who)
-    if len(set(id(sv) for sv in solvers)) != len(solvers):
-        raise ValueError("%s: a solver appears twice" % who)
-    return solvers
-
-
 def _ptr_array(K, ptrs):
     """a C array of K addresses (None entries = NULL), or None for `no such argument`"""
     if ptrs is None or all(p is None for p in ptrs):
@@ -1535,149 +1532,82 @@ def _ptr_array(K, ptrs):
 
 
 def _diff_batch_call(fn, solvers, ptr_lists, opts):
-    """one call of a batch derivative entry under every member's lock (the order of solve_batch); returns the K info dicts"""
+    """one call of a batch derivative entry under every member's lock; returns the K info dicts"""
     K = len(solvers)
-    ordered = sorted(solvers, key=id)
-    for sv in ordered:
-        sv._lock.acquire()
-    try:
-        for sv in solvers:
-            if not sv._work:
-                raise ValueError("Workspace not initialized!")
-        works = (C.c_void_p * K)(*[sv._work for sv in solvers])
+    with _locked(solvers) as works:
         infos = [_ScsHipDiffInfo() for _ in solvers]
         infp = (C.POINTER(_ScsHipDiffInfo) * K)(*[C.pointer(io) for io in infos])
         rc = fn(works, *([_ptr_array(K, pl) for pl in ptr_lists] + [C.byref(opts), infp, K]))
         err = last_error() if rc != 0 else ""
-    finally:
-        for sv in ordered:
-            sv._lock.release()
     if rc != 0:
         raise ValueError("libscs_hip: " + err)
-    return [{"iters": int(io.iters), "residual": float(io.residual), "normal_residual": float(io.normal_residual), "stop": int(io.stop),
-             "time_ms": float(io.time_ms)} for io in infos]
+    return [_diff_info_dict(io) for io in infos]
 
 
-def _host_ptrs(rows):
-    return [v.ctypes.data if v is not None else None for v in rows] if rows is not None else None
+def _diff_list(kind, mem, solvers, rows, lens, want, tol, max_iters, stacked=False):
+    """`kind` of a list of distinct members in ONE call of its batch entry.  rows: what `_many_diff_args` made of the inputs; lens: each
+    member's `_lens()`.  Returns one result dict per member — or (stacked: members of one shape) one dict of (K, .) stacks, whose rows
+    the call writes straight into, with the list of the K infos."""
+    K = len(solvers)
+    opts = _diff_opts(tol, max_iters)
+    chosen, sizes = _diff_chosen(kind, want), kind.outs
+    if stacked:
+        out = cols = {k: mem.zeros((K, lens[0][sizes[k]])) for k in chosen}
+    else:
+        out = [{k: mem.zeros(ln[sizes[k]]) for k in chosen} for ln in lens]
+        cols = {k: [o[k] for o in out] for k in chosen}
+    fn, ins = _diff_entry(kind, mem, True, [rows[name] for name, _ in kind.ins])
+    ptrs = [[mem.address(v) if v is not None else None for v in r] if r is not None else None for r in ins]
+    ptrs += [[mem.address(a) for a in cols[k]] if k in cols else None for k in kind.outs]
+    mem.ready()
+    infos = _diff_batch_call(fn, solvers, ptrs, opts)
+    if stacked:
+        out["info"] = infos
+    else:
+        for o, info in zip(out, infos):
+            o["info"] = info
+    return out
+
+
+def _diff_batch(kind, device, who, solvers, vals, want, tol, max_iters):
+    """`kind` of a list of solvers the caller names: vals = one sequence (or (K, .) array) per input, in the order of kind.ins"""
+    solvers = _batch_solvers(solvers, who)
+    dev = None
+    if device:
+        devs = set(sv._device_index() for sv in solvers)
+        if len(devs) > 1:
+            raise ValueError("%s: the solvers live on different GPUs" % who)
+        dev = devs.pop() if devs else 0
+    if not solvers:
+        return []
+    lens = [sv._lens() for sv in solvers]
+    have_P = all(sv._pattern["P"] is not None for sv in solvers)
+    _, rows = _many_diff_args(_diff_spec(kind, vals, lens), len(solvers), want, have_P, device=dev)
+    return _diff_list(kind, _device_memory(dev) if device else _HOST, solvers, rows, lens, want, tol, max_iters)
 
 
 def adjoint_batch(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
     """`adjoint` of several solved backend `SCS` objects in one call (include/scs_hip.h: scs_hip_adjoint_batch): equally shaped members
     share every kernel launch of the LSQR iteration.  dx, dy, ds: sequences (or (K, .) arrays) with one vector per solver; None, or a
     None entry, counts as 0.  Returns the list of dicts `adjoint` would return for each, with the same bits."""
-    solvers = _batch_solvers(solvers, "adjoint_batch")
-    if not solvers:
-        return []
-    K = len(solvers)
-    have_P = all(sv._pattern["P"] is not None for sv in solvers)
-    _, rows = _many_diff_args((("dx", dx, [sv.n for sv in solvers]), ("dy", dy, [sv.m for sv in solvers]), ("ds", ds, [sv.m for sv in solvers])),
-                              K, want, have_P)
-    opts = _diff_opts(tol, max_iters)
-    outs, want_t = [], None
-    for sv in solvers:
-        want_t, sizes = sv._want_sizes(want)
-        outs.append({k: np.zeros(sizes[k]) for k in want_t})
-    ptrs = [_host_ptrs(rows[k]) for k in ("dx", "dy", "ds")] + [[o[k].ctypes.data for o in outs] if k in want_t else None for k in ("b", "c", "A", "P")]
-    infos = _diff_batch_call(_lib.scs_hip_adjoint_batch, solvers, ptrs, opts)
-    res = []
-    for o, info in zip(outs, infos):
-        r = {"d" + k: o[k] for k in want_t}
-        r["info"] = info
-        res.append(r)
-    return res
-
-
-def _batch_pert_spec(solvers, db, dc, dA, dP):
-    """the spec of `_many_diff_args` for a forward batch, and whether every member has a P"""
-    nnz_a = [int(sv._pattern["A"][1].shape[0]) for sv in solvers]
-    nnz_p = [int(sv._pattern["P"][1].shape[0]) if sv._pattern["P"] is not None else 0 for sv in solvers]
-    have_P = all(sv._pattern["P"] is not None for sv in solvers)
-    return (("db", db, [sv.m for sv in solvers]), ("dc", dc, [sv.n for sv in solvers]), ("dA", dA, nnz_a), ("dP", dP, nnz_p)), have_P
+    return _diff_batch(_ADJOINT, False, "adjoint_batch", solvers, (dx, dy, ds), want, tol, max_iters)
 
 
 def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
     """`derivative` of several solved backend `SCS` objects in one call: db, dc, dA, dP as the vectors of `adjoint_batch` (dA / dP: one
     value array of nnz(A) / nnz(P) elements per solver).  Returns the list of dicts `derivative` would return for each, with the same
     bits."""
-    solvers = _batch_solvers(solvers, "derivative_batch")
-    if not solvers:
-        return []
-    K = len(solvers)
-    spec, have_P = _batch_pert_spec(solvers, db, dc, dA, dP)
-    _, rows = _many_diff_args(spec, K, have_P=have_P)
-    opts = _diff_opts(tol, max_iters)
-    outs = [{"dx": np.zeros(sv.n), "dy": np.zeros(sv.m), "ds": np.zeros(sv.m)} for sv in solvers]
-    ptrs = [_host_ptrs(rows[k]) for k in ("db", "dc", "dA", "dP")] + [[o[k].ctypes.data for o in outs] for k in ("dx", "dy", "ds")]
-    if dA is None and dP is None:
-        infos = _diff_batch_call(_lib.scs_hip_derivative_batch, solvers, ptrs[:2] + ptrs[4:], opts)
-    else:
-        infos = _diff_batch_call(_lib.scs_hip_derivative_full_batch, solvers, ptrs, opts)
-    for o, info in zip(outs, infos):
-        o["info"] = info
-    return outs
-
-
-def _batch_device(solvers, who):
-    solvers = _batch_solvers(solvers, who)
-    devs = set(sv._device_index() for sv in solvers)
-    if len(devs) > 1:
-        raise ValueError("%s: the solvers live on different GPUs" % who)
-    return solvers, (devs.pop() if devs else 0)
+    return _diff_batch(_DERIVATIVE, False, "derivative_batch", solvers, (db, dc, dA, dP), None, tol, max_iters)
 
 
 def adjoint_batch_device(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
     """`adjoint_batch` over float64 torch tensors on the solvers' GPU (taken and returned); same bits."""
-    solvers, dev = _batch_device(solvers, "adjoint_batch_device")
-    if not solvers:
-        return []
-    K = len(solvers)
-    have_P = all(sv._pattern["P"] is not None for sv in solvers)
-    _, rows = _many_diff_args((("dx", dx, [sv.n for sv in solvers]), ("dy", dy, [sv.m for sv in solvers]), ("ds", ds, [sv.m for sv in solvers])),
-                              K, want, have_P, device=dev)
-    opts = _diff_opts(tol, max_iters)
-    import torch
-    tdev = torch.device("cuda", dev)
-    outs, want_t, sizes_all = [], None, []
-    for sv in solvers:
-        want_t, sizes = sv._want_sizes(want)
-        sizes_all.append(sizes)
-        outs.append({k: torch.zeros(sizes[k], dtype=torch.float64, device=tdev) for k in want_t})
-    ins = [[t.data_ptr() if t is not None else None for t in rows[k]] if rows[k] is not None else None for k in ("dx", "dy", "ds")]
-    ptrs = ins + [[o[k].data_ptr() if sz[k] > 0 else None for o, sz in zip(outs, sizes_all)] if k in want_t else None for k in ("b", "c", "A", "P")]
-    _sync_torch_stream(dev)
-    infos = _diff_batch_call(_lib.scs_hip_adjoint_batch_device, solvers, ptrs, opts)
-    res = []
-    for o, info in zip(outs, infos):
-        r = {"d" + k: o[k] for k in want_t}
-        r["info"] = info
-        res.append(r)
-    return res
+    return _diff_batch(_ADJOINT, True, "adjoint_batch_device", solvers, (dx, dy, ds), want, tol, max_iters)
 
 
 def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
     """`derivative_batch` over float64 torch tensors on the solvers' GPU."""
-    solvers, dev = _batch_device(solvers, "derivative_batch_device")
-    if not solvers:
-        return []
-    K = len(solvers)
-    spec, have_P = _batch_pert_spec(solvers, db, dc, dA, dP)
-    _, rows = _many_diff_args(spec, K, have_P=have_P, device=dev)
-    opts = _diff_opts(tol, max_iters)
-    import torch
-    tdev = torch.device("cuda", dev)
-    outs = [{"dx": torch.zeros(sv.n, dtype=torch.float64, device=tdev), "dy": torch.zeros(sv.m, dtype=torch.float64, device=tdev),
-             "ds": torch.zeros(sv.m, dtype=torch.float64, device=tdev)} for sv in solvers]
-    ins = [[t.data_ptr() if t is not None else None for t in rows[k]] if rows[k] is not None else None for k in ("db", "dc", "dA", "dP")]
-    ptrs = ins + [[o[k].data_ptr() for o in outs] for k in ("dx", "dy", "ds")]
-    _sync_torch_stream(dev)
-    if dA is None and dP is None:
-        infos = _diff_batch_call(_lib.scs_hip_derivative_batch_device, solvers, ptrs[:2] + ptrs[4:], opts)
-    else:
-        infos = _diff_batch_call(_lib.scs_hip_derivative_full_batch_device, solvers, ptrs, opts)
-    for o, info in zip(outs, infos):
-        o["info"] = info
-    return outs
+    return _diff_batch(_DERIVATIVE, True, "derivative_batch_device", solvers, (db, dc, dA, dP), None, tol, max_iters)
 
 
 def diff_batch_plan(solvers, want=("b", "c")):
@@ -1687,23 +1617,7 @@ def diff_batch_plan(solvers, want=("b", "c")):
     if not solvers:
         return []
     want = _diff_want(want, True)
-    K = len(solvers)
-    ordered = sorted(solvers, key=id)
-    for sv in ordered:
-        sv._lock.acquire()
-    try:
-        for sv in solvers:
-            if not sv._work:
-                raise ValueError("Workspace not initialized!")
-        works = (C.c_void_p * K)(*[sv._work for sv in solvers])
-        out = (c_int * K)()
-        rc = _lib.scs_hip_diff_batch_plan(works, K, 1 if "A" in want else 0, 1 if "P" in want else 0, out)
-    finally:
-        for sv in ordered:
-            sv._lock.release()
-    if rc < 0:
-        raise RuntimeError("libscs_hip: " + last_error())
-    return [int(v) for v in out]
+    return _plan_call(solvers, lambda works, K, out: _lib.scs_hip_diff_batch_plan(works, K, 1 if "A" in want else 0, 1 if "P" in want else 0, out))
 
 
 def data_perturbation(solver, dA=None, dP=None):

@@ -29,76 +29,59 @@ second call on), backward is ONE `adjoint_many_device` call — the K members ar
 import torch
 
 
+def _solved(ctx, solver, out):
+  """a forward's book-keeping: the solver's generation counts its solves, and the backward of this one holds its number"""
+  solver._autograd_generation = getattr(solver, "_autograd_generation", 0) + 1
+  solver.autograd_info = out["info"]
+  ctx.solver = solver
+  ctx.generation = solver._autograd_generation
+  return out["x"], out["y"], out["s"]
+
+
+def _still_resident(ctx, who, what):
+  if getattr(ctx.solver, "_autograd_generation", 0) != ctx.generation:
+    raise RuntimeError("scs.autograd.%s: the solver was solved again before this backward; its resident %s" % (who, what))
+
+
 class _Solve(torch.autograd.Function):
-
-  @staticmethod
-  def forward(ctx, solver, b, c):
-    solver.update_device(b.detach().contiguous(), c.detach().contiguous())
-    warm = bool(getattr(solver, "_autograd_generation", 0))
-    out = solver.solve_device(warm_start=warm)
-    solver._autograd_generation = getattr(solver, "_autograd_generation", 0) + 1
-    solver.autograd_info = out["info"]
-    # (detached views: the returned tensors get a grad_fn that holds ctx and with it the solver — the solver must not hold them back)
-    solver._autograd_last = (out["x"].detach(), out["y"].detach(), out["s"].detach())
-    ctx.solver = solver
-    ctx.generation = solver._autograd_generation
-    return out["x"], out["y"], out["s"]
-
-  @staticmethod
-  @torch.autograd.function.once_differentiable
-  def backward(ctx, gx, gy, gs):
-    solver = ctx.solver
-    if getattr(solver, "_autograd_generation", 0) != ctx.generation:
-      raise RuntimeError("scs.autograd.solve: the solver was solved again before this backward; its resident solution is another one")
-    if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
-      return None, None, None
-    res = solver.adjoint_device(dx=gx.contiguous(), dy=gy.contiguous(), ds=gs.contiguous(), want=("b", "c"),
-                                tol=getattr(solver, "autograd_tol", 1e-8))
-    solver.autograd_adjoint_info = res["info"]
-    return None, res["db"] if ctx.needs_input_grad[1] else None, res["dc"] if ctx.needs_input_grad[2] else None
-
-
-class _SolveMatrix(torch.autograd.Function):
-  """`_Solve` with the values of A and / or P as inputs (None = the solver's own)"""
+  """A, P: the values of the matrices as inputs, None = the solver's own"""
 
   @staticmethod
   def forward(ctx, solver, b, c, A, P):
-    solver.update_matrix_device(A.detach().contiguous() if A is not None else None, P.detach().contiguous() if P is not None else None)
+    ctx.matrix = A is not None or P is not None
+    if ctx.matrix:
+      solver.update_matrix_device(A.detach().contiguous() if A is not None else None, P.detach().contiguous() if P is not None else None)
     solver.update_device(b.detach().contiguous(), c.detach().contiguous())
-    last = getattr(solver, "_autograd_last", None)  # (the new matrix left a cold iterate: the previous solution goes in explicitly)
-    if last is not None:
+    last = getattr(solver, "_autograd_last", None)
+    if not ctx.matrix:
+      out = solver.solve_device(warm_start=bool(getattr(solver, "_autograd_generation", 0)))
+    elif last is not None:  # (the new matrix left a cold iterate: the previous solution goes in explicitly)
       out = solver.solve_device(warm_start=True, x=last[0], y=last[1], s=last[2])
     else:
       out = solver.solve_device(warm_start=False)
-    solver._autograd_generation = getattr(solver, "_autograd_generation", 0) + 1
-    solver.autograd_info = out["info"]
     # (detached views: the returned tensors get a grad_fn that holds ctx and with it the solver — the solver must not hold them back)
     solver._autograd_last = (out["x"].detach(), out["y"].detach(), out["s"].detach())
-    ctx.solver = solver
-    ctx.generation = solver._autograd_generation
-    return out["x"], out["y"], out["s"]
+    return _solved(ctx, solver, out)
 
   @staticmethod
   @torch.autograd.function.once_differentiable
   def backward(ctx, gx, gy, gs):
-    solver = ctx.solver
-    if getattr(solver, "_autograd_generation", 0) != ctx.generation:
-      raise RuntimeError("scs.autograd.solve: the solver was solved again before this backward; its resident solution is another one")
-    want = tuple(k for k, need in zip(("b", "c", "A", "P"), ctx.needs_input_grad[1:5]) if need)
-    if not want:
+    _still_resident(ctx, "solve", "solution is another one")
+    need = ctx.needs_input_grad[1:5]
+    if not any(need):
       return None, None, None, None, None
-    res = solver.adjoint_device(dx=gx.contiguous(), dy=gy.contiguous(), ds=gs.contiguous(), want=want,
-                                tol=getattr(solver, "autograd_tol", 1e-8))
-    solver.autograd_adjoint_info = res["info"]
-    return (None,) + tuple(res.get("d" + k) for k in ("b", "c", "A", "P"))
+    # (with matrices, `want` holds exactly the inputs that need a gradient; without, the call is the one it always was)
+    want = tuple(k for k, nd in zip(("b", "c", "A", "P"), need) if nd) if ctx.matrix else ("b", "c")
+    res = ctx.solver.adjoint_device(dx=gx.contiguous(), dy=gy.contiguous(), ds=gs.contiguous(), want=want,
+                                    tol=getattr(ctx.solver, "autograd_tol", 1e-8))
+    ctx.solver.autograd_adjoint_info = res["info"]
+    return (None,) + tuple(res["d" + k] if nd else None for k, nd in zip(("b", "c", "A", "P"), need))
 
 
 def solve(solver, b, c, A=None, P=None):
   """(x, y, s) of the solver's problem with the data b, c and — when given — the matrix values A, P (1-D tensors in the constructor's
   canonical order), differentiable with respect to each tensor passed."""
-  if A is None and P is None:
-    return _Solve.apply(solver, b, c)
-  return _SolveMatrix.apply(solver, b, c, A, P)
+  return _Solve.apply(solver, b, c, A, P)
 
 
 class _SolveMany(torch.autograd.Function):
@@ -106,24 +89,17 @@ class _SolveMany(torch.autograd.Function):
   @staticmethod
   def forward(ctx, solver, B, C):
     warm = bool(getattr(solver, "_autograd_generation", 0))
-    out = solver.solve_many_device(b=B.detach().contiguous(), c=C.detach().contiguous(), warm_start=warm)
-    solver._autograd_generation = getattr(solver, "_autograd_generation", 0) + 1
-    solver.autograd_info = out["info"]
-    ctx.solver = solver
-    ctx.generation = solver._autograd_generation
-    return out["x"], out["y"], out["s"]
+    return _solved(ctx, solver, solver.solve_many_device(b=B.detach().contiguous(), c=C.detach().contiguous(), warm_start=warm))
 
   @staticmethod
   @torch.autograd.function.once_differentiable
   def backward(ctx, gx, gy, gs):
-    solver = ctx.solver
-    if getattr(solver, "_autograd_generation", 0) != ctx.generation:
-      raise RuntimeError("scs.autograd.solve_many: the solver was solved again before this backward; its resident solutions are others")
+    _still_resident(ctx, "solve_many", "solutions are others")
     if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
       return None, None, None
-    res = solver.adjoint_many_device(dx=gx.contiguous(), dy=gy.contiguous(), ds=gs.contiguous(), want=("b", "c"),
-                                     tol=getattr(solver, "autograd_tol", 1e-8))
-    solver.autograd_adjoint_info = res["info"]
+    res = ctx.solver.adjoint_many_device(dx=gx.contiguous(), dy=gy.contiguous(), ds=gs.contiguous(), want=("b", "c"),
+                                         tol=getattr(ctx.solver, "autograd_tol", 1e-8))
+    ctx.solver.autograd_adjoint_info = res["info"]
     return None, res["db"] if ctx.needs_input_grad[1] else None, res["dc"] if ctx.needs_input_grad[2] else None
 
 
