@@ -101,6 +101,17 @@ SCS_HIP_API int scs_hip_proj_cone(scs_float *x, const ScsCone *k, scs_int m, int
  * cones; the others are refused by name.  (parity tests) */
 SCS_HIP_API int scs_hip_dproj_cone(const scs_float *v, const scs_float *u, const ScsCone *cone, scs_int len, scs_float *out_Wu, scs_float *out_WmIu);
 
+/* The pack and sum kernels of scs_hip_adjoint_shared (below; csrc/grad_shared.hpp) on host stacks and nothing else: with X, DC (K x n) and
+ * Y, DB (K x m) row-major,
+ *     out_dA[p] = sum_k ( Y[k,i] DC[k,j] - DB[k,i] X[k,j] )     p = stored entry (i, j) of the m x n CSC pattern (Ap, Ai)
+ *     out_dP[q] = sum_k ( DC[k,c] X[k,r] + DC[k,r] X[k,c] ), c < r;  sum_k DC[k,r] X[k,r] on the diagonal     q = entry (c, r) of the
+ * CSC pattern (Pp, Pi) of an upper triangle of order n (Pp may be NULL: no P; an output may be NULL; an entry below the diagonal gets 0).
+ * An output without an entry launches nothing.  Two calls give the same bits.  0, or -1 with the reason in scs_hip_last_error (a pattern
+ * that is no pattern, K < 1).  (parity tests) */
+SCS_HIP_API int scs_hip_grad_matrix_sum(scs_int m, scs_int n, const scs_int *Ap, const scs_int *Ai, const scs_int *Pp, const scs_int *Pi, scs_int K,
+                                        const scs_float *X, const scs_float *Y, const scs_float *DB, const scs_float *DC, scs_float *out_dA,
+                                        scs_float *out_dP);
+
 /* The same projection applied to `count` vectors one after the other (xs: count x m, row-major, in place) through ONE set of cone
  * workspaces, warm-started from call to call as inside the ADMM loop (K9: eigenvectors of the previous call, periodic
  * re-orthogonalisation, refinement stage; box cone: the previous t).  stats (may be NULL): scs_hip_psd_refine_stats records of the
@@ -282,6 +293,29 @@ SCS_HIP_API scs_int scs_hip_adjoint_batch_device(ScsWork **w, const scs_float **
 SCS_HIP_API scs_int scs_hip_adjoint_batch(ScsWork **w, const scs_float **gx, const scs_float **gy, const scs_float **gs, scs_float **db,
                                           scs_float **dc, scs_float **dAx, scs_float **dPx, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info,
                                           scs_int count);
+/* The adjoint of `count` workspaces that SHARE one matrix set (a workspace and its scs_hip_clone's), with the gradients of the matrix
+ * values SUMMED over the members: the case of one learned matrix and a batch of right-hand sides.  gx .. dc are the arrays of
+ * scs_hip_adjoint_batch[_device]; the two matrix outputs are ONE vector each, dAx_sum of nnz(A) and dPx_sum of nnz(P) (triangle) values in
+ * the order of scs_hip_adjoint's dAx / dPx; either may be NULL.
+ *   The members are differentiated exactly as scs_hip_adjoint_batch[_device] does with dAx = dPx = NULL — the same grouping, the same
+ *   launches — so every member's db, dc and info (but time_ms) are bit for bit those of that call; a member whose db / dc is not asked for
+ *   keeps them in its own scratch.  Then the members' x, y, db, dc are packed, at most 256 members at a time, into panels with the member
+ *   index fastest, and one kernel per matrix walks the stored pattern ONCE per chunk (csrc/grad_shared.hpp):
+ *       dAx_sum[p] = sum_k ( y_k[i] dc_k[j] - db_k[i] x_k[j] ),    dPx_sum[q] = sum_k ( dc_k[c] x_k[r] + dc_k[r] x_k[c] )  (diagonal: once)
+ *   over all members in index order.  Nothing of K x nnz is formed: the call borrows 2 (n + m) min(K, 256) doubles of panels from the block
+ *   pool (the chunk is lowered where that would exceed 256 MiB, the cap of the grouped PSD preparation above) and returns them.  The order
+ *   of every sum is fixed by count and the chunk alone; there are no floating-point atomics, and two calls on the same state give the same
+ *   bits, as do the host and the device entry.
+ *   Refusals (-1, the reason with the member index in scs_hip_last_error, before any device work, every workspace usable): those of
+ *   scs_hip_adjoint_batch[_device]; a member that does not hold the matrix set of member 0 (scs_hip_shares_matrix); dPx_sum where
+ *   scs_hip_adjoint refuses dPx (no P, or a P whose values scs_hip_update_matrix would refuse); dAx_sum and dPx_sum both NULL.
+ * scs_hip_adjoint_shared takes HOST pointers, stages them and runs the device path (same bits). */
+SCS_HIP_API scs_int scs_hip_adjoint_shared_device(ScsWork **w, const scs_float **gx_dev, const scs_float **gy_dev, const scs_float **gs_dev,
+                                                  scs_float **db_dev, scs_float **dc_dev, scs_float *dAx_sum_dev, scs_float *dPx_sum_dev,
+                                                  const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count);
+SCS_HIP_API scs_int scs_hip_adjoint_shared(ScsWork **w, const scs_float **gx, const scs_float **gy, const scs_float **gs, scs_float **db,
+                                           scs_float **dc, scs_float *dAx_sum, scs_float *dPx_sum, const ScsHipDiffOpts *opts,
+                                           ScsHipDiffInfo **info, scs_int count);
 SCS_HIP_API scs_int scs_hip_derivative_batch_device(ScsWork **w, const scs_float **db_dev, const scs_float **dc_dev, scs_float **dx_dev,
                                                     scs_float **dy_dev, scs_float **ds_dev, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info,
                                                     scs_int count);

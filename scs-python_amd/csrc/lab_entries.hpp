@@ -320,6 +320,69 @@ int scs_hip_dproj_cone(const scs_float *v, const scs_float *u, const ScsCone *co
   }
 }
 
+// The pack and sum kernels of scs_hip_adjoint_shared (csrc/grad_shared.hpp) on host stacks: X, DC (K x n), Y, DB (K x m), row-major.
+// A: the CSC pattern (Ap, Ai) of an m x n matrix; P: the CSC pattern of an upper triangle of order n, or Pp == NULL.
+int scs_hip_grad_matrix_sum(scs_int m, scs_int n, const scs_int *Ap, const scs_int *Ai, const scs_int *Pp, const scs_int *Pi, scs_int K,
+                            const scs_float *X, const scs_float *Y, const scs_float *DB, const scs_float *DC, scs_float *out_dA,
+                            scs_float *out_dP) {
+  try {
+    set_last_error("");
+    const char *who = "scs_hip_grad_matrix_sum: ";
+    if (m < 0 || n < 0 || K < 1) throw std::runtime_error(std::string(who) + "m, n must not be negative and K must be positive");
+    if (!Ap || !X || !Y || !DB || !DC) throw std::runtime_error(std::string(who) + "null argument");
+    auto pattern_ok = [&](const scs_int *p, const scs_int *idx, long rows, const char *name) {
+      if (p[0] != 0) throw std::runtime_error(std::string(who) + name + ": column pointers do not start at 0");
+      for (long j = 0; j < n; ++j)
+        if (p[j + 1] < p[j]) throw std::runtime_error(std::string(who) + name + ": column pointers descend");
+      if (p[n] > 0 && !idx) throw std::runtime_error(std::string(who) + name + ": null row indices");
+      for (long q = 0; q < p[n]; ++q)
+        if (idx[q] < 0 || idx[q] >= rows) throw std::runtime_error(std::string(who) + name + ": row index out of range");
+    };
+    pattern_ok(Ap, Ai, m, "A");
+    if (Pp) pattern_ok(Pp, Pi, n, "P");
+    const long a_nnz = Ap[n], p_nnz = Pp ? Pp[n] : 0;
+    const bool do_a = out_dA && a_nnz > 0, do_p = out_dP && p_nnz > 0;
+    if (!do_a && !do_p) return 0;  // outputs without an entry: nothing is launched
+    TmpStream ts;
+    const size_t sn = (size_t)n, sm = (size_t)m, sK = (size_t)K;
+    DevBuf<int> ap, ai, pp, pi;
+    DevBuf<double> dX, dY, dDB, dDC, dA, dP;
+    GradSumJob job;
+    job.n = (int)n; job.m = (int)m;
+    dX.upload(X, sK * sn, ts.s);
+    dDC.upload(DC, sK * sn, ts.s);
+    if (do_a) {
+      ap.upload(Ap, sn + 1, ts.s);
+      ai.upload(Ai, (size_t)a_nnz, ts.s);
+      dY.upload(Y, sK * sm, ts.s);
+      dDB.upload(DB, sK * sm, ts.s);
+      dA.alloc_zero((size_t)a_nnz, ts.s);
+      job.a_rp = ap.p; job.a_ci = ai.p; job.a_nnz = a_nnz; job.dA = dA.p;
+    }
+    if (do_p) {  // the triangle's own columns are the rows the kernel walks: every entry lies on or above the diagonal
+      pp.upload(Pp, sn + 1, ts.s);
+      pi.upload(Pi, (size_t)p_nnz, ts.s);
+      dP.alloc_zero((size_t)p_nnz, ts.s);
+      job.p_rp = pp.p; job.p_ci = pi.p; job.p_up = pp.p; job.p_nnz = p_nnz; job.dP = dP.p;
+    }
+    std::vector<const double *> vx, vy, vb, vc;
+    for (size_t k = 0; k < sK; ++k) {
+      vx.push_back(dX.p + k * sn);
+      vc.push_back(dDC.p + k * sn);
+      vy.push_back(do_a ? dY.p + k * sm : nullptr);
+      vb.push_back(do_a ? dDB.p + k * sm : nullptr);
+    }
+    grad_sum_run(job, vx, vy, vb, vc, ts.s);
+    if (do_a) dA.download(out_dA, (size_t)a_nnz, ts.s);
+    if (do_p) dP.download(out_dP, (size_t)p_nnz, ts.s);
+    HIP_CHECK(hipStreamSynchronize(ts.s));
+    return 0;
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return -1;
+  }
+}
+
 int scs_hip_proj_cone_seq(scs_float *xs, const ScsCone *k_in, scs_int m, int dual, int count, scs_float *stats, int stats_cap) {
   const ScsCone k_short = short_cone(k_in);
   const ScsCone *k = k_in ? &k_short : nullptr;

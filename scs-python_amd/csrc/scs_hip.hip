@@ -51,6 +51,7 @@
 #include "perturb.hpp"
 #include "diff.hpp"
 #include "diff_batch.hpp"
+#include "grad_shared.hpp"
 
 // ================================================================ C ABI
 // A consumer compiled without USE_SPECTRAL_CONES hands over a ScsCone that ends at psize: the plain entry points copy that
@@ -698,11 +699,20 @@ int scs_hip_diff_batch_plan(ScsWork **works, scs_int count, int want_dA, int wan
 }
 long scs_hip_diff_group_launches(void) { return g_diff_group_launches.load(); }
 
-// dev: the members' pointers are device pointers; else host pointers, staged around the same path (same bits)
+// the two outputs of scs_hip_adjoint_shared[_device]: ONE vector each for all members (csrc/grad_shared.hpp); nullptr = not wanted
+struct SharedSum {
+  scs_float *dA = nullptr, *dP = nullptr;
+};
+// dev: the members' pointers are device pointers; else host pointers, staged around the same path (same bits).  sum: the members share
+// one matrix set and carry no dAx / dPx of their own; after they are differentiated as ever, the sums of their matrix gradients go to *sum.
 static scs_int diff_batch_entry(ScsWork **works, std::vector<DiffCall> calls, const ScsHipDiffOpts *o, ScsHipDiffInfo **infos, scs_int count,
-                                bool dev, const char *who) {
+                                bool dev, const char *who, const SharedSum *sum = nullptr) {
   set_last_error("");
   if (!diff_batch_members_ok(works, count, who)) return -1;
+  if (sum && !sum->dA && !sum->dP) {
+    set_last_error(std::string(who) + ": dAx_sum and dPx_sum are both NULL: nothing to sum");
+    return -1;
+  }
   const bool adjoint = calls[0].adjoint;  // (count >= 1: one call per member)
   std::vector<std::unique_lock<std::mutex>> locks;
   std::vector<hipStream_t> saved;
@@ -719,13 +729,38 @@ static scs_int diff_batch_entry(ScsWork **works, std::vector<DiffCall> calls, co
     std::vector<int> want((size_t)count, 0);
     for (int i = 0; i < count; ++i) {
       const DiffCall &call = calls[(size_t)i];
-      diff_check(works[i], call, dev, std::string(who) + ": member " + std::to_string(i), works[0]->device);
+      const std::string member = std::string(who) + ": member " + std::to_string(i);
+      if (sum) {  // the ladder of a member that asks for what the sums hold (the sum outputs stand in its dAx / dPx slots)
+        DiffCall asked = call;
+        asked.out[2] = sum->dA; asked.out[3] = sum->dP;
+        diff_check(works[i], asked, dev, member, works[0]->device);
+        if (!scs_hip_shares_matrix(works[i], works[0]))
+          throw std::runtime_error(member + ": does not share the matrix set of member 0 (scs_hip_clone): the matrix gradients of different matrices cannot be summed");
+      } else {
+        diff_check(works[i], call, dev, member, works[0]->device);
+      }
       want[(size_t)i] = adjoint ? ((call.out[2] ? 1 : 0) | (call.out[3] ? 2 : 0)) : ((call.pert[0] ? 1 : 0) | (call.pert[1] ? 2 : 0));
     }
     HIP_CHECK(hipSetDevice(works[0]->device));
     hipStream_t s = works[0]->stream;
     ArenaScope no_arena(nullptr);
     std::vector<DiffStage> stages(dev ? 0 : (size_t)count);  // host twins: every member's vectors
+    DevBuf<double> sum_a, sum_p;                               // ... and the two sums
+    GradSumJob gsum;
+    if (sum) {
+      ScsHipWork *w0 = works[0];
+      gsum.n = w0->n; gsum.m = w0->m;
+      gsum.a_rp = w0->At.rowptr.p; gsum.a_ci = w0->At.col.p; gsum.a_nnz = (long)w0->At.nnz;
+      gsum.dA = sum->dA; gsum.dP = sum->dP;
+      if (sum->dP) {
+        diff_build_tri(w0);  // (it may still refuse: before any member is differentiated)
+        gsum.p_rp = w0->Pf.rowptr.p; gsum.p_ci = w0->Pf.col.p; gsum.p_up = w0->diff.tri_up.p; gsum.p_nnz = w0->mats->p_nnz_in;
+      }
+      if (!dev) {
+        if (sum->dA) { sum_a.alloc((size_t)std::max(gsum.a_nnz, 1L)); gsum.dA = sum_a.p; }
+        if (sum->dP) { sum_p.alloc((size_t)std::max(gsum.p_nnz, 1L)); gsum.dP = sum_p.p; }
+      }
+    }
     if (!dev) {
       for (int i = 0; i < count; ++i) calls[(size_t)i] = stages[(size_t)i].stage(works[i], calls[(size_t)i], s);
       HIP_CHECK(hipStreamSynchronize(s));
@@ -758,6 +793,18 @@ static scs_int diff_batch_entry(ScsWork **works, std::vector<DiffCall> calls, co
       saved.clear();
       restored.clear();
     }
+    if (sum) {  // every member's db, dc lie in its own scratch (DiffWiring: tA, tP), its solution in solx, soly: all members, in index order
+      std::vector<const double *> X, Y, DB, DC;
+      for (int i = 0; i < count; ++i) {
+        const ScsHipWork *w = works[i];
+        X.push_back(w->solx.p); Y.push_back(w->soly.p); DB.push_back(w->diff.tA.p); DC.push_back(w->diff.tP.p);
+      }
+      grad_sum_run(gsum, X, Y, DB, DC, s);
+      if (!dev) {
+        if (sum->dA) sum_a.download(sum->dA, (size_t)gsum.a_nnz, s);
+        if (sum->dP) sum_p.download(sum->dP, (size_t)gsum.p_nnz, s);
+      }
+    }
     if (!dev) {
       for (int i = 0; i < count; ++i) stages[(size_t)i].fetch(works[i], s);
       HIP_CHECK(hipStreamSynchronize(s));
@@ -780,6 +827,16 @@ static scs_int adjoint_batch_entry(ScsWork **w, const scs_float **gx, const scs_
                                  at_or_null(dAx, i), at_or_null(dPx, i)));
   return diff_batch_entry(w, calls, opts, info, count, dev, who);
 }
+// the members as scs_hip_adjoint_batch[_device] takes them with dAx = dPx = NULL, then the two sums
+static scs_int adjoint_shared_entry(ScsWork **w, const scs_float **gx, const scs_float **gy, const scs_float **gs, scs_float **db, scs_float **dc,
+                                    scs_float *dAx_sum, scs_float *dPx_sum, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count,
+                                    bool dev, const char *who) {
+  std::vector<DiffCall> calls;
+  for (int i = 0; i < count; ++i)
+    calls.push_back(adjoint_call(at_or_null(gx, i), at_or_null(gy, i), at_or_null(gs, i), at_or_null(db, i), at_or_null(dc, i), nullptr, nullptr));
+  const SharedSum sum{dAx_sum, dPx_sum};
+  return diff_batch_entry(w, calls, opts, info, count, dev, who, &sum);
+}
 static scs_int derivative_batch_entry(ScsWork **w, const scs_float **db, const scs_float **dc, const scs_float **dAx, const scs_float **dPx,
                                       scs_float **dx, scs_float **dy, scs_float **ds, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info,
                                       scs_int count, bool dev, const char *who) {
@@ -797,6 +854,16 @@ scs_int scs_hip_adjoint_batch_device(ScsWork **w, const scs_float **gx_dev, cons
 scs_int scs_hip_adjoint_batch(ScsWork **w, const scs_float **gx, const scs_float **gy, const scs_float **gs, scs_float **db, scs_float **dc,
                               scs_float **dAx, scs_float **dPx, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count) {
   return adjoint_batch_entry(w, gx, gy, gs, db, dc, dAx, dPx, opts, info, count, /*dev=*/false, "scs_hip_adjoint_batch");
+}
+scs_int scs_hip_adjoint_shared_device(ScsWork **w, const scs_float **gx_dev, const scs_float **gy_dev, const scs_float **gs_dev, scs_float **db_dev,
+                                      scs_float **dc_dev, scs_float *dAx_sum_dev, scs_float *dPx_sum_dev, const ScsHipDiffOpts *opts,
+                                      ScsHipDiffInfo **info, scs_int count) {
+  return adjoint_shared_entry(w, gx_dev, gy_dev, gs_dev, db_dev, dc_dev, dAx_sum_dev, dPx_sum_dev, opts, info, count, /*dev=*/true,
+                              "scs_hip_adjoint_shared_device");
+}
+scs_int scs_hip_adjoint_shared(ScsWork **w, const scs_float **gx, const scs_float **gy, const scs_float **gs, scs_float **db, scs_float **dc,
+                               scs_float *dAx_sum, scs_float *dPx_sum, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count) {
+  return adjoint_shared_entry(w, gx, gy, gs, db, dc, dAx_sum, dPx_sum, opts, info, count, /*dev=*/false, "scs_hip_adjoint_shared");
 }
 scs_int scs_hip_derivative_batch_device(ScsWork **w, const scs_float **db_dev, const scs_float **dc_dev, scs_float **dx_dev, scs_float **dy_dev,
                                         scs_float **ds_dev, const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count) {

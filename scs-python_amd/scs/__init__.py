@@ -289,14 +289,17 @@ class SCS(object):
     return self._solver.derivative_device(db, dc, tol, max_iters, dA=dA, dP=dP)
 
 
-  def adjoint_many(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+  def adjoint_many(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None, reduce=None):
     """`adjoint` of the K problems the last `solve_many` solved, differentiated in lock step: dx (K, n), dy (K, m), ds (K, m), None = 0.
-    Returns K dicts like `adjoint()`, with the bits K separate calls would give."""
-    return self._solver.adjoint_many(dx, dy, ds, want, tol, max_iters)
+    Returns K dicts like `adjoint()`, with the bits K separate calls would give.  reduce="sum" (needs "A" or "P" in `want`): the gradients
+    of the shared matrix summed over the K problems, without a (K, nnz) stack — the pair (results, grads) of the K dicts without dA / dP
+    and {"dA": (nnz,), "dP": (nnz(P),)}."""
+    return self._solver.adjoint_many(dx, dy, ds, want, tol, max_iters, reduce=reduce)
 
-  def adjoint_many_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
-    """`adjoint_many` over (K, .) float64 torch tensors on the solver's GPU: {"db": (K, m), "dc": (K, n), ["dA"], ["dP"], "info": [K]}."""
-    return self._solver.adjoint_many_device(dx, dy, ds, want, tol, max_iters)
+  def adjoint_many_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None, reduce=None):
+    """`adjoint_many` over (K, .) float64 torch tensors on the solver's GPU: {"db": (K, m), "dc": (K, n), ["dA"], ["dP"], "info": [K]}.
+    reduce="sum": dA (nnz,) and dP (nnz(P),) are the sums over the K problems."""
+    return self._solver.adjoint_many_device(dx, dy, ds, want, tol, max_iters, reduce=reduce)
 
   def derivative_many(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
     """`derivative` of the K problems the last `solve_many` solved, in lock step: db (K, m), dc (K, n), dA (K, nnz(A)), dP (K, nnz(P)),
@@ -346,11 +349,12 @@ def _raw_solvers(solvers, who):
   return raw
 
 
-def adjoint_batch(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+def adjoint_batch(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None, reduce=None):
   """`SCS.adjoint` of several solved `SCS` objects as one batch: equally shaped problems are differentiated in lock step and share
   every kernel launch.  dx, dy, ds: one vector per solver (a sequence, or a (K, .) array); None, or a None entry, is 0.  Returns one
-  dict per solver, with the bits `.adjoint()` gives."""
-  return _scs_hip.adjoint_batch(_raw_solvers(solvers, "adjoint_batch"), dx, dy, ds, want, tol, max_iters)
+  dict per solver, with the bits `.adjoint()` gives.  reduce="sum" (needs "A" or "P" in `want`; the solvers are one solver and its
+  `clone()`s): (results, grads) — the dicts without dA / dP, and {"dA", "dP"} summed over the solvers."""
+  return _scs_hip.adjoint_batch(_raw_solvers(solvers, "adjoint_batch"), dx, dy, ds, want, tol, max_iters, reduce=reduce)
 
 
 def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
@@ -358,9 +362,9 @@ def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=Non
   return _scs_hip.derivative_batch(_raw_solvers(solvers, "derivative_batch"), db, dc, tol, max_iters, dA=dA, dP=dP)
 
 
-def adjoint_batch_device(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+def adjoint_batch_device(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None, reduce=None):
   """`adjoint_batch` over float64 torch tensors on the solvers' GPU (taken and returned)."""
-  return _scs_hip.adjoint_batch_device(_raw_solvers(solvers, "adjoint_batch_device"), dx, dy, ds, want, tol, max_iters)
+  return _scs_hip.adjoint_batch_device(_raw_solvers(solvers, "adjoint_batch_device"), dx, dy, ds, want, tol, max_iters, reduce=reduce)
 
 
 def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):

@@ -252,6 +252,11 @@ def _load():
     for fn in (lib.scs_hip_adjoint_batch, lib.scs_hip_adjoint_batch_device):
         fn.restype = c_int
         fn.argtypes = [_PV] + [_PV] * 7 + [C.POINTER(_ScsHipDiffOpts), C.POINTER(C.POINTER(_ScsHipDiffInfo)), c_int]
+    for fn in (lib.scs_hip_adjoint_shared, lib.scs_hip_adjoint_shared_device):  # (the two sums: one vector each, not an array of them)
+        fn.restype = c_int
+        fn.argtypes = [_PV] + [_PV] * 5 + [C.c_void_p] * 2 + [C.POINTER(_ScsHipDiffOpts), C.POINTER(C.POINTER(_ScsHipDiffInfo)), c_int]
+    lib.scs_hip_grad_matrix_sum.restype = c_int
+    lib.scs_hip_grad_matrix_sum.argtypes = [c_int, c_int, _PI, _PI, _PI, _PI, c_int, _PD, _PD, _PD, _PD, _PD, _PD]
     for fn in (lib.scs_hip_derivative_batch, lib.scs_hip_derivative_batch_device):
         fn.restype = c_int
         fn.argtypes = [_PV] + [_PV] * 5 + [C.POINTER(_ScsHipDiffOpts), C.POINTER(C.POINTER(_ScsHipDiffInfo)), c_int]
@@ -1045,9 +1050,10 @@ class SCS(object):
             raise ValueError("%d rows, but solve_many has solved %d member%s of this solver" % (K, have, "" if have == 1 else "s"))
         return [self] + self._many[:K - 1]
 
-    def _diff_many(self, kind, device, vals, want, tol, max_iters):
+    def _diff_many(self, kind, device, vals, want, tol, max_iters, reduce=None):
         """`kind` of the members the last solve_many solved: vals = (K, .) stacks in the order of kind.ins.  On the device the results
         are stacks too, and the one grouped call writes straight into their rows."""
+        kind = _diff_reduce(kind, reduce, want)
         self._refuse_dP(kind, vals)
         mem = _device_memory(self._device_index()) if device else _HOST
         lens = self._lens()
@@ -1055,20 +1061,23 @@ class SCS(object):
         members = self._many_members(K)
         return _diff_list(kind, mem, members, rows, [lens] * len(members), want, tol, max_iters, stacked=device)
 
-    def adjoint_many(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+    def adjoint_many(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None, reduce=None):
         """`adjoint` of the K members the last `solve_many` solved, in lock step (`adjoint_batch`): dx (K, n), dy (K, m), ds (K, m),
-        None = 0.  Returns the K dicts `adjoint` would return, with the same bits."""
-        return self._diff_many(_ADJOINT, False, (dx, dy, ds), want, tol, max_iters)
+        None = 0.  Returns the K dicts `adjoint` would return, with the same bits.  reduce="sum" (with "A" or "P" in `want`): the
+        members share this solver's matrix, and the gradients of its values come summed over them — the pair (results, grads) of the K
+        dicts without dA / dP and {"dA": (nnz,), "dP": (nnz(P),)} (include/scs_hip.h: scs_hip_adjoint_shared)."""
+        return self._diff_many(_ADJOINT, False, (dx, dy, ds), want, tol, max_iters, reduce)
 
     def derivative_many(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
         """`derivative` of the K members the last `solve_many` solved, in lock step: db (K, m), dc (K, n), dA (K, nnz(A)),
         dP (K, nnz(P)), None = 0."""
         return self._diff_many(_DERIVATIVE, False, (db, dc, dA, dP), None, tol, max_iters)
 
-    def adjoint_many_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+    def adjoint_many_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None, reduce=None):
         """`adjoint_many` over float64 torch tensors (K, .) on the solver's GPU: one grouped call that writes straight into the rows of
-        {"db": (K, m), "dc": (K, n), ["dA": (K, nnz)], ["dP"], "info": [K dicts]}."""
-        return self._diff_many(_ADJOINT, True, (dx, dy, ds), want, tol, max_iters)
+        {"db": (K, m), "dc": (K, n), ["dA": (K, nnz)], ["dP"], "info": [K dicts]}.  reduce="sum": the same dict with dA (nnz,) and
+        dP (nnz(P),) summed over the members; no (K, nnz) stack is formed."""
+        return self._diff_many(_ADJOINT, True, (dx, dy, ds), want, tol, max_iters, reduce)
 
     def derivative_many_device(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
         """`derivative_many` over float64 torch tensors (K, .) on the solver's GPU: {"dx": (K, n), "dy": (K, m), "ds": (K, m), "info"}."""
@@ -1411,11 +1420,26 @@ def batch_plan(solvers):
 # matrices; `outs` are the results under the names they are returned by (a dict in slot order).  `entry` is the stem of its four C entries: + "_batch" for a
 # list of members, + "_device" for device pointers.  `short`: the stem for a call whose matrix values are all None, which takes the
 # slots without them (scs_hip_derivative[_batch][_device] are the full entries with NULL dAx and dPx, under their own names).
-_DiffKind = collections.namedtuple("_DiffKind", "ins vectors outs entry short")
+# `summed`: the results that are ONE vector for all members of a list — the sum over them — where the others are one per member; a kind
+# with such results has list entries only, under its stem as it stands (scs_hip_adjoint_shared[_device]).
+_DiffKind = collections.namedtuple("_DiffKind", "ins vectors outs entry short summed")
 _ADJOINT = _DiffKind(ins=(("dx", "n"), ("dy", "m"), ("ds", "m")), vectors=3, outs={"db": "m", "dc": "n", "dA": "A", "dP": "P"},
-                     entry="scs_hip_adjoint", short=None)  # (`want` selects among the outputs: "b" is db ...)
+                     entry="scs_hip_adjoint", short=None, summed=())  # (`want` selects among the outputs: "b" is db ...)
 _DERIVATIVE = _DiffKind(ins=(("db", "m"), ("dc", "n"), ("dA", "A"), ("dP", "P")), vectors=2, outs={"dx": "n", "dy": "m", "ds": "m"},
-                        entry="scs_hip_derivative_full", short="scs_hip_derivative")
+                        entry="scs_hip_derivative_full", short="scs_hip_derivative", summed=())
+_ADJOINT_SUM = _ADJOINT._replace(entry="scs_hip_adjoint_shared", summed=("dA", "dP"))  # members of ONE matrix: `reduce="sum"`
+
+
+def _diff_reduce(kind, reduce, want):
+    """`reduce` of the adjoint of a list of members: None = every member's own dA / dP; "sum" = their sums over the members, which
+    needs "A" or "P" in `want`.  Returns the kind that serves the call."""
+    if reduce is None:
+        return kind
+    if not isinstance(reduce, str) or reduce != "sum":
+        raise ValueError("reduce must be None or 'sum', not %r" % (reduce,))
+    if isinstance(want, (tuple, list)) and not ("A" in want or "P" in want):
+        raise ValueError("reduce='sum' sums the gradients of the matrices: want must hold 'A' or 'P'")
+    return _ADJOINT_SUM
 
 # Where the vectors live.  check(solver, name, value, key, lens): one input, checked before the library is called, as it goes on;
 # zeros(shape): a result; address(vector): what C gets; ready(): right before the call; device: the GPU index, None on the host.
@@ -1458,7 +1482,7 @@ def _diff_entry(kind, mem, batch, ins):
     # dA is None and dP is None: the short entry (the same path in the library; a refusal then names the entry it always named)
     if kind.short and all(v is None for v in ins[kind.vectors:]):
         stem, ins = kind.short, ins[:kind.vectors]
-    return getattr(_lib, stem + ("_batch" if batch else "") + mem.suffix), ins
+    return getattr(_lib, stem + ("_batch" if batch and not kind.summed else "") + mem.suffix), ins
 
 
 def _diff_info_dict(info):
@@ -1532,12 +1556,13 @@ def _ptr_array(K, ptrs):
 
 
 def _diff_batch_call(fn, solvers, ptr_lists, opts):
-    """one call of a batch derivative entry under every member's lock; returns the K info dicts"""
+    """one call of a batch derivative entry under every member's lock; returns the K info dicts.  ptr_lists: per slot the K addresses
+    of an array argument (or None), or ONE address (an int) where the slot is one vector for all members"""
     K = len(solvers)
     with _locked(solvers) as works:
         infos = [_ScsHipDiffInfo() for _ in solvers]
         infp = (C.POINTER(_ScsHipDiffInfo) * K)(*[C.pointer(io) for io in infos])
-        rc = fn(works, *([_ptr_array(K, pl) for pl in ptr_lists] + [C.byref(opts), infp, K]))
+        rc = fn(works, *([pl if isinstance(pl, int) else _ptr_array(K, pl) for pl in ptr_lists] + [C.byref(opts), infp, K]))
         err = last_error() if rc != 0 else ""
     if rc != 0:
         raise ValueError("libscs_hip: " + err)
@@ -1547,18 +1572,21 @@ def _diff_batch_call(fn, solvers, ptr_lists, opts):
 def _diff_list(kind, mem, solvers, rows, lens, want, tol, max_iters, stacked=False):
     """`kind` of a list of distinct members in ONE call of its batch entry.  rows: what `_many_diff_args` made of the inputs; lens: each
     member's `_lens()`.  Returns one result dict per member — or (stacked: members of one shape) one dict of (K, .) stacks, whose rows
-    the call writes straight into, with the list of the K infos."""
+    the call writes straight into, with the list of the K infos.  The results a kind sums over the members (kind.summed) are one vector
+    each: an entry of the stacked dict, or — member by member — a second dict beside the list, (results, grads)."""
     K = len(solvers)
     opts = _diff_opts(tol, max_iters)
     chosen, sizes = _diff_chosen(kind, want), kind.outs
+    one = [k for k in chosen if k in kind.summed]
     if stacked:
-        out = cols = {k: mem.zeros((K, lens[0][sizes[k]])) for k in chosen}
+        out = cols = {k: mem.zeros(lens[0][sizes[k]] if k in one else (K, lens[0][sizes[k]])) for k in chosen}
     else:
-        out = [{k: mem.zeros(ln[sizes[k]]) for k in chosen} for ln in lens]
-        cols = {k: [o[k] for o in out] for k in chosen}
+        grads = {k: mem.zeros(lens[0][sizes[k]]) for k in one}
+        out = [{k: mem.zeros(ln[sizes[k]]) for k in chosen if k not in one} for ln in lens]
+        cols = {k: grads[k] if k in one else [o[k] for o in out] for k in chosen}
     fn, ins = _diff_entry(kind, mem, True, [rows[name] for name, _ in kind.ins])
     ptrs = [[mem.address(v) if v is not None else None for v in r] if r is not None else None for r in ins]
-    ptrs += [[mem.address(a) for a in cols[k]] if k in cols else None for k in kind.outs]
+    ptrs += [(int(mem.address(cols[k])) if k in one else [mem.address(a) for a in cols[k]]) if k in cols else None for k in kind.outs]
     mem.ready()
     infos = _diff_batch_call(fn, solvers, ptrs, opts)
     if stacked:
@@ -1566,11 +1594,12 @@ def _diff_list(kind, mem, solvers, rows, lens, want, tol, max_iters, stacked=Fal
     else:
         for o, info in zip(out, infos):
             o["info"] = info
-    return out
+    return (out, grads) if kind.summed and not stacked else out
 
 
-def _diff_batch(kind, device, who, solvers, vals, want, tol, max_iters):
+def _diff_batch(kind, device, who, solvers, vals, want, tol, max_iters, reduce=None):
     """`kind` of a list of solvers the caller names: vals = one sequence (or (K, .) array) per input, in the order of kind.ins"""
+    kind = _diff_reduce(kind, reduce, want)
     solvers = _batch_solvers(solvers, who)
     dev = None
     if device:
@@ -1579,18 +1608,20 @@ def _diff_batch(kind, device, who, solvers, vals, want, tol, max_iters):
             raise ValueError("%s: the solvers live on different GPUs" % who)
         dev = devs.pop() if devs else 0
     if not solvers:
-        return []
+        return ([], {}) if kind.summed else []
     lens = [sv._lens() for sv in solvers]
     have_P = all(sv._pattern["P"] is not None for sv in solvers)
     _, rows = _many_diff_args(_diff_spec(kind, vals, lens), len(solvers), want, have_P, device=dev)
     return _diff_list(kind, _device_memory(dev) if device else _HOST, solvers, rows, lens, want, tol, max_iters)
 
 
-def adjoint_batch(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+def adjoint_batch(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None, reduce=None):
     """`adjoint` of several solved backend `SCS` objects in one call (include/scs_hip.h: scs_hip_adjoint_batch): equally shaped members
     share every kernel launch of the LSQR iteration.  dx, dy, ds: sequences (or (K, .) arrays) with one vector per solver; None, or a
-    None entry, counts as 0.  Returns the list of dicts `adjoint` would return for each, with the same bits."""
-    return _diff_batch(_ADJOINT, False, "adjoint_batch", solvers, (dx, dy, ds), want, tol, max_iters)
+    None entry, counts as 0.  Returns the list of dicts `adjoint` would return for each, with the same bits.  reduce="sum" (with "A" or
+    "P" in `want`; the solvers must share one matrix: a solver and its `clone()`s): the pair (results, grads) — the dicts without
+    dA / dP, and {"dA", "dP"} summed over the solvers (scs_hip_adjoint_shared)."""
+    return _diff_batch(_ADJOINT, False, "adjoint_batch", solvers, (dx, dy, ds), want, tol, max_iters, reduce)
 
 
 def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
@@ -1600,9 +1631,9 @@ def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=Non
     return _diff_batch(_DERIVATIVE, False, "derivative_batch", solvers, (db, dc, dA, dP), None, tol, max_iters)
 
 
-def adjoint_batch_device(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+def adjoint_batch_device(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None, reduce=None):
     """`adjoint_batch` over float64 torch tensors on the solvers' GPU (taken and returned); same bits."""
-    return _diff_batch(_ADJOINT, True, "adjoint_batch_device", solvers, (dx, dy, ds), want, tol, max_iters)
+    return _diff_batch(_ADJOINT, True, "adjoint_batch_device", solvers, (dx, dy, ds), want, tol, max_iters, reduce)
 
 
 def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
@@ -1721,6 +1752,28 @@ def dproj_cone(v, u, cone):
     wu, wmiu = np.zeros_like(v), np.zeros_like(v)
     _check(_lib.scs_hip_dproj_cone(_pd(v), _pd(u), C.byref(k), v.shape[0], _pd(wu), _pd(wmiu)))
     return wu, wmiu
+
+
+def grad_matrix_sum(A, P, X, Y, DB, DC):
+    """(dA, dP): the summed matrix gradients of K members from their stacks X, DC (K, n) and Y, DB (K, m) over the patterns of the scipy
+    CSC matrices A (m x n) and P (an upper triangle of order n, or None: dP is None) — the pack and sum kernels of
+    `adjoint_many(reduce="sum")` on their own (include/scs_hip.h: scs_hip_grad_matrix_sum; tests)."""
+    m, n = A.shape
+    X, Y, DB, DC = (np.ascontiguousarray(v, dtype=np.float64) for v in (X, Y, DB, DC))
+    K = X.shape[0] if X.ndim == 2 else 0
+    for name, v, ln in (("X", X, n), ("Y", Y, m), ("DB", DB, m), ("DC", DC, n)):
+        if v.ndim != 2 or v.shape != (K, ln):
+            raise ValueError("%s must be a (K, %d) array" % (name, ln))
+    ap, ai = np.ascontiguousarray(A.indptr, dtype=np.int32), np.ascontiguousarray(A.indices, dtype=np.int32)
+    dA, dP, pp, pi = np.zeros(ai.shape[0]), None, None, None
+    if P is not None:
+        if P.shape != (n, n):
+            raise ValueError("P must be %d x %d" % (n, n))
+        pp, pi = np.ascontiguousarray(P.indptr, dtype=np.int32), np.ascontiguousarray(P.indices, dtype=np.int32)
+        dP = np.zeros(pi.shape[0])
+    _check(_lib.scs_hip_grad_matrix_sum(m, n, _pi(ap), _pi(ai), _pi(pp) if pp is not None else None, _pi(pi) if pi is not None else None,
+                                        K, _pd(X), _pd(Y), _pd(DB), _pd(DC), _pd(dA), _pd(dP) if dP is not None else None))
+    return dA, dP
 
 
 def trim_pool():

@@ -16,16 +16,16 @@ def solve_batch(solvers, warm_start=False):
     return _scs_hip.solve_batch(solvers, warm_start)
 
 
-def adjoint_batch(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
-    return _scs_hip.adjoint_batch(solvers, dx, dy, ds, want, tol, max_iters)
+def adjoint_batch(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None, reduce=None):
+    return _scs_hip.adjoint_batch(solvers, dx, dy, ds, want, tol, max_iters, reduce=reduce)
 
 
 def derivative_batch(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
     return _scs_hip.derivative_batch(solvers, db, dc, tol, max_iters, dA=dA, dP=dP)
 
 
-def adjoint_batch_device(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
-    return _scs_hip.adjoint_batch_device(solvers, dx, dy, ds, want, tol, max_iters)
+def adjoint_batch_device(solvers, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None, reduce=None):
+    return _scs_hip.adjoint_batch_device(solvers, dx, dy, ds, want, tol, max_iters, reduce=reduce)
 
 
 def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):

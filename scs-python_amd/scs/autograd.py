@@ -23,9 +23,15 @@ updated again (RuntimeError otherwise).  Double backward and torch forward mode 
 call `SCS.derivative_device(db, dc, dA=, dP=)`.
 
     X, Y, S = scs.autograd.solve_many(solver, B, C)
+    X, Y, S = scs.autograd.solve_many(solver, B, C, A=Ax, P=Px)
 
 is the same layer for K problems over the solver's matrix: B (K, m), C (K, n); forward is `solve_many_device` (warm-started from the
-second call on), backward is ONE `adjoint_many_device` call — the K members are differentiated in lock step."""
+second call on), backward is ONE `adjoint_many_device` call — the K members are differentiated in lock step.  A and P, when given,
+are the values of the ONE matrix the K problems share (as in `solve`): forward is `update_matrix_device` — which finishes the cached
+members; the solve makes new ones on the new values — then `solve_many_device`, from the second call on warm-started explicitly from
+the X, Y, S the layer returned last.  Backward stays one `adjoint_many_device` call whose `want` holds the inputs that need a
+gradient, with `reduce="sum"` when A or P is among them: their gradients are (nnz,) tensors, the sums over the K members, and no
+(K, nnz) stack is formed.  With A = P = None the layer makes the calls it always made."""
 import torch
 
 
@@ -85,25 +91,43 @@ def solve(solver, b, c, A=None, P=None):
 
 
 class _SolveMany(torch.autograd.Function):
+  """`_Solve` for K problems over the solver's matrix.  A, P: the values of the SHARED matrices as inputs, None = the solver's own"""
 
   @staticmethod
-  def forward(ctx, solver, B, C):
-    warm = bool(getattr(solver, "_autograd_generation", 0))
-    return _solved(ctx, solver, solver.solve_many_device(b=B.detach().contiguous(), c=C.detach().contiguous(), warm_start=warm))
+  def forward(ctx, solver, B, C, A, P):
+    ctx.matrix = A is not None or P is not None
+    if ctx.matrix:  # (finishes the cached clones, which read the matrix set: solve_many_device makes new ones on the new values)
+      solver.update_matrix_device(A.detach().contiguous() if A is not None else None, P.detach().contiguous() if P is not None else None)
+    B, C = B.detach().contiguous(), C.detach().contiguous()
+    last = getattr(solver, "_autograd_last_many", None)
+    if not ctx.matrix:
+      out = solver.solve_many_device(b=B, c=C, warm_start=bool(getattr(solver, "_autograd_generation", 0)))
+    elif last is not None and last[0].shape[0] == B.shape[0]:  # (the members start cold: the previous solutions go in explicitly)
+      out = solver.solve_many_device(b=B, c=C, warm_start=True, x=last[0], y=last[1], s=last[2])
+    else:
+      out = solver.solve_many_device(b=B, c=C, warm_start=False)
+    if ctx.matrix:
+      solver._autograd_last_many = (out["x"].detach(), out["y"].detach(), out["s"].detach())
+    return _solved(ctx, solver, out)
 
   @staticmethod
   @torch.autograd.function.once_differentiable
   def backward(ctx, gx, gy, gs):
     _still_resident(ctx, "solve_many", "solutions are others")
-    if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
-      return None, None, None
-    res = ctx.solver.adjoint_many_device(dx=gx.contiguous(), dy=gy.contiguous(), ds=gs.contiguous(), want=("b", "c"),
-                                         tol=getattr(ctx.solver, "autograd_tol", 1e-8))
+    need = ctx.needs_input_grad[1:5]
+    if not any(need):
+      return None, None, None, None, None
+    # (as _Solve.backward; the gradients of the shared A and P are the sums over the K members: reduce="sum")
+    want = tuple(k for k, nd in zip(("b", "c", "A", "P"), need) if nd) if ctx.matrix else ("b", "c")
+    reduce = dict(reduce="sum") if need[2] or need[3] else {}
+    res = ctx.solver.adjoint_many_device(dx=gx.contiguous(), dy=gy.contiguous(), ds=gs.contiguous(), want=want,
+                                         tol=getattr(ctx.solver, "autograd_tol", 1e-8), **reduce)
     ctx.solver.autograd_adjoint_info = res["info"]
-    return None, res["db"] if ctx.needs_input_grad[1] else None, res["dc"] if ctx.needs_input_grad[2] else None
+    return (None,) + tuple(res["d" + k] if nd else None for k, nd in zip(("b", "c", "A", "P"), need))
 
 
-def solve_many(solver, B, C):
-  """(X, Y, S), (K, .) tensors: the solutions of the solver's problem with the rows of B (K, m) and C (K, n) as data, differentiable
-  with respect to both."""
-  return _SolveMany.apply(solver, B, C)
+def solve_many(solver, B, C, A=None, P=None):
+  """(X, Y, S), (K, .) tensors: the solutions of the solver's problem with the rows of B (K, m) and C (K, n) as data and — when given —
+  the matrix values A, P (1-D tensors in the constructor's canonical order) shared by the K problems; differentiable with respect to
+  each tensor passed (the gradients of A and P are summed over the K problems)."""
+  return _SolveMany.apply(solver, B, C, A, P)

@@ -34,6 +34,16 @@ the workspace's stream, one W apply of the cone — the box cone in BOTH forms a
 --box-sizes adds the two forms of the box apply at further sizes (the crossing of the two forms: kDboxMultiMin).
 
   python tools/adjoint_bench.py --cones [--box-bounds 60000] [--pow-cones 4000] [--box-sizes 1000,4000,16000,60000,99999] [--out profiles/adjoint_box_pow.txt]
+
+--shared is the leg of the gradient of ONE matrix shared by a batch (csrc/grad_shared.hpp).  K config-5 members (config5_small, PSD cones
+included) over one matrix are solved by solve_many_device; then, interleaved and repeated, leg (a) = adjoint_many_device(want b, c, A)
+followed by .sum(0) over its (K, nnz) stack — the only way to that gradient before `reduce`, and the same entry with the same slots now —
+and leg (b) = adjoint_many_device(want b, c, A, reduce="sum").  Per leg: the time of a call to --tol under --lsqr-cap, the time of the
+gradient part (both legs capped at 1 LSQR iteration, tol 1e-300), and the device bytes a first call takes above the solve, on a freshly
+solved batch after scs_hip_trim_pool: the growth of pool_stats()["live_bytes"] (the library's blocks: scratch, tables, panels) and of
+torch's peak allocation (the results: the stack of leg (a) lives there).
+
+  python tools/adjoint_bench.py --shared [--shared-k 64,512] [--reps 5] [--out profiles/adjoint_shared.txt]
 """
 import argparse
 import os
@@ -269,6 +279,87 @@ def cones_leg(args):
             f.write(text + "\n")
 
 
+def shared_leg(args):
+    import torch
+    import scs
+    from scs import _scs_hip
+    import problem_gen as pg
+    if _scs_hip.device_count() < 1:
+        raise SystemExit("adjoint_bench: no HIP device (there is nothing to measure without one)")
+    data, K, n = make_workload("config5_sdp", pg, lambda z, K: _scs_hip.proj_cone(z, K, dual=True))
+    m, nnz = data["A"].shape[0], data["A"].nnz
+    want = ("b", "c", "A")
+    fmt = lambda v: "%8.2f [%8.2f .. %8.2f]" % (float(np.median(v)), min(v), max(v))
+    lines = ["adjoint_bench --shared: config-5 members (m %d, n %d, nnz(A) %d) over one matrix, want (b, c, A); tol %g, LSQR cap %d, ADMM cap %d; "
+             "%d interleaved repetitions, ms: median [min .. max]" % (m, n, nnz, args.tol, args.lsqr_cap, args.solve_iters, args.reps),
+             "leg (a) = adjoint_many_device(want) + dA.sum(0) (the call of the parent commit: the same entry, the same slots); leg (b) = "
+             "reduce=\"sum\"; gradient part = the same calls capped at 1 LSQR iteration; bytes = what a first call takes above the solve "
+             "(library blocks + torch peak)",
+             "%5s | %-30s | %-30s | %-12s | %-30s | %-30s | %-23s | %-23s | %10s | %s" % (
+                 "K", "(a) stack + sum ms", "(b) reduce=sum ms", "(a) spread", "(a) gradient part ms", "(b) gradient part ms", "(a) bytes lib + torch",
+                 "(b) bytes lib + torch", "K nnz 8", "max |dA_a - dA_b| / max |dA|")]
+
+    def solved(count):
+        rng = np.random.default_rng(count)
+        B = data["b"][None, :] * (1.0 + 1e-3 * rng.standard_normal((count, 1)))
+        C = data["c"][None, :] * (1.0 + 1e-3 * rng.standard_normal((count, 1)))
+        sv = scs.SCS(data, K, linear_solver=scs.LinearSolver.HIP_INDIRECT, verbose=False, eps_abs=1e-6, eps_rel=1e-6, max_iters=args.solve_iters)
+        sv.solve_many_device(b=torch.as_tensor(B).cuda(), c=torch.as_tensor(C).cuda())
+        g = [torch.as_tensor(rng.standard_normal((count, k_))).cuda() for k_ in (n, m, m)]
+        return sv, g
+
+    def leg_a(sv, g, tol, cap):
+        r = sv.adjoint_many_device(g[0], g[1], g[2], want=want, tol=tol, max_iters=cap)
+        return r["dA"].sum(0), r
+
+    def leg_b(sv, g, tol, cap):
+        r = sv.adjoint_many_device(g[0], g[1], g[2], want=want, tol=tol, max_iters=cap, reduce="sum")
+        return r["dA"], r
+
+    def first_call_bytes(count, leg):
+        sv, g = solved(count)
+        torch.cuda.synchronize()
+        _scs_hip.trim_pool()
+        torch.cuda.reset_peak_memory_stats()
+        lib0, t0 = _scs_hip.pool_stats()["live_bytes"], torch.cuda.memory_allocated()
+        leg(sv, g, 1e-300, 1)
+        torch.cuda.synchronize()
+        out = (_scs_hip.pool_stats()["live_bytes"] - lib0, torch.cuda.max_memory_allocated() - t0)
+        del sv, g
+        return out
+
+    for count in [int(v) for v in args.shared_k.split(",")]:
+        bytes_a, bytes_b = first_call_bytes(count, leg_a), first_call_bytes(count, leg_b)
+        sv, g = solved(count)
+        for leg in (leg_a, leg_b):  # (the first call of each kind allocates)
+            leg(sv, g, args.tol, args.lsqr_cap)
+            leg(sv, g, 1e-300, 1)
+        ms = {k: [] for k in ("a", "b", "a1", "b1")}
+        for _ in range(args.reps):
+            for key, leg, tol, cap in (("a", leg_a, args.tol, args.lsqr_cap), ("b", leg_b, args.tol, args.lsqr_cap), ("a1", leg_a, 1e-300, 1),
+                                       ("b1", leg_b, 1e-300, 1)):
+                t, out = timed(lambda: leg(sv, g, tol, cap), torch)
+                ms[key].append(t)
+                if key == "a":
+                    dA_a = out[0]
+                if key == "b":
+                    dA_b, iters = out[0], [i["iters"] for i in out[1]["info"]]
+        spread = max(ms["a"]) - min(ms["a"])
+        verdict = "not slower" if float(np.median(ms["b"])) <= float(np.median(ms["a"])) + spread else "SLOWER"
+        diff = float((dA_a - dA_b).abs().max() / dA_a.abs().max())
+        lines.append("%5d | %-30s | %-30s | %-12s | %-30s | %-30s | %10d + %10d | %10d + %10d | %10d | %.2e" % (
+            count, fmt(ms["a"]), fmt(ms["b"]), "%.2f ms" % spread, fmt(ms["a1"]), fmt(ms["b1"]), bytes_a[0], bytes_a[1], bytes_b[0], bytes_b[1],
+            count * nnz * 8, diff))
+        lines.append("%5d   (b) against (a) + its spread: %s; LSQR iterations min %d max %d; panels of (b): 2 (n + m) min(K, 256) 8 = %d bytes" % (
+            count, verdict, min(iters), max(iters), 2 * (n + m) * min(count, 256) * 8))
+        del sv, g
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="target_lp_soc,target_qp,config5_member,config5_sdp,config4_psd")
@@ -285,6 +376,8 @@ def main():
     ap.add_argument("--pow-cones", type=int, default=4000)
     ap.add_argument("--box-sizes", default="1000,4000,16000,60000,99999")
     ap.add_argument("--kernel-reps", type=int, default=200)
+    ap.add_argument("--shared", action="store_true", help="the leg of the summed gradient of a shared matrix (reduce=\"sum\")")
+    ap.add_argument("--shared-k", default="64,512")
     ap.add_argument("--child-derivative", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--root", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -294,6 +387,8 @@ def main():
         return matrix_leg(args)
     if args.cones:
         return cones_leg(args)
+    if args.shared:
+        return shared_leg(args)
 
     import torch
     import scs
