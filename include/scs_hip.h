@@ -337,6 +337,29 @@ SCS_HIP_API scs_int scs_hip_derivative_full_batch(ScsWork **w, const scs_float *
 SCS_HIP_API int scs_hip_diff_batch_plan(ScsWork **w, scs_int count, int want_dA, int want_dP, scs_int *group_of);
 /* grouped launches issued by the batch derivative entries since the process started (tests, tools; as scs_hip_tiled_launches) */
 SCS_HIP_API long scs_hip_diff_group_launches(void);
+/* Several directions at ONE solution: K cotangents (adjoint) or K perturbations (derivative) of the workspace's last solve in one call.
+ * The arrays are row-major, one direction per row: GX K x n, GY and GS K x m (NULL = zeros, as in scs_hip_adjoint), DB K x m, DC K x n,
+ * DAx K x nnz(A), DPx K x nnz(P) (NULL = not wanted); for the derivative DB K x m and DC K x n in, DX K x n, DY and DS K x m out.
+ * infos: K entries, or NULL.  The preparation (the fixed point, the cone records, the eigen-decomposition of the PSD blocks) runs once,
+ * then the K directions are K LSQR lanes on the one workspace in lock step: one launch per kernel for all lanes, and the products read
+ * A, A' and P once per tile of lanes.  Every direction's outputs and info (apart from time_ms, which is the call's) have the bits of
+ * scs_hip_adjoint / scs_hip_derivative on that direction alone.  A workspace whose layouts the grouped derivative does not cover
+ * (column-sorted or slab layouts, PSD orders above 32, a long box cone) is served one direction after the other, same bits.
+ * Refusals as the single entries', and K < 1 or K > 32 (the caller chunks; the lanes beyond the first cost 8 m + 6 n doubles each and
+ * are kept until scs_finish).  The host twins stage the arrays like the single entries do. */
+SCS_HIP_API scs_int scs_hip_adjoint_multi_device(ScsWork *w, scs_int K, const scs_float *GX_dev, const scs_float *GY_dev,
+                                                 const scs_float *GS_dev, scs_float *DB_dev, scs_float *DC_dev, scs_float *DAx_dev,
+                                                 scs_float *DPx_dev, const ScsHipDiffOpts *opts, ScsHipDiffInfo *infos);
+SCS_HIP_API scs_int scs_hip_adjoint_multi(ScsWork *w, scs_int K, const scs_float *GX, const scs_float *GY, const scs_float *GS, scs_float *DB,
+                                          scs_float *DC, scs_float *DAx, scs_float *DPx, const ScsHipDiffOpts *opts, ScsHipDiffInfo *infos);
+SCS_HIP_API scs_int scs_hip_derivative_multi_device(ScsWork *w, scs_int K, const scs_float *DB_dev, const scs_float *DC_dev,
+                                                    scs_float *DX_dev, scs_float *DY_dev, scs_float *DS_dev, const ScsHipDiffOpts *opts,
+                                                    ScsHipDiffInfo *infos);
+SCS_HIP_API scs_int scs_hip_derivative_multi(ScsWork *w, scs_int K, const scs_float *DB, const scs_float *DC, scs_float *DX, scs_float *DY,
+                                             scs_float *DS, const ScsHipDiffOpts *opts, ScsHipDiffInfo *infos);
+/* lanes per workgroup of the multi entries' products: sets 4 or 8 (anything else: only reads) and returns the previous value.  For
+ * tools/adjoint_multi_bench.py, which measures both; the results do not depend on it. */
+SCS_HIP_API int scs_hip_diff_lane_tile(int tile);
 /* the HIP device a workspace lives on (-1: NULL) */
 SCS_HIP_API int scs_hip_work_device(const ScsWork *w);
 

@@ -31,6 +31,14 @@
 //
 // A call reads solx / soly / sols and the matrices, and writes the workspace's DiffScratch only (the eigen-decomposition of the PSD
 // blocks borrows a block of the pool for the call; the solve's psd_scratch is not touched).
+//
+// Lanes (lsqr.hpp DiffScratch / DiffLane).  The scratch has a part that belongs to the SOLUTION — vhat, the cone records, the PSD
+// tables, the box state, the power cones' W, tri_up: what the preparation writes and every apply of W reads — and a part that belongs
+// to ONE right-hand side, a lane: the LSQR vectors, the product slots, the partials, the state and flag blocks.  Lane 0 is the scratch
+// itself and all a one-direction call touches.  K directions at one solution (scs_hip_adjoint_multi / scs_hip_derivative_multi,
+// csrc/scs_hip.hip diff_multi_entry) prepare once and then run K lanes: diff_wiring(w, call, lane) wires lane `lane` exactly as it
+// wires lane 0, GroupDiff takes the (workspace, lane) pairs as its members, and the three SpMVs of a DiffProduct read the matrix once
+// per tile of lanes (spmv_lanes.hpp).  Where GroupDiff::member_ok does not hold the K directions go through diff_impl in turn on lane 0.
 #pragma once
 
 namespace scship {
@@ -222,6 +230,17 @@ static void diff_alloc(ScsHipWork *w) {
   d.fl.alloc(LF_COUNT);
   d.ready = true;
 }
+// lanes 1 .. K-1 of a call that differentiates K directions at once (lsqr.hpp DiffLane): taken at the first call that needs them
+static void diff_alloc_lanes(ScsHipWork *w, int K) {
+  diff_alloc(w);
+  DiffScratch &d = w->diff;
+  ArenaScope no_arena(nullptr);
+  while ((int)d.more.size() + 1 < K) {
+    std::unique_ptr<DiffLane> L(new DiffLane());
+    L->alloc_lane((size_t)w->n, (size_t)w->m, (size_t)vec_blocks((long)w->n + w->m));
+    d.more.push_back(std::move(L));
+  }
+}
 
 // column pointers of the caller's triangle of P from the resident full matrix (once per workspace)
 static void diff_build_tri(ScsHipWork *w) {
@@ -276,7 +295,7 @@ struct DiffProduct {
   LsqrProd read;
 };
 
-// Which buffer of a workspace's DiffScratch holds what during one call: the one place where slots are aliased and products are wired.
+// Which buffer of one lane of a workspace's DiffScratch holds what during one call: the one place where slots are aliased and products are wired.
 // Both call paths read it: diff_impl launches from it, GroupDiff::run (diff_batch.hpp) fills its tables from it.
 struct DiffWiring {
   // adjoint right-hand side: k_adj_in leaves gx^ in uh[0..n), gy^ in gyh = x[n..) and gs^ in gsh = tA (both free until LSQR starts);
@@ -294,8 +313,8 @@ struct DiffWiring {
   double *dc = nullptr, *db = nullptr;
   DprojIo fin{};
 };
-static DiffWiring diff_wiring(ScsHipWork *w, const DiffCall &a) {
-  DiffScratch &d = w->diff;
+static DiffWiring diff_wiring(ScsHipWork *w, const DiffCall &a, int lane = 0) {
+  DiffLane &d = w->diff.lane(lane);
   const int n = w->n;
   const double *tP = w->has_P ? d.tP.p : nullptr;
   auto J = [&](const double *q) {
@@ -317,8 +336,8 @@ static DiffWiring diff_wiring(ScsHipWork *w, const DiffCall &a) {
   } else {
     wr.db_in = a.in[0]; wr.dc_in = a.in[1];
     if (a.perturbs()) {
-      wr.dc_in = wr.eff_c = d.eff.p;
-      wr.db_in = wr.eff_b = d.eff.p + n;
+      wr.dc_in = wr.eff_c = w->diff.eff.p;
+      wr.db_in = wr.eff_b = w->diff.eff.p + n;
     }
     wr.pv = Jt(d.uh.p); wr.pu = J(d.vh.p);
     wr.fin = DprojIo{d.x.p + n, nullptr, d.dW.p, d.dWmI.p};

@@ -16,6 +16,12 @@
 // and until the host has seen its flag its kernels return at once on its own done flag.  Per chunk of iterations ONE gather launch
 // and ONE copy of G x LF_COUNT ints cross the host.  Each member keeps its own DiffScratch; the group owns the argument tables, the
 // member lists and the two gathered blocks, and gives its device blocks back to the block pool when the call ends.
+//
+// A member is a (workspace, lane) pair (lsqr.hpp DiffLane).  In a batch every member is lane 0 of a workspace of its own.  In a multi
+// call (scs_hip_adjoint_multi: K directions at ONE solution, one_work) the members are lanes 0 .. K-1 of one workspace: the preparation
+// runs for member 0 alone (it writes what belongs to the solution), every other table holds one record per lane as ever, and the three
+// SpMVs of a product go through k_spmv_stream_lanes (spmv_lanes.hpp), which reads the one matrix once per tile of lanes.  Iteration
+// state, stopping rule, done flag and the member list work per lane exactly as they work per workspace.
 #pragma once
 
 namespace scship {
@@ -35,11 +41,20 @@ inline void launch_grouped_k(const GTable<Fn, Threads, A...> &t, const int *list
 }
 
 static std::atomic<long> g_diff_group_launches{0};  // scs_hip_diff_group_launches(): tests, tools/adjoint_batch_bench.py
+// lanes of one workspace per workgroup of the lanes' product (spmv_lanes.hpp): 4 or 8.  4 by the table of profiles/adjoint_multi.txt
+// (the measured problems have few row blocks: at tile 8 half as many workgroups each serve twice the lanes in turn, and a call of
+// K >= 8 lanes took 1.2 - 1.4 times as long); scs_hip_diff_lane_tile() moves it for tools/adjoint_multi_bench.py, which measures both.
+static std::atomic<int> g_diff_lane_tile{4};
 
 constexpr size_t kDiffPsdBorrowMax = (size_t)256 << 20;  // K9-layout scratch borrowed at once by the grouped decomposition (bytes)
 
 struct GroupDiff {
+  // A member is (workspace, lane): a batch has G workspaces on their lane 0; a multi call (scs_hip_adjoint_multi, one_work) has ONE
+  // solved workspace whose K directions are the members W[g] = w, lane[g] = g.  Then the preparation — what belongs to the solution —
+  // runs for member 0 alone, and the three products of a DiffProduct read the matrix once per lane tile (spmv_lanes.hpp).
   std::vector<ScsHipWork *> W;
+  std::vector<int> lane;  // empty: every member on lane 0
+  bool one_work = false;
   std::vector<DiffCall> calls;
   std::vector<ScsHipDiffInfo *> infos;
   bool adjoint = true;
@@ -116,6 +131,7 @@ struct GroupDiff {
   double *st_h = nullptr;
   std::vector<DprojPlan> plans;
   long launches = 0;
+  int lane_tile = 4;
 
   ~GroupDiff() {
     if (s && hipStreamSynchronize(s) == hipSuccess) {  // the stream is drained: the group's device blocks are the pool's
@@ -171,12 +187,17 @@ struct GroupDiff {
     go(d.soc, list, count);
     go(d.soc_big, list, count);
   }
+  template <class T> void go_spmv(const T &t, const int *list, int count) {
+    if (!one_work) return go(t, list, count);
+    launch_lanes(t, list, count, lane_tile, s);
+    if (t.used && count > 0 && t.gx > 0) ++launches;
+  }
   void go_prod(const ProdTabs &p, const int *list, int count) {  // (the order of a DiffProduct)
     if (!p.transposed) go_dproj(p.dp, list, count);
-    go(p.ar, list, count);
+    go_spmv(p.ar, list, count);
     if (p.transposed) go_dproj(p.dp, list, count);
-    go(p.at, list, count);
-    go(p.pf, list, count);
+    go_spmv(p.at, list, count);
+    go_spmv(p.pf, list, count);
   }
   void sync() {
     HIP_CHECK(hipGetLastError());  // (launches are not checked one by one)
@@ -199,6 +220,8 @@ struct GroupDiff {
     const int nbN = vec_blocks(N);
     const bool want_dA = adjoint && calls[0].out[2], want_dP = adjoint && calls[0].out[3];
     ArenaScope no_arena(nullptr);
+    lane_tile = g_diff_lane_tile.load() == 8 ? 8 : 4;
+    const int GP = one_work ? 1 : G;  // members that prepare: the first of each workspace
 
     HIP_CHECK(hipHostMalloc((void **)&flags_h, sizeof(int) * LF_COUNT * G));
     HIP_CHECK(hipHostMalloc((void **)&lists_h, sizeof(int) * 2 * G));
@@ -225,7 +248,7 @@ struct GroupDiff {
     if (p0.sym3.count > 0) { t_pow_prep.resize(SG); t_pow_prep.gx = ceil_div(p0.sym3.count, kConeThreads); }
     // the decomposition borrows K9-layout scratch for a slice of the members at a time (stream order protects its reuse)
     const size_t per_member = (size_t)std::max(p0.psd.scratch_doubles, 1L);
-    const int slice = (int)std::max<size_t>(1, std::min<size_t>(SG, kDiffPsdBorrowMax / (per_member * sizeof(double))));
+    const int slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)GP, kDiffPsdBorrowMax / (per_member * sizeof(double))));
     DevBuf<double> psd_scratch;
     if (p0.psd.count > 0) {
       psd_scratch.alloc(per_member * (size_t)slice);
@@ -264,7 +287,8 @@ struct GroupDiff {
     const PsdRefineCfg refine_off = psd_refine_default(false);
     for (int g = 0; g < G; ++g) {
       ScsHipWork *w = W[(size_t)g];
-      DiffScratch &d = w->diff;
+      const int ln = lane.empty() ? 0 : lane[(size_t)g];
+      DiffLane &d = w->diff.lane(ln);
       const DiffCall &a = calls[(size_t)g];
       const DprojPlan &plan = plans[(size_t)g];
       const double *D = w->normalized ? w->D.p : nullptr, *E = w->normalized ? w->E.p : nullptr;
@@ -272,7 +296,7 @@ struct GroupDiff {
       gx_ar = std::max(gx_ar, w->Ar.view().csr.nblk);
       gx_at = std::max(gx_at, w->At.view().csr.nblk);
       if (has_P) gx_pf = std::max(gx_pf, w->Pf.view().csr.nblk);
-      t_vhat.set(g, (const double *)w->sols.p, (const double *)w->soly.p, D, sigma, m, d.vhat.p);
+      t_vhat.set(g, (const double *)w->sols.p, (const double *)w->soly.p, D, sigma, m, w->diff.vhat.p);
       if (t_prep_wave.used) t_prep_wave.set(g, plan.vh, plan.off, plan.dim, plan.n_soc, plan.G, plan.cinfo);
       if (t_prep_block.used) t_prep_block.set(g, plan.vh, plan.off, plan.dim, plan.big, plan.cinfo);
       if (t_box_prep.used) t_box_prep.set(g, plan.vh + plan.box.off, plan.box.bl, plan.box.bu, plan.box.bsize, plan.box.tmp, plan.box.st);
@@ -284,7 +308,7 @@ struct GroupDiff {
                       (const int *)nullptr, plan.psd.tol2, refine_off, 0);
         t_psd_gather.set(g, plan.psd, (const double *)scr, plan.vh);
       }
-      const DiffWiring wr = diff_wiring(w, a);
+      const DiffWiring wr = diff_wiring(w, a, ln);
       const int *done = d.fl.p + LF_DONE;
       // right-hand side and results: the kernels of the call's direction
       if (adjoint) {
@@ -300,7 +324,7 @@ struct GroupDiff {
           gx_ga = std::max(gx_ga, vec_blocks((long)w->At.nnz));
         }
         if (want_dP) {
-          t_grad_p.set(g, (const int *)w->Pf.rowptr.p, (const int *)w->Pf.col.p, n, (long)w->Pf.nnz, (const int *)d.tri_up.p,
+          t_grad_p.set(g, (const int *)w->Pf.rowptr.p, (const int *)w->Pf.col.p, n, (long)w->Pf.nnz, (const int *)w->diff.tri_up.p,
                        (const double *)w->solx.p, (const double *)wr.dc, a.out[3]);
           gx_gp = std::max(gx_gp, vec_blocks((long)w->Pf.nnz));
         }
@@ -334,10 +358,10 @@ struct GroupDiff {
     for_tables([&](auto &t) { t.upload(s); });
 
     // ---- the fixed point and the cone records ----
-    go(t_vhat, all_d, G);
+    go(t_vhat, all_d, GP);
     if (t_psd_eig.used) {
-      for (int lo = 0; lo < G; lo += slice) {
-        const int cnt = std::min(slice, G - lo);
+      for (int lo = 0; lo < GP; lo += slice) {
+        const int cnt = std::min(slice, GP - lo);
         go(t_psd_copy, all_d + lo, cnt);
         go(t_psd_eig, all_d + lo, cnt);
         go(t_psd_gather, all_d + lo, cnt);
@@ -347,10 +371,10 @@ struct GroupDiff {
       psd_scratch.release();
       --t_pool_release;
     }
-    go(t_box_prep, all_d, G);  // (the order of launch_dproj_prep: after the PSD blocks, whose tmp_m holds box.tmp)
-    go(t_pow_prep, all_d, G);
-    go(t_prep_wave, all_d, G);
-    go(t_prep_block, all_d, G);
+    go(t_box_prep, all_d, GP);  // (the order of launch_dproj_prep: after the PSD blocks, whose tmp_m holds box.tmp)
+    go(t_pow_prep, all_d, GP);
+    go(t_prep_wave, all_d, GP);
+    go(t_prep_block, all_d, GP);
 
     // ---- right-hand side into uh, x = w = 0 ----
     if (adjoint) {

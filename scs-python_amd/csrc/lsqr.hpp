@@ -16,6 +16,8 @@
 // is up.  Stopping: the standard rules with atol = btol = tol (1: |r| <= tol |g| + tol |M| |x|; 2: |M' r| <= tol |M| |r|) and an
 // iteration cap (3).  All sums have a fixed order: two calls on the same state give the same bits.
 #pragma once
+#include <memory>
+
 #include "common.hpp"
 #include "vec.hpp"
 
@@ -188,16 +190,39 @@ __global__ __launch_bounds__(kVecThreads) void k_lsqr_u(int k, LsqrProd tu, doub
 }
 
 // Scratch of the derivative entry points (diff.hpp): taken from the block pool at a workspace's first call, kept until scs_finish.
-// 4 vectors of n + m (uh, vh, w, x), 4 of m (tA, dW, dWmI, vhat), 2 of n (tAt, tP): 8 m + 6 n doubles, plus partials and cone records,
-// plus 4 NP^2 + NP doubles per PSD block (dproj_psd.hpp DprojPsdTables: V, V', lam, two apply frames).
-struct DiffScratch {
+// It has two parts.
+//   What belongs to the SOLUTION (DiffScratch): the fixed point vhat, the SOC records cinfo, the PSD tables' V / V' / lam, the box state
+//   and ticket, the power cones' W (sym3) and the triangle's column pointers tri_up.  One per workspace, written by the preparation.
+//   What belongs to ONE RIGHT-HAND SIDE, a lane (DiffLane): the LSQR vectors uh, vh, w, x (n + m each), the product slots tA, dW, dWmI
+//   (m) and tAt, tP (n), the norm partials, the state and flag blocks: 8 m + 6 n doubles plus partials.
+// Lane 0 is the scratch itself (DiffScratch derives from DiffLane): every one-direction entry point uses it and nothing else.  Lanes
+// 1 .. K-1 are taken from the block pool at the first call that differentiates K directions at once (diff.hpp diff_alloc_lanes), kept
+// until scs_finish and returned to the pool with the rest.  The two apply frames of a PSD block (dproj_psd.hpp: 2 NP^2 doubles of the
+// 4 NP^2 + NP per block) are per right-hand side too, but only the five-launch tile path touches them, and that path never runs in
+// lock step (GroupDiff::member_ok): they stay where they are, inside lane 0's frames.
+constexpr int kDiffLanesMax = 32;  // directions of one multi call (include/scs_hip.h)
+struct DiffLane {
+  DevBuf<double> uh, vh, w, x, tA, dW, dWmI, tAt, tP, partU, partV, partX, st;
+  DevBuf<int> fl;
+  void alloc_lane(size_t n, size_t m, size_t nb) {
+    for (DevBuf<double> *b : {&uh, &vh, &w, &x}) b->alloc(n + m);
+    for (DevBuf<double> *b : {&tA, &dW, &dWmI}) b->alloc(m);
+    for (DevBuf<double> *b : {&tAt, &tP}) b->alloc(n);
+    for (DevBuf<double> *b : {&partU, &partV, &partX}) b->alloc(nb);
+    st.alloc(L_COUNT);
+    fl.alloc(LF_COUNT);
+  }
+};
+struct DiffScratch : DiffLane {
   bool ready = false, tri_ready = false;
-  DevBuf<double> uh, vh, w, x, tA, dW, dWmI, vhat, tAt, tP, cinfo, partU, partV, partX, st;
+  DevBuf<double> vhat, cinfo;
   DprojPsdTables psd;
   DevBuf<double> box, sym3;     // the box cone's state (dbox_scratch_doubles) and the power cones' W (6 per cone); none of either: not allocated
   DevBuf<unsigned> box_ticket;  // (k_proj_box_round, box cones above kDboxMultiMin only)
-  DevBuf<int> fl, tri_up;  // tri_up: column pointers of the caller's triangle of P (the gather of dL/dP), built at the first request
+  DevBuf<int> tri_up;      // column pointers of the caller's triangle of P (the gather of dL/dP), built at the first request
   DevBuf<double> eff;      // (dc_eff ; db_eff) of a forward call that perturbs A or P (perturb.hpp): n + m, taken at the first such call
+  std::vector<std::unique_ptr<DiffLane>> more;  // lanes 1 ..
+  DiffLane &lane(int k) { return k == 0 ? static_cast<DiffLane &>(*this) : *more[(size_t)k - 1]; }
 };
 
 }  // namespace scship

@@ -50,6 +50,7 @@
 #include "matrix_update.hpp"
 #include "perturb.hpp"
 #include "diff.hpp"
+#include "spmv_lanes.hpp"
 #include "diff_batch.hpp"
 #include "grad_shared.hpp"
 
@@ -884,6 +885,101 @@ scs_int scs_hip_derivative_full_batch(ScsWork **w, const scs_float **db, const s
 scs_int scs_hip_derivative_batch(ScsWork **w, const scs_float **db, const scs_float **dc, scs_float **dx, scs_float **dy, scs_float **ds,
                                  const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count) {
   return derivative_batch_entry(w, db, dc, nullptr, nullptr, dx, dy, ds, opts, info, count, /*dev=*/false, "scs_hip_derivative_batch");
+}
+
+// ---- several directions at one solution (include/scs_hip.h; lanes: csrc/lsqr.hpp, csrc/diff_batch.hpp, csrc/spmv_lanes.hpp) ----
+int scs_hip_diff_lane_tile(int tile) {
+  if (tile == 4 || tile == 8) return g_diff_lane_tile.exchange(tile);
+  return g_diff_lane_tile.load();
+}
+// base: the call of direction 0 — row 0 of every array.  Direction k reads and writes row k.
+static scs_int diff_multi_entry(ScsWork *w, scs_int K, DiffCall base, const ScsHipDiffOpts *o, ScsHipDiffInfo *infos, bool dev, const char *who) {
+  if (!w) {
+    set_last_error(std::string(who) + ": null workspace");
+    return -1;
+  }
+  try {
+    set_last_error("");
+    std::lock_guard<std::mutex> lock(w->mtx);
+    diff_check(w, base, /*dev=*/false, who);
+    if (K < 1) throw std::runtime_error(std::string(who) + ": K = " + std::to_string((long)K) + ": at least one direction");
+    if (K > kDiffLanesMax)
+      throw std::runtime_error(std::string(who) + ": K = " + std::to_string((long)K) + " exceeds the limit of " + std::to_string(kDiffLanesMax) +
+                               " directions per call");
+    if (dev) diff_check_device(w, base, who);
+    HIP_CHECK(hipSetDevice(w->device));
+    ScsHipWork::ScratchTurn turn(w);
+    hipStream_t s = w->stream;
+    ArenaScope no_arena(nullptr);
+    const size_t SK = (size_t)K;
+    DevBuf<double> bin[3], bout[4];
+    const DiffCall host = base;
+    if (!dev) {  // the host twin: K rows of every array through the staging of the single entries (DiffStage), in one copy each
+      for (int k = 0; k < 3; ++k)
+        if (host.in[k]) {
+          bin[k].upload(host.in[k], SK * (size_t)host.in_len(w, k), s);
+          base.in[k] = bin[k].p;
+        }
+      for (int k = 0; k < 4; ++k)
+        if (host.out[k]) {
+          bout[k].alloc(std::max(SK * (size_t)host.out_len(w, k), (size_t)1));
+          base.out[k] = bout[k].p;
+        }
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+    std::vector<DiffCall> calls(SK, base);
+    for (size_t k = 0; k < SK; ++k) {
+      for (int i = 0; i < 3; ++i)
+        if (base.in[i]) calls[k].in[i] = base.in[i] + k * (size_t)base.in_len(w, i);
+      for (int i = 0; i < 4; ++i)
+        if (base.out[i]) calls[k].out[i] = base.out[i] + k * (size_t)base.out_len(w, i);
+    }
+    if (GroupDiff::member_ok(w)) {
+      diff_alloc_lanes(w, (int)K);
+      if (base.adjoint && base.out[3]) diff_build_tri(w);
+      GroupDiff gd;
+      gd.adjoint = base.adjoint;
+      gd.s = s;
+      gd.one_work = true;
+      for (int k = 0; k < (int)K; ++k) {
+        gd.W.push_back(w);
+        gd.lane.push_back(k);
+        gd.calls.push_back(calls[(size_t)k]);
+        gd.infos.push_back(infos ? infos + k : nullptr);
+      }
+      gd.run(o);
+    } else {  // layouts the lock-step path does not cover: one direction after the other on lane 0, same bits
+      for (int k = 0; k < (int)K; ++k) diff_impl(w, calls[(size_t)k], o, infos ? infos + k : nullptr);
+    }
+    if (!dev) {
+      for (int k = 0; k < 4; ++k)
+        if (host.out[k]) bout[k].download(host.out[k], SK * (size_t)host.out_len(w, k), s);
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+    return 0;
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return -1;
+  }
+}
+scs_int scs_hip_adjoint_multi_device(ScsWork *w, scs_int K, const scs_float *GX_dev, const scs_float *GY_dev, const scs_float *GS_dev,
+                                     scs_float *DB_dev, scs_float *DC_dev, scs_float *DAx_dev, scs_float *DPx_dev, const ScsHipDiffOpts *opts,
+                                     ScsHipDiffInfo *infos) {
+  return diff_multi_entry(w, K, adjoint_call(GX_dev, GY_dev, GS_dev, DB_dev, DC_dev, DAx_dev, DPx_dev), opts, infos, /*dev=*/true,
+                          "scs_hip_adjoint_multi_device");
+}
+scs_int scs_hip_adjoint_multi(ScsWork *w, scs_int K, const scs_float *GX, const scs_float *GY, const scs_float *GS, scs_float *DB, scs_float *DC,
+                              scs_float *DAx, scs_float *DPx, const ScsHipDiffOpts *opts, ScsHipDiffInfo *infos) {
+  return diff_multi_entry(w, K, adjoint_call(GX, GY, GS, DB, DC, DAx, DPx), opts, infos, /*dev=*/false, "scs_hip_adjoint_multi");
+}
+scs_int scs_hip_derivative_multi_device(ScsWork *w, scs_int K, const scs_float *DB_dev, const scs_float *DC_dev, scs_float *DX_dev,
+                                        scs_float *DY_dev, scs_float *DS_dev, const ScsHipDiffOpts *opts, ScsHipDiffInfo *infos) {
+  return diff_multi_entry(w, K, derivative_call(DB_dev, DC_dev, nullptr, nullptr, DX_dev, DY_dev, DS_dev), opts, infos, /*dev=*/true,
+                          "scs_hip_derivative_multi_device");
+}
+scs_int scs_hip_derivative_multi(ScsWork *w, scs_int K, const scs_float *DB, const scs_float *DC, scs_float *DX, scs_float *DY, scs_float *DS,
+                                 const ScsHipDiffOpts *opts, ScsHipDiffInfo *infos) {
+  return diff_multi_entry(w, K, derivative_call(DB, DC, nullptr, nullptr, DX, DY, DS), opts, infos, /*dev=*/false, "scs_hip_derivative_multi");
 }
 
 void scs_finish(ScsWork *w) {

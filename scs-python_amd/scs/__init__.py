@@ -310,6 +310,34 @@ class SCS(object):
     """`derivative_many` over (K, .) float64 torch tensors on the solver's GPU."""
     return self._solver.derivative_many_device(db, dc, tol, max_iters, dA=dA, dP=dP)
 
+  def adjoint_multi(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+    """`adjoint` of the last solve for K cotangents at once: dx (K, n), dy (K, m), ds (K, m), None = 0; K is read from them.  Returns
+    {"db": (K, m), "dc": (K, n), ["dA"], ["dP"], "info": [K dicts]}, row k with the bits of `adjoint` on direction k: one preparation,
+    K LSQR solves in lock step that read the matrices once per tile of directions.  Any K (served in chunks of 32)."""
+    return self._solver.adjoint_multi(dx, dy, ds, want, tol, max_iters)
+
+  def adjoint_multi_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+    """`adjoint_multi` over (K, .) float64 torch tensors on the solver's GPU (taken and returned); same bits."""
+    return self._solver.adjoint_multi_device(dx, dy, ds, want, tol, max_iters)
+
+  def derivative_multi(self, db=None, dc=None, tol=1e-8, max_iters=None):
+    """`derivative` of the last solve for K perturbations at once: db (K, m), dc (K, n), None = 0.  Returns {"dx": (K, n), "dy": (K, m),
+    "ds": (K, m), "info": [K dicts]}, row k with the bits of `derivative` on direction k."""
+    return self._solver.derivative_multi(db, dc, tol, max_iters)
+
+  def derivative_multi_device(self, db=None, dc=None, tol=1e-8, max_iters=None):
+    """`derivative_multi` over (K, .) float64 torch tensors on the solver's GPU (taken and returned); same bits."""
+    return self._solver.derivative_multi_device(db, dc, tol, max_iters)
+
+  def jacobian(self, of="x", wrt="b", rows=None, tol=1e-8, max_iters=None):
+    """The dense block d of[rows] / d wrt of the last solve, shape (len(rows), len(wrt)): of in "x", "y", "s"; wrt in "b", "c"; rows =
+    indices into `of` (None: all of them).  One `adjoint_multi` with the rows' unit cotangents.  Returns (J, infos)."""
+    return self._solver.jacobian(of, wrt, rows, tol, max_iters)
+
+  def jacobian_device(self, of="x", wrt="b", rows=None, tol=1e-8, max_iters=None):
+    """`jacobian` as a float64 torch tensor on the solver's GPU."""
+    return self._solver.jacobian_device(of, wrt, rows, tol, max_iters)
+
 
 def solve(data, cone, **settings):
   """Legacy one-shot API; warm-start vectors may ride along in `data`."""

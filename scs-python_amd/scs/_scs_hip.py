@@ -25,6 +25,7 @@ import contextlib
 import functools
 import ctypes as C
 import importlib.util
+import operator
 import os
 import threading
 import warnings
@@ -264,6 +265,12 @@ def _load():
     lib.scs_hip_diff_batch_plan.argtypes = [_PV, c_int, c_int, c_int, C.POINTER(c_int)]
     lib.scs_hip_diff_group_launches.restype = C.c_long
     lib.scs_hip_diff_group_launches.argtypes = []
+    for name, slots in (("scs_hip_adjoint_multi", 7), ("scs_hip_derivative_multi", 5)):  # (infos: an array of K, not one)
+        for fn in (getattr(lib, name), getattr(lib, name + "_device")):
+            fn.restype = c_int
+            fn.argtypes = [C.c_void_p, c_int] + [C.c_void_p] * slots + [C.POINTER(_ScsHipDiffOpts), C.POINTER(_ScsHipDiffInfo)]
+    lib.scs_hip_diff_lane_tile.restype = C.c_int
+    lib.scs_hip_diff_lane_tile.argtypes = [C.c_int]
     lib.scs_hip_dproj_cone.restype = c_int
     lib.scs_hip_dproj_cone.argtypes = [_PD, _PD, C.POINTER(_ScsCone), c_int, _PD, _PD]
     lib.scs_hip_work_device.restype = c_int
@@ -938,7 +945,8 @@ class SCS(object):
 
     # ------------------------------------------------------ derivatives of the last solve (include/scs_hip.h)
     # The twelve public functions (here and adjoint_batch ... below) name a kind (_ADJOINT / _DERIVATIVE), a memory (host arrays or
-    # device tensors) and their arguments; `_diff` serves one solver, `_diff_list` a list of members.
+    # device tensors) and their arguments; `_diff` serves one solver, `_diff_list` a list of members.  The multi functions
+    # (adjoint_multi ... jacobian) are the same kinds and memories in a third call shape: `_diff_multi`, K directions of one solver.
     def _diff_call(self, fn, ptrs, opts):
         info = _ScsHipDiffInfo()
         with self._lock:
@@ -1082,6 +1090,88 @@ class SCS(object):
     def derivative_many_device(self, db=None, dc=None, tol=1e-8, max_iters=None, dA=None, dP=None):
         """`derivative_many` over float64 torch tensors (K, .) on the solver's GPU: {"dx": (K, n), "dy": (K, m), "ds": (K, m), "info"}."""
         return self._diff_many(_DERIVATIVE, True, (db, dc, dA, dP), None, tol, max_iters)
+
+    # ------------------------------------- several directions at ONE solution (include/scs_hip.h: scs_hip_adjoint_multi)
+    def _diff_multi(self, kind, device, vals, want, tol, max_iters):
+        """`kind` of this solver's last solve along K directions at once: vals = (K, .) stacks in the order of kind.ins, on the host
+        or (device) on the solver's GPU; the results are (K, .) stacks whose rows the library writes, in chunks of the C limit."""
+        if not self._work:
+            raise ValueError("Workspace not initialized!")
+        if want is not None:
+            want = _diff_want(want, self._pattern["P"] is not None)
+        lens = self._lens()
+        opts = _diff_opts(tol, max_iters)
+        mem = _device_memory(self._device_index()) if device else _HOST
+        K, ins = _multi_diff_args(_diff_spec(kind, vals, lens), device=mem.device)
+        out = {k: mem.zeros((K, lens[kind.outs[k]])) for k in _diff_chosen(kind, want)}
+        fn = getattr(_lib, kind.entry + mem.suffix)
+        mem.ready()
+        infos = []
+        for lo in range(0, K, MULTI_MAX):
+            hi = min(K, lo + MULTI_MAX)
+            ptrs = [mem.address(v[lo:hi]) if v is not None else None for v in ins]
+            ptrs += [mem.address(out[k][lo:hi]) if k in out else None for k in kind.outs]
+            chunk = (_ScsHipDiffInfo * (hi - lo))()
+            with self._lock:
+                if not self._work:
+                    raise ValueError("Workspace not initialized!")
+                rc = fn(self._work, hi - lo, *(ptrs + [C.byref(opts), chunk]))
+                err = last_error() if rc != 0 else ""
+            if rc != 0:
+                raise ValueError("libscs_hip: " + err)
+            infos += [_diff_info_dict(io) for io in chunk]
+        out["info"] = infos
+        return out
+
+    def adjoint_multi(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+        """`adjoint` of the last solve for K cotangents at once: dx (K, n), dy (K, m), ds (K, m), None = 0, K read from them.  Returns
+        {"db": (K, m), "dc": (K, n), ["dA": (K, nnz)], ["dP"], "info": [K dicts]}; row k has the bits of `adjoint` on direction k.  The
+        preparation runs once and the K LSQR solves advance in lock step, reading the matrices once per tile of directions."""
+        return self._diff_multi(_ADJOINT_MULTI, False, (dx, dy, ds), want, tol, max_iters)
+
+    def adjoint_multi_device(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None):
+        """`adjoint_multi` over (K, .) float64 torch tensors on the solver's GPU (taken and returned); same bits."""
+        return self._diff_multi(_ADJOINT_MULTI, True, (dx, dy, ds), want, tol, max_iters)
+
+    def derivative_multi(self, db=None, dc=None, tol=1e-8, max_iters=None):
+        """`derivative` of the last solve for K perturbations at once: db (K, m), dc (K, n), None = 0.  Returns {"dx": (K, n),
+        "dy": (K, m), "ds": (K, m), "info": [K dicts]}; row k has the bits of `derivative` on direction k."""
+        return self._diff_multi(_DERIVATIVE_MULTI, False, (db, dc), None, tol, max_iters)
+
+    def derivative_multi_device(self, db=None, dc=None, tol=1e-8, max_iters=None):
+        """`derivative_multi` over (K, .) float64 torch tensors on the solver's GPU (taken and returned); same bits."""
+        return self._diff_multi(_DERIVATIVE_MULTI, True, (db, dc), None, tol, max_iters)
+
+    def _jacobian(self, device, of, wrt, rows, tol, max_iters):
+        if of not in ("x", "y", "s"):
+            raise ValueError("of must be 'x', 'y' or 's', not %r" % (of,))
+        if wrt not in ("b", "c"):
+            raise ValueError("wrt must be 'b' or 'c', not %r" % (wrt,))
+        size = self.n if of == "x" else self.m
+        rows = list(range(size)) if rows is None else [operator.index(r) for r in rows]
+        for r in rows:
+            if not 0 <= r < size:
+                raise ValueError("rows holds %d: %s has %d entries" % (r, of, size))
+        if not rows:
+            raise ValueError("rows is empty")
+        if device:
+            import torch
+            G = torch.zeros((len(rows), size), dtype=torch.float64, device=torch.device("cuda", self._device_index()))
+            G[torch.arange(len(rows)), torch.tensor(rows, dtype=torch.long)] = 1.0
+        else:
+            G = np.zeros((len(rows), size))
+            G[np.arange(len(rows)), rows] = 1.0
+        res = self._diff_multi(_ADJOINT_MULTI, device, tuple(G if k == of else None for k in ("x", "y", "s")), (wrt,), tol, max_iters)
+        return res["d" + wrt], res["info"]
+
+    def jacobian(self, of="x", wrt="b", rows=None, tol=1e-8, max_iters=None):
+        """The dense block d of[rows] / d wrt of the last solve, (len(rows), len(wrt)): of in "x", "y", "s", wrt in "b", "c", rows =
+        indices into `of` (None: all).  `adjoint_multi` with the unit cotangents of the rows.  Returns (J, infos)."""
+        return self._jacobian(False, of, wrt, rows, tol, max_iters)
+
+    def jacobian_device(self, of="x", wrt="b", rows=None, tol=1e-8, max_iters=None):
+        """`jacobian` as a float64 torch tensor on the solver's GPU."""
+        return self._jacobian(True, of, wrt, rows, tol, max_iters)
 
     # -------------------------------------------------- bench hooks (not part of the reference surface)
     def _set_profiling(self, on):
@@ -1428,6 +1518,54 @@ _ADJOINT = _DiffKind(ins=(("dx", "n"), ("dy", "m"), ("ds", "m")), vectors=3, out
 _DERIVATIVE = _DiffKind(ins=(("db", "m"), ("dc", "n"), ("dA", "A"), ("dP", "P")), vectors=2, outs={"dx": "n", "dy": "m", "ds": "m"},
                         entry="scs_hip_derivative_full", short="scs_hip_derivative", summed=())
 _ADJOINT_SUM = _ADJOINT._replace(entry="scs_hip_adjoint_shared", summed=("dA", "dP"))  # members of ONE matrix: `reduce="sum"`
+
+
+# K directions at ONE solution: the slots of the single entries, each a (K, .) stack, behind a count (`SCS._diff_multi`)
+_ADJOINT_MULTI = _ADJOINT._replace(entry="scs_hip_adjoint_multi")
+_DERIVATIVE_MULTI = _DERIVATIVE._replace(ins=_DERIVATIVE.ins[:2], entry="scs_hip_derivative_multi", short=None)
+MULTI_MAX = 32  # directions per C call (include/scs_hip.h); more are served in chunks
+
+
+def _multi_diff_args(spec, device=None):
+    """Argument checks of the multi entries, before the library is called (pure Python; torch is touched only for device arguments).
+    spec: (name, value, length) triples; a value is None (0 for every direction) or a (K, length) stack — on the host a numpy array of
+    floats, on the device (device = the GPU index) a contiguous float64 torch tensor there.  K is read from the values: they must
+    agree, and one at least must be given.  Returns (K, [None or the stack, as a fresh C-contiguous float64 array on the host])."""
+    K, got = None, []
+    for name, val, length in spec:
+        if val is None:
+            got.append(None)
+            continue
+        if device is None:
+            if not isinstance(val, np.ndarray) or not np.issubdtype(val.dtype, np.floating):
+                raise TypeError("%s must be a 2-D numpy array of floats, one row per direction" % name)
+        else:
+            import torch
+            if not isinstance(val, torch.Tensor):
+                raise TypeError("%s must be a 2-D torch.Tensor on the solver's GPU, one row per direction, not %s" % (name, type(val).__name__))
+            if val.dtype != torch.float64:
+                raise TypeError("%s must be a float64 tensor, not %s" % (name, val.dtype))
+        if val.ndim != 2:
+            raise ValueError("%s must be 2-D, one row per direction" % name)
+        if int(val.shape[0]) < 1:
+            raise ValueError("%s holds no direction" % name)
+        if int(val.shape[1]) != length:
+            raise ValueError("%s has incompatible dimension with A: rows of %d elements, not %d" % (name, length, int(val.shape[1])))
+        if K is None:
+            K = int(val.shape[0])
+        if int(val.shape[0]) != K:
+            raise ValueError("%s holds %d directions where the arguments before it hold %d" % (name, int(val.shape[0]), K))
+        if device is None:
+            got.append(np.array(val, dtype=np.float64, order="C", copy=True))
+        else:
+            if not val.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+            if val.device.type != "cuda" or val.device.index != device:
+                raise ValueError("%s must live on the workspace's GPU (cuda:%d), not on %s" % (name, device, val.device))
+            got.append(val)
+    if K is None:
+        raise ValueError("no direction given: %s are all None" % ", ".join(name for name, _, _ in spec))
+    return K, got
 
 
 def _diff_reduce(kind, reduce, want):
