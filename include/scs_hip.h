@@ -360,6 +360,41 @@ SCS_HIP_API scs_int scs_hip_derivative_multi(ScsWork *w, scs_int K, const scs_fl
 /* lanes per workgroup of the multi entries' products: sets 4 or 8 (anything else: only reads) and returns the previous value.  For
  * tools/adjoint_multi_bench.py, which measures both; the results do not depend on it. */
 SCS_HIP_API int scs_hip_diff_lane_tile(int tile);
+/* Newton polish of the resident solution (csrc/refine.hpp).  The solve is a first-order method: it reaches 1e-4 quickly and 1e-9 slowly,
+ * and the derivative entries above are only meaningful at an accurate fixed point.  A Newton step on F(x, v) = 0 is one forward-mode
+ * solve J d = -F on the machinery of scs_hip_derivative; Pi_K(v) = W(v) v (Pi_K is positively homogeneous) gives s = Pi(v) and
+ * y = Pi(v) - v from one apply of W, so no projection of the solve is called and none of its state is touched.
+ *   Start: the resident (x, v = s - y) of the last solve.  Step: LSQR on J d = -F (lsqr_tol, lsqr_max_iters), then t = 1, 1/2, ... (at
+ *   most 10 halvings) until |F(z + t d)|_2 < (1 - 1e-4 t) |F(z)|_2; every trial re-derives W at its own v.  Stop rule: the solver's
+ *   three criteria with eps_abs = eps_rel = tol in the caller's units,
+ *       |Ax + s - b|_inf <= tol (1 + max(|Ax|_inf, |s|_inf, |b|_inf)),  |Px + A'y + c|_inf <= tol (1 + max(|Px|_inf, |A'y|_inf, |c|_inf)),
+ *       |x'Px + c'x + b'y| <= tol (1 + max(|x'Px|, |c'x|, |b'y|)).
+ *   info->stop = 1: the criteria hold; 2: max_steps reached; 3: no t gave a decrease.  On 2 and 3 the best accepted point is kept.
+ *   steps = accepted steps, halvings and lsqr_iters are totals; merit = |F|_2 in the solver's scaled coordinates; res_pri, res_dual,
+ *   gap, pobj, dobj are those of the final point (the *_before ones: of the starting point), in the caller's units.
+ * A start that already meets the criteria returns steps = 0, stop = 1 and leaves the resident solution bit for bit as it was, and so
+ * does a call in which no step is accepted.  Otherwise the accepted point REPLACES the resident solution: every later derivative
+ * entry, scs_hip_solution_to_device and a device warm start read it.  sol (host pointers for scs_hip_refine, device pointers of the
+ * workspace's device for scs_hip_refine_device; sol or any member may be NULL) receives the resident x, y, s after the call.  opts and
+ * info may be NULL.  Two calls on the same state give the same bits, and so do the host and the device entry.  The first call takes
+ * 2 (n + m) doubles (plus the partials of one reduction pass) from the block pool beside the derivative's scratch, kept until
+ * scs_finish; a workspace that never refines takes nothing.  Every loop is bounded on the host.
+ * Returns 0, or -1 with the reason in scs_hip_last_error — before any device work, the workspace unchanged and usable: a NULL workspace;
+ * the refusals of scs_hip_derivative (no solve yet, not solved, stale, a cone without a derivative, by name); a NaN tol; (device
+ * entry) a pointer that is not device memory of the workspace's device. */
+typedef struct {
+  scs_float tol;          /* stop rule; <= 0: 1e-9 */
+  scs_int max_steps;      /* <= 0: 10 */
+  scs_float lsqr_tol;     /* inner atol = btol; <= 0: 1e-8 */
+  scs_int lsqr_max_iters; /* <= 0: 4 (n + m) */
+} ScsHipRefineOpts;
+typedef struct {
+  scs_int steps, halvings, lsqr_iters, stop;
+  scs_float merit_before, merit_after;
+  scs_float res_pri_before, res_dual_before, gap_before, res_pri, res_dual, gap, pobj, dobj, time_ms;
+} ScsHipRefineInfo;
+SCS_HIP_API scs_int scs_hip_refine(ScsWork *w, ScsSolution *sol, const ScsHipRefineOpts *opts, ScsHipRefineInfo *info);
+SCS_HIP_API scs_int scs_hip_refine_device(ScsWork *w, ScsSolution *sol_dev, const ScsHipRefineOpts *opts, ScsHipRefineInfo *info);
 /* the HIP device a workspace lives on (-1: NULL) */
 SCS_HIP_API int scs_hip_work_device(const ScsWork *w);
 

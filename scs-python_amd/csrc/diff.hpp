@@ -369,39 +369,17 @@ template <class StepU, class StepV, class Finished> static void lsqr_drive(long 
   }
 }
 
-// One workspace.  The caller holds w->mtx and the scratch turn, has selected the device and refused bad arguments (diff_check).  All
-// pointers are device pointers.
-static void diff_impl(ScsHipWork *w, const DiffCall &a, const ScsHipDiffOpts *o, ScsHipDiffInfo *info) {
-  const double t0 = now_ms();
+// LSQR on lane 0 of one workspace, from the right-hand side in uh (wr.start_add: what k_lsqr_start adds into its rows >= n) to the
+// answer in x: the start, the products as `wr` wires them over `plan`, the chunks of lsqr_drive.  hfl: the flag block as LSQR left it.
+// diff_impl and refine_impl (refine.hpp) both solve through here.
+static void diff_lsqr(ScsHipWork *w, const DiffWiring &wr, const DprojPlan &plan, const DiffLimits &lim, int *hfl) {
   hipStream_t s = w->stream;
-  const int n = w->n, m = w->m;
-  const long N = (long)n + m;
-  const DiffLimits lim(o, N);
-  diff_alloc(w);
-  if (a.adjoint && a.out[3]) diff_build_tri(w);
-  if (a.perturbs()) pert_alloc(w, a.pert[0] != nullptr, a.pert[1] != nullptr, "scs_hip_derivative_full");
+  const int n = w->n;
+  const long N = (long)n + w->m;
   DiffScratch &d = w->diff;
-  const double *D = w->normalized ? w->D.p : nullptr, *E = w->normalized ? w->E.p : nullptr;
-  const double sigma = w->normalized ? w->scal.sigma : 1.0;
   const int nbN = vec_blocks(N);
   const dim3 gN(nbN), bV(kVecThreads);
   const int *done = d.fl.p + LF_DONE;
-  const DiffWiring wr = diff_wiring(w, a);
-
-  // ---- the fixed point and the cone records ----
-  hipLaunchKernelGGL(k_dproj_vhat, dim3(vec_blocks(m)), bV, 0, s, (const double *)w->sols.p, (const double *)w->soly.p, D, sigma, m, d.vhat.p);
-  const DprojPlan plan = diff_plan(w);
-  launch_dproj_prep(plan, s);
-
-  // ---- right-hand side into uh, x = w = 0 ----
-  if (a.adjoint) {
-    hipLaunchKernelGGL(k_adj_in, gN, bV, 0, s, a.in[0], a.in[1], a.in[2], D, E, sigma, n, m, d.uh.p, wr.gyh, wr.gsh);
-    launch_dproj(plan, wr.rhs_gs, nullptr, s);
-    launch_dproj(plan, wr.rhs_gy, nullptr, s);
-  } else {
-    if (wr.eff_c) pert_launch(w, a.pert[0], a.pert[1], a.in[1], a.in[0], -1.0, wr.eff_c, wr.eff_b, s);
-    hipLaunchKernelGGL(k_fwd_in, gN, bV, 0, s, wr.db_in, wr.dc_in, D, E, sigma, n, m, d.uh.p);
-  }
   hipLaunchKernelGGL(k_lsqr_start, gN, bV, 0, s, d.uh.p, wr.start_add[0], wr.start_add[1], n, N, d.x.p, d.w.p, d.partU.p, d.st.p, d.fl.p);
 
   // ---- LSQR: the products leave their results in tAt, tP, tA, dW ----
@@ -422,13 +400,50 @@ static void diff_impl(ScsHipWork *w, const DiffCall &a, const ScsHipDiffOpts *o,
     hipLaunchKernelGGL(k_lsqr_u, gN, bV, 0, s, k, wr.pu.read, d.uh.p, (const double *)d.vh.p, d.w.p, n, N, (const double *)d.partV.p,
                        (const double *)d.partX.p, nbN, d.partU.p, d.st.p, d.fl.p, lim.tol);
   };
-  int hfl[LF_COUNT] = {0, 0, 0, 0};
+  for (int k = 0; k < LF_COUNT; ++k) hfl[k] = 0;
   lsqr_drive(lim.cap, step_u, step_v, [&] {
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(hfl, d.fl.p, sizeof(hfl), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(hfl, d.fl.p, sizeof(int) * LF_COUNT, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     return hfl[LF_DONE] != 0;
   });
+}
+
+// One workspace.  The caller holds w->mtx and the scratch turn, has selected the device and refused bad arguments (diff_check).  All
+// pointers are device pointers.
+static void diff_impl(ScsHipWork *w, const DiffCall &a, const ScsHipDiffOpts *o, ScsHipDiffInfo *info) {
+  const double t0 = now_ms();
+  hipStream_t s = w->stream;
+  const int n = w->n, m = w->m;
+  const long N = (long)n + m;
+  const DiffLimits lim(o, N);
+  diff_alloc(w);
+  if (a.adjoint && a.out[3]) diff_build_tri(w);
+  if (a.perturbs()) pert_alloc(w, a.pert[0] != nullptr, a.pert[1] != nullptr, "scs_hip_derivative_full");
+  DiffScratch &d = w->diff;
+  const double *D = w->normalized ? w->D.p : nullptr, *E = w->normalized ? w->E.p : nullptr;
+  const double sigma = w->normalized ? w->scal.sigma : 1.0;
+  const int nbN = vec_blocks(N);
+  const dim3 gN(nbN), bV(kVecThreads);
+  const DiffWiring wr = diff_wiring(w, a);
+
+  // ---- the fixed point and the cone records ----
+  hipLaunchKernelGGL(k_dproj_vhat, dim3(vec_blocks(m)), bV, 0, s, (const double *)w->sols.p, (const double *)w->soly.p, D, sigma, m, d.vhat.p);
+  const DprojPlan plan = diff_plan(w);
+  launch_dproj_prep(plan, s);
+
+  // ---- right-hand side into uh, x = w = 0 ----
+  if (a.adjoint) {
+    hipLaunchKernelGGL(k_adj_in, gN, bV, 0, s, a.in[0], a.in[1], a.in[2], D, E, sigma, n, m, d.uh.p, wr.gyh, wr.gsh);
+    launch_dproj(plan, wr.rhs_gs, nullptr, s);
+    launch_dproj(plan, wr.rhs_gy, nullptr, s);
+  } else {
+    if (wr.eff_c) pert_launch(w, a.pert[0], a.pert[1], a.in[1], a.in[0], -1.0, wr.eff_c, wr.eff_b, s);
+    hipLaunchKernelGGL(k_fwd_in, gN, bV, 0, s, wr.db_in, wr.dc_in, D, E, sigma, n, m, d.uh.p);
+  }
+  // ---- LSQR ----
+  int hfl[LF_COUNT] = {0, 0, 0, 0};
+  diff_lsqr(w, wr, plan, lim, hfl);
   double hst[L_COUNT];
   HIP_CHECK(hipMemcpyAsync(hst, d.st.p, sizeof(hst), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));

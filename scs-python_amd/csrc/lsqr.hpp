@@ -222,6 +222,12 @@ struct DiffScratch : DiffLane {
   DevBuf<int> tri_up;      // column pointers of the caller's triangle of P (the gather of dL/dP), built at the first request
   DevBuf<double> eff;      // (dc_eff ; db_eff) of a forward call that perturbs A or P (perturb.hpp): n + m, taken at the first such call
   std::vector<std::unique_ptr<DiffLane>> more;  // lanes 1 ..
+  // scs_hip_refine (refine.hpp): the base and the trial point of the Newton iteration (x^ n and v^ m each: 2 (n + m) doubles), the
+  // partials of the residual pass and its state block.  Taken at the first refine call; a workspace that never refines has none.
+  struct Refine {
+    bool ready = false;
+    DevBuf<double> bx, bv, tx, tv, part, st;
+  } refine;
   DiffLane &lane(int k) { return k == 0 ? static_cast<DiffLane &>(*this) : *more[(size_t)k - 1]; }
 };
 

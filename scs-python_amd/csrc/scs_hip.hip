@@ -50,6 +50,7 @@
 #include "matrix_update.hpp"
 #include "perturb.hpp"
 #include "diff.hpp"
+#include "refine.hpp"
 #include "spmv_lanes.hpp"
 #include "diff_batch.hpp"
 #include "grad_shared.hpp"
@@ -885,6 +886,48 @@ scs_int scs_hip_derivative_full_batch(ScsWork **w, const scs_float **db, const s
 scs_int scs_hip_derivative_batch(ScsWork **w, const scs_float **db, const scs_float **dc, scs_float **dx, scs_float **dy, scs_float **ds,
                                  const ScsHipDiffOpts *opts, ScsHipDiffInfo **info, scs_int count) {
   return derivative_batch_entry(w, db, dc, nullptr, nullptr, dx, dy, ds, opts, info, count, /*dev=*/false, "scs_hip_derivative_batch");
+}
+
+// ---- Newton polish of the resident solution (include/scs_hip.h; csrc/refine.hpp) ----
+// locking, device selection and the scratch turn are diff_entry's; every refusal comes before device work
+static scs_int refine_entry(ScsWork *w, ScsSolution *sol, const ScsHipRefineOpts *o, ScsHipRefineInfo *info, bool dev, const char *who) {
+  if (!w) {
+    set_last_error(std::string(who) + ": null workspace");
+    return -1;
+  }
+  try {
+    set_last_error("");
+    std::lock_guard<std::mutex> lock(w->mtx);
+    std::string why = diff_refusal(w);
+    if (why.empty() && o && o->tol != o->tol) why = "tol is NaN";
+    if (!why.empty()) throw std::runtime_error(std::string(who) + ": " + why);
+    if (dev && sol) {
+      if (sol->x) check_device_vector(sol->x, w->device, who, "sol_dev->x");
+      if (sol->y) check_device_vector(sol->y, w->device, who, "sol_dev->y");
+      if (sol->s) check_device_vector(sol->s, w->device, who, "sol_dev->s");
+    }
+    HIP_CHECK(hipSetDevice(w->device));
+    ScsHipWork::ScratchTurn turn(w);
+    refine_impl(w, o, info);
+    if (sol && dev) {
+      w->hand_over_solution(sol);
+    } else if (sol) {
+      if (sol->x) w->solx.download(sol->x, w->n, w->stream);
+      if (sol->y) w->soly.download(sol->y, w->m, w->stream);
+      if (sol->s) w->sols.download(sol->s, w->m, w->stream);
+      HIP_CHECK(hipStreamSynchronize(w->stream));
+    }
+    return 0;
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return -1;
+  }
+}
+scs_int scs_hip_refine(ScsWork *w, ScsSolution *sol, const ScsHipRefineOpts *opts, ScsHipRefineInfo *info) {
+  return refine_entry(w, sol, opts, info, /*dev=*/false, "scs_hip_refine");
+}
+scs_int scs_hip_refine_device(ScsWork *w, ScsSolution *sol_dev, const ScsHipRefineOpts *opts, ScsHipRefineInfo *info) {
+  return refine_entry(w, sol_dev, opts, info, /*dev=*/true, "scs_hip_refine_device");
 }
 
 // ---- several directions at one solution (include/scs_hip.h; lanes: csrc/lsqr.hpp, csrc/diff_batch.hpp, csrc/spmv_lanes.hpp) ----

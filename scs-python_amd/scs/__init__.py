@@ -289,6 +289,19 @@ class SCS(object):
     return self._solver.derivative_device(db, dc, tol, max_iters, dA=dA, dP=dP)
 
 
+  def refine(self, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None):
+    """Polish the last solution on the GPU by Newton steps on its optimality conditions (each one LSQR solve of `derivative`'s system
+    to `lsqr_tol` plus a backtracking line search) until the solver's three stopping criteria hold with eps_abs = eps_rel = `tol`, at
+    most `max_steps` steps.  Returns {"x", "y", "s", "info"}; info["stop_reason"] is "converged", "max_steps" or "no_decrease".  The
+    polished point becomes the solver's solution: `adjoint`, `derivative`, `jacobian` and the next warm start read it.  Cones as
+    `adjoint`; ValueError before a solve, after one that did not end solved, and after an update without a new solve."""
+    return self._solver.refine(tol, max_steps, lsqr_tol, lsqr_max_iters)
+
+  def refine_device(self, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None):
+    """`refine` with "x", "y", "s" as fresh float64 torch tensors on the solver's GPU; same bits."""
+    return self._solver.refine_device(tol, max_steps, lsqr_tol, lsqr_max_iters)
+
+
   def adjoint_many(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None, reduce=None):
     """`adjoint` of the K problems the last `solve_many` solved, differentiated in lock step: dx (K, n), dy (K, m), ds (K, m), None = 0.
     Returns K dicts like `adjoint()`, with the bits K separate calls would give.  reduce="sum" (needs "A" or "P" in `want`): the gradients

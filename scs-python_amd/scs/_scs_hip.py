@@ -100,6 +100,17 @@ class _ScsHipDiffInfo(C.Structure):
     _fields_ = [("iters", c_int), ("residual", c_dbl), ("normal_residual", c_dbl), ("stop", c_int), ("time_ms", c_dbl)]
 
 
+class _ScsHipRefineOpts(C.Structure):
+    _fields_ = [("tol", c_dbl), ("max_steps", c_int), ("lsqr_tol", c_dbl), ("lsqr_max_iters", c_int)]
+
+
+class _ScsHipRefineInfo(C.Structure):
+    _fields_ = [("steps", c_int), ("halvings", c_int), ("lsqr_iters", c_int), ("stop", c_int),
+                ("merit_before", c_dbl), ("merit_after", c_dbl), ("res_pri_before", c_dbl), ("res_dual_before", c_dbl),
+                ("gap_before", c_dbl), ("res_pri", c_dbl), ("res_dual", c_dbl), ("gap", c_dbl), ("pobj", c_dbl), ("dobj", c_dbl),
+                ("time_ms", c_dbl)]
+
+
 class _ScsHipPoolStats(C.Structure):
     _fields_ = [("held_bytes", C.c_size_t), ("held_blocks", C.c_size_t), ("live_bytes", C.c_size_t),
                 ("hits", C.c_size_t), ("misses", C.c_size_t)]
@@ -269,6 +280,9 @@ def _load():
         for fn in (getattr(lib, name), getattr(lib, name + "_device")):
             fn.restype = c_int
             fn.argtypes = [C.c_void_p, c_int] + [C.c_void_p] * slots + [C.POINTER(_ScsHipDiffOpts), C.POINTER(_ScsHipDiffInfo)]
+    for fn in (lib.scs_hip_refine, lib.scs_hip_refine_device):
+        fn.restype = c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(_ScsSolution), C.POINTER(_ScsHipRefineOpts), C.POINTER(_ScsHipRefineInfo)]
     lib.scs_hip_diff_lane_tile.restype = C.c_int
     lib.scs_hip_diff_lane_tile.argtypes = [C.c_int]
     lib.scs_hip_dproj_cone.restype = c_int
@@ -1174,6 +1188,47 @@ class SCS(object):
         return self._jacobian(True, of, wrt, rows, tol, max_iters)
 
     # -------------------------------------------------- bench hooks (not part of the reference surface)
+    # ------------------------------------------------------ Newton polish of the last solve (include/scs_hip.h: scs_hip_refine)
+    def _refine_call(self, fn, sol, opts):
+        """lock held"""
+        info = _ScsHipRefineInfo()
+        rc = fn(self._work, C.byref(sol), C.byref(opts), C.byref(info))
+        if rc != 0:
+            raise ValueError("libscs_hip: " + last_error())
+        return _refine_info_dict(info)
+
+    def refine(self, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None):
+        """Polish the solution of the last solve by Newton steps on its optimality conditions, on the device: each step is one LSQR
+        solve of the system `derivative` solves (lsqr_tol, lsqr_max_iters: None = 4 (n + m)) and a backtracking line search; it stops
+        when the solver's three criteria hold with eps_abs = eps_rel = tol, after max_steps accepted steps, or when no step length
+        gives a decrease.  Returns {"x", "y", "s", "info"}; info = the figures of ScsHipRefineInfo and "stop_reason" ("converged",
+        "max_steps", "no_decrease").  The polished point replaces the resident solution: `adjoint`, `derivative`, `jacobian` and
+        `solve(warm_start=True)` start from it."""
+        opts = _refine_opts(tol, max_steps, lsqr_tol, lsqr_max_iters)
+        with self._lock:
+            if not self._work:
+                raise ValueError("Workspace not initialized!")
+            sol = _ScsSolution(_pd(self._x), _pd(self._y), _pd(self._s))
+            info = self._refine_call(_lib.scs_hip_refine, sol, opts)
+            xo, yo, so = self._x.copy(), self._y.copy(), self._s.copy()
+        return {"x": xo, "y": yo, "s": so, "info": info}
+
+    def refine_device(self, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None):
+        """`refine` with the result as three fresh float64 torch tensors on the solver's GPU; same bits."""
+        opts = _refine_opts(tol, max_steps, lsqr_tol, lsqr_max_iters)
+        dev = self._device_index()
+        import torch
+        tdev = torch.device("cuda", dev)
+        out = {"x": torch.empty(self.n, dtype=torch.float64, device=tdev), "y": torch.empty(self.m, dtype=torch.float64, device=tdev),
+               "s": torch.empty(self.m, dtype=torch.float64, device=tdev)}
+        with self._lock:
+            if not self._work:
+                raise ValueError("Workspace not initialized!")
+            _sync_torch_stream(dev)
+            sol = _ScsSolution(C.cast(out["x"].data_ptr(), _PD), C.cast(out["y"].data_ptr(), _PD), C.cast(out["s"].data_ptr(), _PD))
+            out["info"] = self._refine_call(_lib.scs_hip_refine_device, sol, opts)
+        return out
+
     def _set_profiling(self, on):
         with self._lock:
             _lib.scs_hip_set_profiling(self._work, 1 if on else 0)
@@ -1328,6 +1383,34 @@ def _diff_opts(tol, max_iters):
         if isinstance(max_iters, (bool, np.bool_)) or it <= 0:
             raise ValueError("max_iters must be positive")
     return _ScsHipDiffOpts(t, it)
+
+
+REFINE_STOP = {1: "converged", 2: "max_steps", 3: "no_decrease"}
+
+
+def _refine_opts(tol, max_steps, lsqr_tol, lsqr_max_iters):
+    """tol, lsqr_tol: positive finite reals; max_steps: an int >= 1; lsqr_max_iters: None (4 (n + m)) or a positive int"""
+    vals = []
+    for name, v in (("tol", tol), ("lsqr_tol", lsqr_tol)):
+        t = _as_c_double(name, v)
+        if isinstance(v, (bool, np.bool_)) or not np.isfinite(t) or t <= 0:
+            raise ValueError("%s must be a positive finite number" % name)
+        vals.append(t)
+    steps = _as_c_int("max_steps", max_steps)
+    if isinstance(max_steps, (bool, np.bool_)) or steps < 1:
+        raise ValueError("max_steps must be at least 1")
+    it = 0
+    if lsqr_max_iters is not None:
+        it = _as_c_int("lsqr_max_iters", lsqr_max_iters)
+        if isinstance(lsqr_max_iters, (bool, np.bool_)) or it <= 0:
+            raise ValueError("lsqr_max_iters must be positive")
+    return _ScsHipRefineOpts(vals[0], steps, vals[1], it)
+
+
+def _refine_info_dict(info):
+    d = {name: getattr(info, name) for name, _ in _ScsHipRefineInfo._fields_}
+    d["stop_reason"] = REFINE_STOP.get(d["stop"], "unknown")
+    return d
 
 
 def _device_vec(name, t, length, device):

@@ -9,6 +9,12 @@ import torch.
 `adjoint_device` call for the gradients of b and c, with the LSQR tolerance `solver.autograd_tol` (default 1e-8).  The info dicts of
 the last forward and backward are left in `solver.autograd_info` / `solver.autograd_adjoint_info`.
 
+`solver.autograd_refine_tol` (default None: nothing changes) makes the forward of `solve` polish the solution after the solve:
+`refine_device(tol=solver.autograd_refine_tol)`, Newton steps on the optimality conditions (`SCS.refine`).  The layer returns the
+polished tensors and backward differentiates the polished, resident solution — a loose `eps` for the solve and a tight gradient.  A
+refusal of `refine_device` (a solve that did not end solved) comes through as its ValueError; the info dict of the polish is left in
+`solver.autograd_refine_info`.  `solve_many` does not refine.
+
 A and P, when given, are float64 1-D tensors on the solver's GPU holding the stored VALUES of the matrices in the constructor's
 canonical order (sorted CSC; P: its upper triangle, an off-diagonal value standing for both mirror images) — the learnable parameters
 of a layer usually sit there.  Forward then is `update_matrix_device` with what is given, `update_device(b, c)` and the solve;
@@ -65,6 +71,11 @@ class _Solve(torch.autograd.Function):
       out = solver.solve_device(warm_start=True, x=last[0], y=last[1], s=last[2])
     else:
       out = solver.solve_device(warm_start=False)
+    refine_tol = getattr(solver, "autograd_refine_tol", None)
+    if refine_tol is not None:  # polish the resident solution: backward then differentiates an accurate fixed point
+      info = out["info"]
+      out = solver.refine_device(tol=refine_tol)
+      solver.autograd_refine_info, out["info"] = out["info"], info
     # (detached views: the returned tensors get a grad_fn that holds ctx and with it the solver — the solver must not hold them back)
     solver._autograd_last = (out["x"].detach(), out["y"].detach(), out["s"].detach())
     return _solved(ctx, solver, out)
