@@ -337,6 +337,8 @@ SCS_HIP_API scs_int scs_hip_derivative_full_batch(ScsWork **w, const scs_float *
 SCS_HIP_API int scs_hip_diff_batch_plan(ScsWork **w, scs_int count, int want_dA, int want_dP, scs_int *group_of);
 /* grouped launches issued by the batch derivative entries since the process started (tests, tools; as scs_hip_tiled_launches) */
 SCS_HIP_API long scs_hip_diff_group_launches(void);
+/* host synchronisations made by those groups (and by the groups of scs_hip_refine_batch) since the process started (tools) */
+SCS_HIP_API long scs_hip_diff_group_syncs(void);
 /* Several directions at ONE solution: K cotangents (adjoint) or K perturbations (derivative) of the workspace's last solve in one call.
  * The arrays are row-major, one direction per row: GX K x n, GY and GS K x m (NULL = zeros, as in scs_hip_adjoint), DB K x m, DC K x n,
  * DAx K x nnz(A), DPx K x nnz(P) (NULL = not wanted); for the derivative DB K x m and DC K x n in, DX K x n, DY and DS K x m out.
@@ -395,6 +397,21 @@ typedef struct {
 } ScsHipRefineInfo;
 SCS_HIP_API scs_int scs_hip_refine(ScsWork *w, ScsSolution *sol, const ScsHipRefineOpts *opts, ScsHipRefineInfo *info);
 SCS_HIP_API scs_int scs_hip_refine_device(ScsWork *w, ScsSolution *sol_dev, const ScsHipRefineOpts *opts, ScsHipRefineInfo *info);
+/* scs_hip_refine for `count` solved workspaces at once (csrc/refine_batch.hpp).  Members are grouped as scs_hip_adjoint_batch groups them
+ * with no matrix gradient requested (scs_hip_diff_batch_plan(w, count, 0, 0, ..) describes it): equally shaped members whose layouts the
+ * grouped derivative covers are refined in LOCK STEP, one launch per kernel for the group (scs_hip_diff_group_launches counts them; the
+ * count does not depend on the group's size) and one host synchronisation per evaluation of the residual for the group; a member
+ * without a group goes through the path of scs_hip_refine.  The control flow is per member, on the host, over lists: members of one
+ * group may take different numbers of steps and halvings and stop for different reasons.  Every member's x, y, s and info have the bits
+ * of scs_hip_refine on that member alone, except time_ms, which is its group's; the host and the device entry give the same bits.
+ *   sol and info hold `count` entries; either array and any entry may be NULL.  opts (may be NULL) hold for every member.  Afterwards
+ *   every member's polished point is its resident solution, as after scs_hip_refine.
+ *   Returns 0, or -1 with the reason and the member's index ("member i") in scs_hip_last_error, checked for EVERY member before any
+ *   device work, all workspaces unchanged and usable: the refusals of scs_hip_refine; a NULL member; a workspace that appears twice;
+ *   count <= 0; members on different devices; (device entry) a pointer that is not device memory of the members' device. */
+SCS_HIP_API scs_int scs_hip_refine_batch(ScsWork **w, ScsSolution **sol, const ScsHipRefineOpts *opts, ScsHipRefineInfo **info, scs_int count);
+SCS_HIP_API scs_int scs_hip_refine_batch_device(ScsWork **w, ScsSolution **sol_dev, const ScsHipRefineOpts *opts, ScsHipRefineInfo **info,
+                                                scs_int count);
 /* the HIP device a workspace lives on (-1: NULL) */
 SCS_HIP_API int scs_hip_work_device(const ScsWork *w);
 

@@ -41,6 +41,7 @@ inline void launch_grouped_k(const GTable<Fn, Threads, A...> &t, const int *list
 }
 
 static std::atomic<long> g_diff_group_launches{0};  // scs_hip_diff_group_launches(): tests, tools/adjoint_batch_bench.py
+static std::atomic<long> g_diff_group_syncs{0};     // scs_hip_diff_group_syncs(): host synchronisations of the groups (tools/refine_batch_timing.py)
 // lanes of one workspace per workgroup of the lanes' product (spmv_lanes.hpp): 4 or 8.  4 by the table of profiles/adjoint_multi.txt
 // (the measured problems have few row blocks: at tile 8 half as many workgroups each serve twice the lanes in turn, and a call of
 // K >= 8 lanes took 1.2 - 1.4 times as long); scs_hip_diff_lane_tile() moves it for tools/adjoint_multi_bench.py, which measures both.
@@ -129,8 +130,10 @@ struct GroupDiff {
   DevBuf<double> st_d;            // G x L_COUNT
   int *flags_h = nullptr, *lists_h = nullptr;  // (pinned: every copy here is asynchronous)
   double *st_h = nullptr;
+  const int *all_d = nullptr;                  // the identity list
+  int *active_d = nullptr, *active_h = nullptr;  // the members LSQR still iterates (lsqr_run compacts it)
   std::vector<DprojPlan> plans;
-  long launches = 0;
+  long launches = 0, syncs = 0;
   int lane_tile = 4;
 
   ~GroupDiff() {
@@ -141,6 +144,7 @@ struct GroupDiff {
       --t_pool_release;
     }
     g_diff_group_launches.fetch_add(launches, std::memory_order_relaxed);
+    g_diff_group_syncs.fetch_add(syncs, std::memory_order_relaxed);
     if (flags_h) (void)hipHostFree(flags_h);
     if (lists_h) (void)hipHostFree(lists_h);
     if (st_h) (void)hipHostFree(st_h);
@@ -202,11 +206,83 @@ struct GroupDiff {
   void sync() {
     HIP_CHECK(hipGetLastError());  // (launches are not checked one by one)
     HIP_CHECK(hipStreamSynchronize(s));
+    ++syncs;
   }
   static CsrView csr_of(const DeviceCsr &M) {
     CsrView V = M.view().csr;
     V.pstride = V.nblk;
     return V;
+  }
+
+  // The member lists and the gathered blocks of a group of G members: the identity list and the active list, uploaded.
+  void alloc_lists() {
+    HIP_CHECK(hipHostMalloc((void **)&flags_h, sizeof(int) * LF_COUNT * G));
+    HIP_CHECK(hipHostMalloc((void **)&lists_h, sizeof(int) * 2 * G));
+    HIP_CHECK(hipHostMalloc((void **)&st_h, sizeof(double) * L_COUNT * G));
+    flags_d.alloc((size_t)LF_COUNT * G);
+    st_d.alloc((size_t)L_COUNT * G);
+    lists_d.alloc((size_t)2 * G);
+    for (int g = 0; g < G; ++g) lists_h[g] = lists_h[G + g] = g;
+    HIP_CHECK(hipMemcpyAsync(lists_d.p, lists_h, sizeof(int) * 2 * G, hipMemcpyHostToDevice, s));
+    all_d = lists_d.p;
+    active_d = lists_d.p + G;
+    active_h = lists_h + G;
+  }
+  // ---- LSQR as a piece of its own: GroupDiff::run solves once over all members, GroupRefine (refine_batch.hpp) once per Newton step
+  // over the members that still step.  The tables (the caller sets the products' gx from its members' row blocks and uploads) ...
+  void size_lsqr(const DprojPlan &p0, size_t SG, int nbN) {
+    t_start.resize(SG); t_lsqr_v.resize(SG); t_lsqr_u.resize(SG);
+    t_start.gx = t_lsqr_v.gx = t_lsqr_u.gx = nbN;
+    for (ProdTabs *p : {&pv, &pu}) {
+      p->dp.size(p0, SG);
+      p->ar.resize(SG); p->at.resize(SG);
+      if (has_P) p->pf.resize(SG);
+    }
+    t_gather_fl.resize(SG); t_gather_fl.gx = 1;
+  }
+  // ... member g's records: the same whatever the direction, over the wiring's two products on lane d of w
+  void set_lsqr(int g, const ScsHipWork *w, DiffLane &d, const DprojPlan &plan, const DiffWiring &wr, int nbN, double tol) {
+    const int *done = d.fl.p + LF_DONE;
+    t_start.set(g, d.uh.p, wr.start_add[0], wr.start_add[1], n, N, d.x.p, d.w.p, d.partU.p, d.st.p, d.fl.p);
+    pv.set(g, w, plan, wr.pv, done);
+    pu.set(g, w, plan, wr.pu, done);
+    t_lsqr_v.set(g, wr.pv.read, d.vh.p, (const double *)d.w.p, d.x.p, n, N, (const double *)d.partU.p, nbN, d.partV.p, d.partX.p, d.st.p, d.fl.p);
+    t_lsqr_u.set(g, wr.pu.read, d.uh.p, (const double *)d.vh.p, d.w.p, n, N, (const double *)d.partV.p, (const double *)d.partX.p, nbN,
+                 d.partU.p, d.st.p, d.fl.p, tol);
+    t_gather_fl.set(g, (const int *)d.fl.p, flags_d.p + (size_t)g * LF_COUNT, (int)LF_COUNT);
+  }
+  // ... and the solve: the members active_h[0 .. na), each from the right-hand side in its uh to the answer in its x, in chunks of
+  // iterations between looks at the gathered flags.  list_changed: the caller rewrote the pinned active list (after a synchronisation
+  // of the stream), the device's copy follows before the first launch.  Leaves every member's flag block in flags_h.
+  void lsqr_run(int na, bool list_changed, long cap) {
+    auto push_list = [&] {  // the pinned active list was rewritten or compacted: the device's copy follows before the next launch
+      if (list_changed) HIP_CHECK(hipMemcpyAsync(active_d, active_h, sizeof(int) * (size_t)na, hipMemcpyHostToDevice, s));
+      list_changed = false;
+    };
+    push_list();
+    go(t_start, active_d, na);
+    auto step_v = [&](int k) { go_prod(pv, active_d, na); go_k(t_lsqr_v, active_d, na, k); };
+    auto step_u = [&](int k) {  // (the first launches after every look at the flags)
+      push_list();
+      go_prod(pu, active_d, na);
+      go_k(t_lsqr_u, active_d, na, k);
+    };
+    lsqr_drive(cap, step_u, step_v, [&] {
+      // Only the members still iterating are gathered, but the whole of flags_d comes back.  That is safe: a member's row of flags_d
+      // is written by this gather alone, and a member is in the gather of the look that first finds it done — after which its device
+      // block no longer changes (d_lsqr_v / d_lsqr_u return on the done flag), so the row it left is its final one.  Rows of members
+      // outside this solve (GroupRefine: members that stopped stepping) hold the flags of the last solve they took part in; callers read
+      // the rows of the members they passed in and no others.  Finished members leave the active list.
+      go(t_gather_fl, active_d, na);
+      HIP_CHECK(hipMemcpyAsync(flags_h, flags_d.p, sizeof(int) * LF_COUNT * G, hipMemcpyDeviceToHost, s));
+      sync();  // (the pinned list may be rewritten)
+      int keep = 0;
+      for (int i = 0; i < na; ++i)
+        if (!flags_h[(size_t)active_h[i] * LF_COUNT + LF_DONE]) active_h[keep++] = active_h[i];
+      list_changed = list_changed || keep != na;
+      na = keep;
+      return na == 0;
+    });
   }
 
   // The caller holds every member's mutex, has selected the device, refused bad arguments (diff_check) and run diff_alloc /
@@ -223,16 +299,7 @@ struct GroupDiff {
     lane_tile = g_diff_lane_tile.load() == 8 ? 8 : 4;
     const int GP = one_work ? 1 : G;  // members that prepare: the first of each workspace
 
-    HIP_CHECK(hipHostMalloc((void **)&flags_h, sizeof(int) * LF_COUNT * G));
-    HIP_CHECK(hipHostMalloc((void **)&lists_h, sizeof(int) * 2 * G));
-    HIP_CHECK(hipHostMalloc((void **)&st_h, sizeof(double) * L_COUNT * G));
-    flags_d.alloc((size_t)LF_COUNT * G);
-    st_d.alloc((size_t)L_COUNT * G);
-    lists_d.alloc((size_t)2 * G);
-    for (int g = 0; g < G; ++g) lists_h[g] = lists_h[G + g] = g;
-    HIP_CHECK(hipMemcpyAsync(lists_d.p, lists_h, sizeof(int) * 2 * G, hipMemcpyHostToDevice, s));
-    const int *all_d = lists_d.p;
-    int *active_d = lists_d.p + G, *active_h = lists_h + G;
+    alloc_lists();
 
     // ---- the members' cone plans ----
     plans.clear();
@@ -273,14 +340,7 @@ struct GroupDiff {
       rhs1.size(p0, SG);
       t_fwd_out.resize(SG); t_fwd_out.gx = nbN;
     }
-    t_start.resize(SG); t_lsqr_v.resize(SG); t_lsqr_u.resize(SG);
-    t_start.gx = t_lsqr_v.gx = t_lsqr_u.gx = nbN;
-    for (ProdTabs *p : {&pv, &pu}) {
-      p->dp.size(p0, SG);
-      p->ar.resize(SG); p->at.resize(SG);
-      if (has_P) p->pf.resize(SG);
-    }
-    t_gather_fl.resize(SG); t_gather_fl.gx = 1;
+    size_lsqr(p0, SG, nbN);
     t_gather_st.resize(SG); t_gather_st.gx = 1;
 
     int gx_ar = 0, gx_at = 0, gx_pf = 0, gx_ga = 0, gx_gp = 0;
@@ -309,7 +369,6 @@ struct GroupDiff {
         t_psd_gather.set(g, plan.psd, (const double *)scr, plan.vh);
       }
       const DiffWiring wr = diff_wiring(w, a, ln);
-      const int *done = d.fl.p + LF_DONE;
       // right-hand side and results: the kernels of the call's direction
       if (adjoint) {
         t_adj_in.set(g, a.in[0], a.in[1], a.in[2], D, E, sigma, n, m, d.uh.p, wr.gyh, wr.gsh);
@@ -343,14 +402,7 @@ struct GroupDiff {
         rhs1.set(g, plan, wr.fin, nullptr);
         t_fwd_out.set(g, (const double *)d.x.p, (const double *)d.dW.p, (const double *)d.dWmI.p, D, E, sigma, n, m, a.out[0], a.out[1], a.out[2]);
       }
-      // LSQR: the same records whatever the direction, over the wiring's two products
-      t_start.set(g, d.uh.p, wr.start_add[0], wr.start_add[1], n, N, d.x.p, d.w.p, d.partU.p, d.st.p, d.fl.p);
-      pv.set(g, w, plan, wr.pv, done);
-      pu.set(g, w, plan, wr.pu, done);
-      t_lsqr_v.set(g, wr.pv.read, d.vh.p, (const double *)d.w.p, d.x.p, n, N, (const double *)d.partU.p, nbN, d.partV.p, d.partX.p, d.st.p, d.fl.p);
-      t_lsqr_u.set(g, wr.pu.read, d.uh.p, (const double *)d.vh.p, d.w.p, n, N, (const double *)d.partV.p, (const double *)d.partX.p, nbN,
-                   d.partU.p, d.st.p, d.fl.p, lim.tol);
-      t_gather_fl.set(g, (const int *)d.fl.p, flags_d.p + (size_t)g * LF_COUNT, (int)LF_COUNT);
+      set_lsqr(g, w, d, plan, wr, nbN, lim.tol);
       t_gather_st.set(g, (const double *)d.st.p, st_d.p + (size_t)g * L_COUNT, (long)L_COUNT);
     }
     for (ProdTabs *p : {&pv, &pu}) { p->ar.gx = gx_ar; p->at.gx = gx_at; p->pf.gx = gx_pf; }
@@ -386,30 +438,8 @@ struct GroupDiff {
       go(t_pert_eff, all_d, G);
       go(t_fwd_in, all_d, G);
     }
-    go(t_start, all_d, G);
-
-    // ---- LSQR: chunks of iterations between looks at the gathered flags ----
-    int na = G;  // members of the active list
-    bool list_changed = false;  // the pinned active list was compacted: the device's copy follows before the next step
-    auto step_v = [&](int k) { go_prod(pv, active_d, na); go_k(t_lsqr_v, active_d, na, k); };
-    auto step_u = [&](int k) {  // (the first launches after every look at the flags)
-      if (list_changed) HIP_CHECK(hipMemcpyAsync(active_d, active_h, sizeof(int) * (size_t)na, hipMemcpyHostToDevice, s));
-      list_changed = false;
-      go_prod(pu, active_d, na);
-      go_k(t_lsqr_u, active_d, na, k);
-    };
-    lsqr_drive(lim.cap, step_u, step_v, [&] {
-      // every member's flags (a finished member's block no longer changes); finished members leave the active list
-      go(t_gather_fl, all_d, G);
-      HIP_CHECK(hipMemcpyAsync(flags_h, flags_d.p, sizeof(int) * LF_COUNT * G, hipMemcpyDeviceToHost, s));
-      sync();  // (the pinned list may be rewritten)
-      int keep = 0;
-      for (int i = 0; i < na; ++i)
-        if (!flags_h[(size_t)active_h[i] * LF_COUNT + LF_DONE]) active_h[keep++] = active_h[i];
-      list_changed = list_changed || keep != na;
-      na = keep;
-      return na == 0;
-    });
+    // ---- LSQR over all members (the identity list is on the device) ----
+    lsqr_run(G, false, lim.cap);
     go(t_gather_st, all_d, G);
     HIP_CHECK(hipMemcpyAsync(st_h, st_d.p, sizeof(double) * L_COUNT * G, hipMemcpyDeviceToHost, s));
 

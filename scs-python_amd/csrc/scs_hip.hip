@@ -53,6 +53,7 @@
 #include "refine.hpp"
 #include "spmv_lanes.hpp"
 #include "diff_batch.hpp"
+#include "refine_batch.hpp"
 #include "grad_shared.hpp"
 
 // ================================================================ C ABI
@@ -700,6 +701,7 @@ int scs_hip_diff_batch_plan(ScsWork **works, scs_int count, int want_dA, int wan
   return groups;
 }
 long scs_hip_diff_group_launches(void) { return g_diff_group_launches.load(); }
+long scs_hip_diff_group_syncs(void) { return g_diff_group_syncs.load(); }
 
 // the two outputs of scs_hip_adjoint_shared[_device]: ONE vector each for all members (csrc/grad_shared.hpp); nullptr = not wanted
 struct SharedSum {
@@ -928,6 +930,94 @@ scs_int scs_hip_refine(ScsWork *w, ScsSolution *sol, const ScsHipRefineOpts *opt
 }
 scs_int scs_hip_refine_device(ScsWork *w, ScsSolution *sol_dev, const ScsHipRefineOpts *opts, ScsHipRefineInfo *info) {
   return refine_entry(w, sol_dev, opts, info, /*dev=*/true, "scs_hip_refine_device");
+}
+
+// ---- the polish of a batch (include/scs_hip.h; csrc/refine_batch.hpp) ----
+// Locking, stream redirection and grouping are diff_batch_entry's (plan_diff_batch with no matrix gradients requested); the refusals
+// and each member's hand-over are refine_entry's.
+static scs_int refine_batch_entry(ScsWork **works, ScsSolution **sols, const ScsHipRefineOpts *o, ScsHipRefineInfo **infos, scs_int count, bool dev,
+                                  const char *who) {
+  set_last_error("");
+  if (!diff_batch_members_ok(works, count, who)) return -1;
+  std::vector<std::unique_lock<std::mutex>> locks;
+  std::vector<hipStream_t> saved;
+  std::vector<int> restored;
+  scs_int rc = 0;
+  try {
+    {  // member mutexes in ADDRESS order (as diff_batch_entry)
+      std::vector<int> order((size_t)count);
+      std::iota(order.begin(), order.end(), 0);
+      std::sort(order.begin(), order.end(), [&](int a, int b) { return std::less<ScsHipWork *>()(works[a], works[b]); });
+      for (int j : order) locks.emplace_back(works[j]->mtx);
+    }
+    // every member's refusals, before any device work
+    for (int i = 0; i < count; ++i) {
+      const ScsHipWork *w = works[i];
+      const std::string member = std::string(who) + ": member " + std::to_string(i);
+      std::string why = diff_refusal(w);
+      if (why.empty() && w->device != works[0]->device) why = "the members of a batch live on one device";
+      if (why.empty() && o && o->tol != o->tol) why = "tol is NaN";
+      if (!why.empty()) throw std::runtime_error(member + ": " + why);
+      const ScsSolution *sol = sols ? sols[i] : nullptr;
+      if (dev && sol) {
+        if (sol->x) check_device_vector(sol->x, w->device, member.c_str(), "sol_dev->x");
+        if (sol->y) check_device_vector(sol->y, w->device, member.c_str(), "sol_dev->y");
+        if (sol->s) check_device_vector(sol->s, w->device, member.c_str(), "sol_dev->s");
+      }
+    }
+    HIP_CHECK(hipSetDevice(works[0]->device));
+    hipStream_t s = works[0]->stream;
+    const std::vector<int> want((size_t)count, 0);
+    for (const std::vector<int> &job : plan_diff_batch(works, (int)count, want)) {
+      if (job.size() == 1) {
+        ScsHipWork *w = works[job[0]];
+        ScsHipWork::ScratchTurn turn(w);
+        refine_impl(w, o, infos ? infos[job[0]] : nullptr);
+        continue;
+      }
+      GroupRefine gr;
+      gr.gd.s = s;
+      for (int j : job) {  // every member's kernels go to the group's stream for the duration of the call
+        saved.push_back(works[j]->stream);
+        restored.push_back(j);
+        works[j]->stream = s;
+      }
+      for (int j : job) {
+        refine_alloc(works[j]);
+        gr.gd.W.push_back(works[j]);
+        gr.infos.push_back(infos ? infos[j] : nullptr);
+      }
+      gr.run(o);
+      for (size_t k = 0; k < restored.size(); ++k) works[restored[k]]->stream = saved[k];
+      saved.clear();
+      restored.clear();
+    }
+    // the hand-over of refine_entry, member by member
+    for (int i = 0; i < count; ++i) {
+      ScsHipWork *w = works[i];
+      ScsSolution *sol = sols ? sols[i] : nullptr;
+      if (!sol) continue;
+      if (dev) {
+        w->hand_over_solution(sol);
+      } else {
+        if (sol->x) w->solx.download(sol->x, w->n, w->stream);
+        if (sol->y) w->soly.download(sol->y, w->m, w->stream);
+        if (sol->s) w->sols.download(sol->s, w->m, w->stream);
+        HIP_CHECK(hipStreamSynchronize(w->stream));
+      }
+    }
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    rc = -1;
+  }
+  for (size_t k = 0; k < restored.size(); ++k) works[restored[k]]->stream = saved[k];
+  return rc;
+}
+scs_int scs_hip_refine_batch(ScsWork **w, ScsSolution **sol, const ScsHipRefineOpts *opts, ScsHipRefineInfo **info, scs_int count) {
+  return refine_batch_entry(w, sol, opts, info, count, /*dev=*/false, "scs_hip_refine_batch");
+}
+scs_int scs_hip_refine_batch_device(ScsWork **w, ScsSolution **sol_dev, const ScsHipRefineOpts *opts, ScsHipRefineInfo **info, scs_int count) {
+  return refine_batch_entry(w, sol_dev, opts, info, count, /*dev=*/true, "scs_hip_refine_batch_device");
 }
 
 // ---- several directions at one solution (include/scs_hip.h; lanes: csrc/lsqr.hpp, csrc/diff_batch.hpp, csrc/spmv_lanes.hpp) ----

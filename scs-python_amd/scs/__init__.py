@@ -301,6 +301,17 @@ class SCS(object):
     """`refine` with "x", "y", "s" as fresh float64 torch tensors on the solver's GPU; same bits."""
     return self._solver.refine_device(tol, max_steps, lsqr_tol, lsqr_max_iters)
 
+  def refine_many(self, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None, K=None):
+    """`refine` of the K problems the last `solve_many` solved (K=None: all of them), polished in lock step (`refine_batch`).  Returns
+    {"x": (K, n), "y": (K, m), "s": (K, m), "info": [K dicts]}, row k with the bits `refine` gives on problem k alone.  Every problem's
+    polished point becomes its solution: a following `adjoint_many` and a warm-started `solve_many` read it.  ValueError for a K above
+    what `solve_many` has solved, and for a problem `refine` would refuse (with its index, "member k")."""
+    return self._solver.refine_many(tol, max_steps, lsqr_tol, lsqr_max_iters, K=K)
+
+  def refine_many_device(self, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None, K=None):
+    """`refine_many` with "x", "y", "s" as fresh (K, .) float64 torch tensors on the solver's GPU; same bits."""
+    return self._solver.refine_many_device(tol, max_steps, lsqr_tol, lsqr_max_iters, K=K)
+
 
   def adjoint_many(self, dx=None, dy=None, ds=None, want=("b", "c"), tol=1e-8, max_iters=None, reduce=None):
     """`adjoint` of the K problems the last `solve_many` solved, differentiated in lock step: dx (K, n), dy (K, m), ds (K, m), None = 0.
@@ -381,11 +392,14 @@ def batch_plan(solvers):
   return _scs_hip.batch_plan(raw)
 
 
-def _raw_solvers(solvers, who):
+def _raw_solvers(solvers, who, as_list=False):
+  """the backend objects of a batch; as_list: the batch must be a list or tuple, and a refusal names the member's index"""
+  if as_list and not isinstance(solvers, (list, tuple)):
+    raise TypeError("%s expects a list of solvers, not %s" % (who, type(solvers).__name__))
   raw = []
-  for sv in solvers:
+  for i, sv in enumerate(solvers):
     if not isinstance(sv, SCS) or not isinstance(sv._solver, _scs_hip.SCS):
-      raise TypeError("%s needs scs.SCS objects of the HIP backend" % who)
+      raise TypeError("%s%s needs scs.SCS objects of the HIP backend" % (who, ": member %d:" % i if as_list else ""))
     raw.append(sv._solver)
   return raw
 
@@ -413,6 +427,19 @@ def derivative_batch_device(solvers, db=None, dc=None, tol=1e-8, max_iters=None,
   return _scs_hip.derivative_batch_device(_raw_solvers(solvers, "derivative_batch_device"), db, dc, tol, max_iters, dA=dA, dP=dP)
 
 
+def refine_batch(solvers, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None):
+  """`SCS.refine` of several solved `SCS` objects as one batch: equally shaped problems are polished in lock step — one launch per kernel
+  and one host synchronisation per evaluation for the group — each with its own number of steps, halvings and stop reason.  The options
+  hold for every solver.  Returns one dict per solver, with the bits `.refine()` gives (info["time_ms"] is the group's); every solver's
+  polished point becomes its solution.  A refusal names the solver's index ("member i") and leaves every solver as it was."""
+  return _scs_hip.refine_batch(_raw_solvers(solvers, "refine_batch", as_list=True), tol, max_steps, lsqr_tol, lsqr_max_iters)
+
+
+def refine_batch_device(solvers, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None):
+  """`refine_batch` with every solver's "x", "y", "s" as fresh float64 torch tensors on the solvers' GPU; same bits."""
+  return _scs_hip.refine_batch_device(_raw_solvers(solvers, "refine_batch_device", as_list=True), tol, max_steps, lsqr_tol, lsqr_max_iters)
+
+
 def diff_batch_plan(solvers, want=("b", "c")):
   """How `adjoint_batch(solvers, want=want)` would split the batch: one int per solver, the index of the group it would share launches
   with, or -1 where it is differentiated alone (a shape of its own, a pass or slab matrix layout, a PSD block above order 32, a box cone above 16384 rows)."""
@@ -422,3 +449,8 @@ def diff_batch_plan(solvers, want=("b", "c")):
 def diff_group_launches():
   """Grouped launches the batch derivative entries have issued in this process."""
   return _scs_hip.diff_group_launches()
+
+
+def diff_group_syncs():
+  """Host synchronisations the groups of the batch derivative and refine entries have made in this process."""
+  return _scs_hip.diff_group_syncs()

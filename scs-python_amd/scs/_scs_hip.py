@@ -283,6 +283,11 @@ def _load():
     for fn in (lib.scs_hip_refine, lib.scs_hip_refine_device):
         fn.restype = c_int
         fn.argtypes = [C.c_void_p, C.POINTER(_ScsSolution), C.POINTER(_ScsHipRefineOpts), C.POINTER(_ScsHipRefineInfo)]
+    for fn in (lib.scs_hip_refine_batch, lib.scs_hip_refine_batch_device):
+        fn.restype = c_int
+        fn.argtypes = [_PV, C.POINTER(C.POINTER(_ScsSolution)), C.POINTER(_ScsHipRefineOpts), C.POINTER(C.POINTER(_ScsHipRefineInfo)), c_int]
+    lib.scs_hip_diff_group_syncs.restype = C.c_long
+    lib.scs_hip_diff_group_syncs.argtypes = []
     lib.scs_hip_diff_lane_tile.restype = C.c_int
     lib.scs_hip_diff_lane_tile.argtypes = [C.c_int]
     lib.scs_hip_dproj_cone.restype = c_int
@@ -701,6 +706,7 @@ class SCS(object):
         self._lock = threading.Lock()
         self._fn_keep = []
         self._many = []  # solve_many's clones (members 1 .. K-1), kept for the next call
+        self._many_K = None  # members of the last solve_many (refine_many's default)
         self._pattern = None  # {"A": (indptr, indices), "P": ... or None}: what update_matrix checks against
 
     def _shape(self, m, n):
@@ -839,6 +845,7 @@ class SCS(object):
         while len(pool) < K - 1:
             pool.append(self.clone())
         members = [self] + pool[:K - 1]
+        self._many_K = K
         for i, sv in enumerate(members):
             bi, ci = rows["b"][i] if b is not None else None, rows["c"][i] if c is not None else None
             if bi is not None or ci is not None:
@@ -926,6 +933,7 @@ class SCS(object):
         while len(pool) < K - 1:
             pool.append(self.clone())
         members = [self] + pool[:K - 1]
+        self._many_K = K
         for i, sv in enumerate(members):
             bi, ci = rows["b"][i] if b is not None else None, rows["c"][i] if c is not None else None
             if bi is not None or ci is not None:
@@ -1228,6 +1236,22 @@ class SCS(object):
             sol = _ScsSolution(C.cast(out["x"].data_ptr(), _PD), C.cast(out["y"].data_ptr(), _PD), C.cast(out["s"].data_ptr(), _PD))
             out["info"] = self._refine_call(_lib.scs_hip_refine_device, sol, opts)
         return out
+
+    def refine_many(self, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None, K=None):
+        """`refine` of the first K members the last `solve_many` solved (None: all of them; before any `solve_many`: this solver
+        alone), in lock step (`refine_batch`).  Returns
+        {"x": (K, n), "y": (K, m), "s": (K, m), "info": [K dicts]}, row k with the bits of `refine` on member k.  Every member's
+        polished point becomes its resident solution: `adjoint_many` and a warm-started `solve_many` read it."""
+        opts = _refine_opts(tol, max_steps, lsqr_tol, lsqr_max_iters)
+        res = _refine_list(self._many_members(self._many_K if K is None else K), opts, False)
+        return {"x": np.stack([r["x"] for r in res]), "y": np.stack([r["y"] for r in res]), "s": np.stack([r["s"] for r in res]),
+                "info": [r["info"] for r in res]}
+
+    def refine_many_device(self, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None, K=None):
+        """`refine_many` with "x", "y", "s" as fresh (K, .) float64 torch tensors on the solver's GPU, whose rows the one grouped
+        call writes; same bits."""
+        opts = _refine_opts(tol, max_steps, lsqr_tol, lsqr_max_iters)
+        return _refine_list(self._many_members(self._many_K if K is None else K), opts, True, stacked=True)
 
     def _set_profiling(self, on):
         with self._lock:
@@ -1883,6 +1907,89 @@ def data_perturbation(solver, dA=None, dP=None):
 def diff_group_launches():
     """Grouped launches the batch derivative entries have issued in this process (tests, tools/adjoint_batch_bench.py)."""
     return int(_lib.scs_hip_diff_group_launches())
+
+
+def diff_group_syncs():
+    """Host synchronisations the groups of the batch derivative and refine entries have made in this process (tools)."""
+    return int(_lib.scs_hip_diff_group_syncs())
+
+
+# ---------------------------------------------------------------- Newton polish of a batch (include/scs_hip.h: scs_hip_refine_batch)
+def _refine_solvers(solvers, who):
+    """the list a refine_batch call names: a list or tuple of distinct backend SCS objects, each refusal with its member's index"""
+    if not isinstance(solvers, (list, tuple)):
+        raise TypeError("%s expects a list of solvers, not %s" % (who, type(solvers).__name__))
+    if not solvers:
+        raise ValueError("%s: the list of solvers is empty: there is no member 0" % who)
+    seen = set()
+    for i, sv in enumerate(solvers):
+        if not isinstance(sv, SCS):
+            raise TypeError("%s: member %d: expects scs._scs_hip.SCS objects, not %s" % (who, i, type(sv).__name__))
+        if id(sv) in seen:
+            raise ValueError("%s: member %d: a solver appears twice" % (who, i))
+        seen.add(id(sv))
+    return list(solvers)
+
+
+def _refine_list(solvers, opts, device, stacked=False):
+    """ONE call of scs_hip_refine_batch[_device] over distinct members, under every member's lock.  Host: every member's x, y, s land
+    in its own result arrays (as `refine`) and come back as copies.  Device: fresh float64 torch tensors on the members' GPU — per
+    member, or (stacked: members of one shape) three (K, .) stacks whose rows the call writes.  Returns the list of result dicts, or
+    the stacked dict with the list of infos."""
+    K = len(solvers)
+    if device:
+        import torch
+        devs = set(sv._device_index() for sv in solvers)
+        if len(devs) > 1:
+            raise ValueError("refine_batch_device: the solvers live on different GPUs")
+        dev = devs.pop()
+        tdev = torch.device("cuda", dev)
+        if stacked:
+            out = {"x": torch.empty((K, solvers[0].n), dtype=torch.float64, device=tdev),
+                   "y": torch.empty((K, solvers[0].m), dtype=torch.float64, device=tdev),
+                   "s": torch.empty((K, solvers[0].m), dtype=torch.float64, device=tdev)}
+            rows = [{k: out[k][i] for k in "xys"} for i in range(K)]
+        else:
+            rows = [{"x": torch.empty(sv.n, dtype=torch.float64, device=tdev), "y": torch.empty(sv.m, dtype=torch.float64, device=tdev),
+                     "s": torch.empty(sv.m, dtype=torch.float64, device=tdev)} for sv in solvers]
+    with _locked(solvers) as works:
+        if device:
+            _sync_torch_stream(dev)
+            sols = [_ScsSolution(C.cast(r["x"].data_ptr(), _PD), C.cast(r["y"].data_ptr(), _PD), C.cast(r["s"].data_ptr(), _PD)) for r in rows]
+        else:
+            sols = [_ScsSolution(_pd(sv._x), _pd(sv._y), _pd(sv._s)) for sv in solvers]
+        solp = (C.POINTER(_ScsSolution) * K)(*[C.pointer(so) for so in sols])
+        infos = [_ScsHipRefineInfo() for _ in solvers]
+        infp = (C.POINTER(_ScsHipRefineInfo) * K)(*[C.pointer(io) for io in infos])
+        fn = _lib.scs_hip_refine_batch_device if device else _lib.scs_hip_refine_batch
+        rc = fn(works, solp, C.byref(opts), infp, K)
+        err = last_error() if rc != 0 else ""
+        if rc == 0 and not device:
+            rows = [{"x": sv._x.copy(), "y": sv._y.copy(), "s": sv._s.copy()} for sv in solvers]
+    if rc != 0:
+        raise ValueError("libscs_hip: " + err)
+    dicts = [_refine_info_dict(io) for io in infos]
+    if stacked:
+        out["info"] = dicts
+        return out
+    for r, d in zip(rows, dicts):
+        r["info"] = d
+    return rows
+
+
+def refine_batch(solvers, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None):
+    """`refine` of several solved backend `SCS` objects in one call (include/scs_hip.h: scs_hip_refine_batch): equally shaped members
+    are polished in lock step — one launch per kernel and one host synchronisation per evaluation for the group — each with its own
+    number of steps, halvings and stop reason.  Returns the list of dicts `refine` would return for each, with the same bits
+    (info["time_ms"] is the group's).  The options hold for every member."""
+    solvers = _refine_solvers(solvers, "refine_batch")
+    return _refine_list(solvers, _refine_opts(tol, max_steps, lsqr_tol, lsqr_max_iters), False)
+
+
+def refine_batch_device(solvers, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None):
+    """`refine_batch` with every member's "x", "y", "s" as fresh float64 torch tensors on the solvers' GPU; same bits."""
+    solvers = _refine_solvers(solvers, "refine_batch_device")
+    return _refine_list(solvers, _refine_opts(tol, max_steps, lsqr_tol, lsqr_max_iters), True)
 
 
 # ---------------------------------------------------------------- kernel-level entry points (tests, bench)

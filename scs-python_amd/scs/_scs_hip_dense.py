@@ -38,3 +38,15 @@ def diff_batch_plan(solvers, want=("b", "c")):
 
 def diff_group_launches():
     return _scs_hip.diff_group_launches()
+
+
+def diff_group_syncs():
+    return _scs_hip.diff_group_syncs()
+
+
+def refine_batch(solvers, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None):
+    return _scs_hip.refine_batch(solvers, tol, max_steps, lsqr_tol, lsqr_max_iters)
+
+
+def refine_batch_device(solvers, tol=1e-9, max_steps=10, lsqr_tol=1e-8, lsqr_max_iters=None):
+    return _scs_hip.refine_batch_device(solvers, tol, max_steps, lsqr_tol, lsqr_max_iters)

@@ -13,7 +13,10 @@ the last forward and backward are left in `solver.autograd_info` / `solver.autog
 `refine_device(tol=solver.autograd_refine_tol)`, Newton steps on the optimality conditions (`SCS.refine`).  The layer returns the
 polished tensors and backward differentiates the polished, resident solution — a loose `eps` for the solve and a tight gradient.  A
 refusal of `refine_device` (a solve that did not end solved) comes through as its ValueError; the info dict of the polish is left in
-`solver.autograd_refine_info`.  `solve_many` does not refine.
+`solver.autograd_refine_info`.  `solve_many` honours the same switch: its forward calls `refine_many_device(tol=...)` after the solve
+— the K members are polished in lock step (`SCS.refine_many`) — returns the polished (K, .) tensors, backward differentiates the K
+polished solutions, and `solver.autograd_refine_info` holds the list of the K info dicts.  With the attribute unset (None) the layer
+makes exactly the calls it makes without it.
 
 A and P, when given, are float64 1-D tensors on the solver's GPU holding the stored VALUES of the matrices in the constructor's
 canonical order (sorted CSC; P: its upper triangle, an off-diagonal value standing for both mirror images) — the learnable parameters
@@ -117,6 +120,11 @@ class _SolveMany(torch.autograd.Function):
       out = solver.solve_many_device(b=B, c=C, warm_start=True, x=last[0], y=last[1], s=last[2])
     else:
       out = solver.solve_many_device(b=B, c=C, warm_start=False)
+    refine_tol = getattr(solver, "autograd_refine_tol", None)
+    if refine_tol is not None:  # polish the K resident solutions in lock step: backward then differentiates accurate fixed points
+      info = out["info"]
+      out = solver.refine_many_device(tol=refine_tol, K=int(B.shape[0]))
+      solver.autograd_refine_info, out["info"] = out["info"], info
     if ctx.matrix:
       solver._autograd_last_many = (out["x"].detach(), out["y"].detach(), out["s"].detach())
     return _solved(ctx, solver, out)
